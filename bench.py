@@ -15,10 +15,22 @@ Workloads (one step = one pass of the hot path over the rank's months, inputs HB
   records -> time-series stage on the gathered series -> RCCL SUM all-reduce of the
   predictive records -> predictive summary.  Both collectives are inside the timed region.
 
-value = all ranks' firm-month rows / max-over-ranks time (weak scaling).  At N=1 the line
-also carries the C5 per-rank shard through ShardedStep (`c5_rank_shard`, the N=1 point of
-the C5 scaling curve); at N>1 it also carries the headline panel weak-scaled
-(`headline_weak`, 600 months x 5,000 firms per rank, same exchanges).
+value = all ranks' firm-month rows / max-over-ranks time (weak scaling).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that figure needs: it
+generates the panel, warms up, times exactly N steps and prints the result line
+(`ms_per_step` = milliseconds per timed step).  `--dump-outputs DIR` also writes what the last
+timed step returned (monthly records, status words, moments, the Fama-MacBeth and the
+predictive summaries) as DIR/<name>.npy in float64, finite throughout (NaN padding is written
+as 0 and marked in DIR/<name>_nonfinite.npy, see dump_outputs); the panel is seeded, so two builds run
+with the same arguments can be compared array for array.
+
+`--full` adds every side measurement to the line: the per-kernel device times and the Gram's
+roofline (runs of their own), the measured HBM read / copy peaks, the winsorize/standardize
+variant, the CPU baselines, the firm-characteristic stage and, at N=1, the C5 per-rank shard
+through ShardedStep (`c5_rank_shard`, the N=1 point of the C5 scaling curve); at N>1 the
+headline panel weak-scaled (`headline_weak`, 600 months x 5,000 firms per rank, same
+exchanges).  The --no-* switches trim a --full run.
 """
 import argparse
 import json
@@ -49,6 +61,12 @@ def parse(argv=None):
                          "WORLD_SIZE, else 1)")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (per-kernel times and roofline, measured HBM "
+                         "peaks, standardize variant, CPU baselines, firm characteristics, the C5 shard "
+                         "at N=1, headline_weak at N>1); the --no-* switches below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--workload", choices=("headline", "c5"), default=None,
                     help="default: headline at N=1, c5 at N>1")
     ap.add_argument("--months", type=int, default=600, help="headline months per GPU")
@@ -76,7 +94,10 @@ def parse(argv=None):
     ap.add_argument("--launch-probe", action="store_true",
                     help="test aid: start the ranks as for --gpus N, join a gloo group on the CPU, "
                          "print rank 0's {n_gpus, dist_world} and exit (no GPU call)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps needs at least one timed step")
+    return args
 
 
 class LaunchError(SystemExit):
@@ -159,6 +180,46 @@ def timed_steps(step, steps, warmup, graph, world, dev):
         from fmcore import dist as D
         dt = D.max_over_ranks(dt, dev)
     return dt, out
+
+
+DUMP_BUDGET = 64 * 1000 * 1000   # bytes of --dump-outputs, all arrays together
+
+
+def dump_outputs(out, path):
+    """Write the arrays the timed step returned -- (FMResult, Summary, predictive Summary),
+    as they stand after the last timed step -- as path/<name>.npy in float64 (status words
+    and counts are integers float64 holds exactly).  An array over its share of DUMP_BUDGET
+    is written as a fixed sample: the elements at seeded, sorted flat indices.
+
+    Every file holds finite numbers only.  The records and summaries pad each problem's
+    unused coefficient slots (K < pmax) with NaN, and an unfitted month's record is NaN: such
+    entries are written as 0.0 in <name>.npy and marked in a companion <name>_nonfinite.npy of
+    the same shape (0 finite, 1 NaN, 2 +inf, 3 -inf), written only where there are any, so
+    values and NaN pattern both compare between builds."""
+    gres, summ, psumm = out
+    arrs = {"rec": gres.rec, "status": gres.status}
+    if gres.moments is not None:
+        arrs["moments"] = gres.moments
+    for tag, s in (("summary", summ), ("pred_summary", psumm)):
+        if s is not None:
+            for f in ("mean", "se", "tstat", "nobs"):
+                arrs[f"{tag}_{f}"] = getattr(s, f)
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET // (2 * len(arrs)) // 8   # elements per array (and per companion)
+    written = []
+    for name, t in arrs.items():
+        a = t.detach().cpu().numpy().astype(np.float64)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(20140101).choice(a.size, cap, replace=False))
+            a = a.ravel()[idx]
+        code = np.where(np.isnan(a), 1.0, np.where(a == np.inf, 2.0, np.where(a == -np.inf, 3.0, 0.0)))
+        np.save(os.path.join(path, name + ".npy"), np.where(code == 0.0, a, 0.0))
+        written.append(name)
+        if code.any():
+            np.save(os.path.join(path, name + "_nonfinite.npy"), code)
+            written.append(name + "_nonfinite")
+    return sorted(written)
 
 
 def gen_panel(T, N, seed, month0, dev, E, planes=True):
@@ -268,15 +329,35 @@ def main():
     rows_local = T_loc * N
     dt, out = timed_steps(step, args.steps, args.warmup, not args.no_graph, world, dev)
     gres, summ, psumm = out
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the graph's static buffers still hold the last timed step
+        dumped = dump_outputs(out, args.dump_outputs)
     nfit = int(((gres.status & 1) != 0).sum().item())   # fitted (month, problem) pairs, all ranks
-    ksteps = max(3, min(args.steps, 10)) if workload == "headline" else 2
-    dom, dom_ms, dom_bytes, achieved, dev_ms, kern, sel_roof = kernel_roofline(step, panel, E, ksteps)
-    traffic = _pmc_traffic(dom) if workload == "headline" else None
     ms_step = dt / args.steps * 1e3
     whole = rows_local * B_ROW / (ms_step * 1e-3) / 1e9   # per rank (each rank reads its shard)
-
-    read_peak = _stream_read_gbs(E, dev)
-    copy_peak = _stream_copy_gbs(E, dev)
+    roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "whole_pass": {"bytes_per_row": B_ROW, "achieved": whole, "frac": whole / HBM_PEAK_GBS,
+                               "ms_per_step": ms_step, "per": "rank"}}
+    dev_ms = kern = None
+    if args.full:
+        ksteps = max(3, min(args.steps, 10)) if workload == "headline" else 2
+        dom, dom_ms, dom_bytes, achieved, dev_ms, kern, sel_roof = kernel_roofline(step, panel, E, ksteps)
+        traffic = _pmc_traffic(dom) if workload == "headline" else None
+        read_peak = _stream_read_gbs(E, dev)
+        copy_peak = _stream_copy_gbs(E, dev)
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic["bytes"] if traffic else None,
+                    "traffic_ratio": traffic["bytes"] / dom_bytes if traffic else None,
+                    "traffic_source": traffic["source"] if traffic else None,
+                    "bytes_per_launch": dom_bytes, "avg_launch_ms": dom_ms,
+                    "measured_read_peak": read_peak, "frac_of_measured_read": achieved / read_peak,
+                    "measured_read_peak_source": "fm_stream_probe, 1 GiB, 16-B loads (bench._stream_read_gbs)",
+                    "measured_copy_peak": copy_peak, "frac_of_measured_copy": achieved / copy_peak,
+                    "measured_copy_peak_source": "fm_stream_copy_probe, 1 GiB read + 1 GiB written, 16-B accesses (bench._stream_copy_gbs)",
+                    "whole_pass": roofline["whole_pass"],
+                    "select": sel_roof}
     result = {
         "metric": METRIC,
         "value": rows_local * world * args.steps / dt,
@@ -299,23 +380,11 @@ def main():
                                                         "predictive records (timed)" if world > 1 else ""),
         },
         "regressions_per_s": nfit * args.steps / dt,
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic["bytes"] if traffic else None,
-                     "traffic_ratio": traffic["bytes"] / dom_bytes if traffic else None,
-                     "traffic_source": traffic["source"] if traffic else None,
-                     "bytes_per_launch": dom_bytes, "avg_launch_ms": dom_ms,
-                     "measured_read_peak": read_peak, "frac_of_measured_read": achieved / read_peak,
-                     "measured_read_peak_source": "fm_stream_probe, 1 GiB, 16-B loads (bench._stream_read_gbs)",
-                     "measured_copy_peak": copy_peak, "frac_of_measured_copy": achieved / copy_peak,
-                     "measured_copy_peak_source": "fm_stream_copy_probe, 1 GiB read + 1 GiB written, 16-B accesses (bench._stream_copy_gbs)",
-                     "whole_pass": {"bytes_per_row": B_ROW, "achieved": whole, "frac": whole / HBM_PEAK_GBS,
-                                    "ms_per_step": ms_step, "per": "rank"},
-                     "select": sel_roof},
-        "kernel_ms": {k: round(v, 4) for k, v in dev_ms.items()},
+        "full": args.full,
+        "roofline": roofline,
         "lib_sha16": _lib_sha(),
-        "kernel_ms_eager_events": {k: round(v, 4) for k, v in kern.items()},
         "graph": not args.no_graph,
+        "dumped_outputs": dumped,
         "ingest": {"gen_ms": panel.gen_ms, "layout": "planes" if panel.cols is None else "f64",
                    "panel_hbm_bytes": _panel_bytes(panel),
                    "note": "the panel generated in HBM directly in its layout (fm_gen_panel_planes: high / low "
@@ -325,22 +394,26 @@ def main():
         result["scaling_note"] = ("value at N>1 is the C5 workload; its N=1 point is the N=1 line's "
                                   "c5_rank_shard.rows_per_s (same per-rank shard), the headline's "
                                   "weak-scaled rate is headline_weak.value")
-    if world == 1 and workload == "headline" and not args.no_standardize:
+    full = args.full
+    if full:
+        result["kernel_ms"] = {k: round(v, 4) for k, v in dev_ms.items()}
+        result["kernel_ms_eager_events"] = {k: round(v, 4) for k, v in kern.items()}
+    if full and world == 1 and workload == "headline" and not args.no_standardize:
         result["standardize"] = standardize_stage(panel, args, E, LW, dev)
     if args.check and rank == 0 and world == 1 and workload == "headline":
         result["check"] = check_against_oracle(panel, gres, summ, args, LW)
-    if rank == 0 and world == 1 and workload == "headline" and not args.no_cpu:
+    if full and rank == 0 and world == 1 and workload == "headline" and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(panel, args, LW)
     del step, panel, out, gres, summ, psumm
     E.LAST_LAUNCH.clear()
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_chars:
+    if full and rank == 0 and world == 1 and not args.no_chars:
         result["firm_chars"] = firm_chars_stage(args, E)
         E.LAST_LAUNCH.clear()
         torch.cuda.empty_cache()
-    if world == 1 and workload == "headline" and not args.no_c5:
+    if full and world == 1 and workload == "headline" and not args.no_c5:
         result["c5_rank_shard"] = c5_shard_stage(args, E, LW, dev)
-    if world > 1 and workload == "c5" and not args.no_headline:
+    if full and world > 1 and workload == "c5" and not args.no_headline:
         p2, s2 = make_step(args.months, args.firms, args.seed, world, rank, dev, E, LW, planes=not args.no_planes)
         d2, o2 = timed_steps(s2, args.steps, args.warmup, not args.no_graph, world, dev)
         rows2 = args.months * args.firms

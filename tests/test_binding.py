@@ -79,7 +79,6 @@ BINDING_CELL = 'import sys; sys.path.insert(0, "<repo>/fm-returnprediction_amd")
                "from fmdrop import bind; bind.install()\n"
 
 
-@needs_ref
 def test_integration_md_shows_this_binding():
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for line in BINDING_CELL.strip().splitlines():

@@ -8,6 +8,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" || exit 1
 PT="python -u -m pytest -x -v -p no:cacheprovider --timeout 240 --timeout-method thread ${K:+-k \"$K\"}"
 PROF="cd /tmp && export TMPDIR=/tmp && rocprofv3"
+# these presets want the side measurements (kernel times, roofline, baselines, C5 shard) too
+BENCH_ARGS="--full $BENCH_ARGS"
 specs=()
 for s in "$@"; do
   case $s in
@@ -19,8 +21,8 @@ for s in "$@"; do
     quick)   specs+=("quick:::300:::python bench.py --no-cpu --no-chars --no-c5 --steps 20 $BENCH_ARGS");;
     scan)    specs+=("scan:::300:::python tools/size_scan.py");;
     split)   specs+=("split:::300:::python tools/split_scan.py");;
-    rehearse) specs+=("rehearse:::400:::python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --one-device --c5-months 400 --months 300");;
-    spawn)   specs+=("spawn:::400:::python bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --one-device --c5-months 400 --months 300 --no-headline");;
+    rehearse) specs+=("rehearse:::400:::python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --one-device --c5-months 400 --months 300");;
+    spawn)   specs+=("spawn:::400:::python bench.py --full --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --one-device --c5-months 400 --months 300 --no-headline");;
     tprobe)  specs+=("tprobe:::200:::FM_HIP_LIB=$R/build_variants/probe/libfm_hip.so python tools/tail_probe.py");;
     wgtime)  specs+=("wgtime:::200:::FM_HIP_LIB=$R/build_variants/wgtime/libfm_hip.so python tools/gram_wgtime.py");;
     kbench)  specs+=("kbench:::300:::python tools/kbench.py $KB_LIBS");;
