@@ -135,9 +135,6 @@ __global__ __launch_bounds__(CT) void firm_chars_kernel(fm_chars_args a, int nee
 // ---- rolling std --------------------------------------------------------------------------
 // tile shape (timing builds may override): 256 x 8 measured best -- 512 x 8 0.116, 256 x 16
 // 0.119, 512 x 4 0.179, 1024 x 4 0.205 vs 0.111 ms (profiles/r04/v11_stdbench_tile_sweep.log)
-#ifndef FM_STD_ABL
-#define FM_STD_ABL 0   // timing ablations only (wrong output): 1 no division / sqrt, 2 no first-window block sum, 3 staging + block stats only
-#endif
 #ifndef FM_STD_T
 #define FM_STD_T 256
 #endif
@@ -322,14 +319,6 @@ __global__ __launch_bounds__(ST_T) void rolling_std_kernel(const int64_t* __rest
     const int e0 = HP + t * ST_R;   // staged index of this thread's first row
     const int64_t i0 = b + t * ST_R;
     if (i0 >= n) return;
-#if FM_STD_ABL == 3
-    if (i0 + ST_R <= n) {
-#pragma unroll
-        for (int r = 0; r < ST_R; r += 2)
-            *reinterpret_cast<double2*>(out + i0 + r) = make_double2(xs[spad(e0 + r)] + bm2[t], xs[spad(e0 + r + 1)]);
-    }
-    return;
-#endif
     // first window: staged rows [lo, e0], lo = max(e0 - H, the firm's first row): the highest
     // firm-start bit at or below e0 (fs = -1 when the firm starts before the window)
     const int lo0 = e0 - H;
@@ -378,9 +367,6 @@ __global__ __launch_bounds__(ST_T) void rolling_std_kernel(const int64_t* __rest
         // (two chains), then single blocks: ~W / 32 + 6 states instead of ~W / 8
         int s = jlo + nh;
         const int se = t + nh;
-#if FM_STD_ABL == 2
-        s = se;
-#endif
         for (; s < se && (s & 3) != 0; ++s) acc4(2, bcnt[s], bmean[s], bm2[s]);
         for (; s + 8 <= se; s += 8) {
             acc4(0, scnt[s >> 2], smean[s >> 2], sm2[s >> 2]);
@@ -455,14 +441,10 @@ __global__ __launch_bounds__(ST_T) void rolling_std_kernel(const int64_t* __rest
                 rv = 0.0;   // pandas: every observation in the window is the same value
             } else {
                 const double c = (double)cnt;
-#if FM_STD_ABL == 1
-                rv = (s2 * c - s1 * s1) * scale;
-#else
                 // the division by c (c - 1) as a product with its tabled reciprocal (within an
                 // ulp of the quotient)
                 const double var = (s2 * c - s1 * s1) * ivar[cnt];
                 rv = sqrt(var > 0.0 ? var : 0.0) * scale;
-#endif
             }
         }
         res[r] = rv;

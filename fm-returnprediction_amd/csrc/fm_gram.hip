@@ -24,7 +24,7 @@ namespace {
 constexpr int GT = 256;
 constexpr int GNW = GT / WAVE;
 #ifndef FM_GRAM_MINW
-#define FM_GRAM_MINW (FM_GRAM_PF2 ? 2 : 3)
+#define FM_GRAM_MINW 3
 #endif
 constexpr int GRAM_MINW = FM_GRAM_MINW;   // waves per SIMD the register budget allows
 #ifndef FM_GRAM_WGTIME

@@ -19,27 +19,6 @@
 
 #include "fm_common.h"
 
-// A/B and ablation knobs: timing builds only (tools/kbench.py), never the shipped library
-#ifndef FM_AB_GRAM_NOMFMA
-#define FM_AB_GRAM_NOMFMA 0
-#endif
-#ifndef FM_AB_GRAM_NOLOAD
-#define FM_AB_GRAM_NOLOAD 0
-#endif
-#ifndef FM_AB_GRAM_NOSCATTER
-#define FM_AB_GRAM_NOSCATTER 0
-#endif
-#ifndef FM_AB_GRAM_DPPOLD
-#define FM_AB_GRAM_DPPOLD 0   // 1: the rotations through update_dpp(0, ...) (zero-initialised)
-#endif
-#ifndef FM_GRAM_PF2
-#define FM_GRAM_PF2 0   // 1: two tiles of row loads in flight per wave (two register buffers)
-#endif
-#ifndef FM_GRAM_TOUCH
-#define FM_GRAM_TOUCH 0   // 1: one 4-byte load per 128-byte line of the tile after next (L2 warm-up;
-                          // measured 123.4 vs 110.3 us without: not used)
-#endif
-
 namespace fm {
 namespace {
 
@@ -56,13 +35,8 @@ __device__ __forceinline__ uint32_t push_valid(uint32_t nn, double x) {
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double x) {
     const uint64_t u = (uint64_t)__double_as_longlong(x);
-#if FM_AB_GRAM_DPPOLD
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xF, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, false);
-#else
     const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-#endif
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
@@ -117,16 +91,16 @@ struct GramWave {
     const fm_gram_args& a;
     int64_t r0, r1;
     int w, lane, ntile;
-    // register buffers of row loads: the next tile's loads are issued as soon as this tile's
-    // values sit in LDS, and fly during its MFMAs (FM_GRAM_PF2: two tiles ahead)
+    // register buffer of row loads: the next tile's loads are issued as soon as this tile's
+    // values sit in LDS, and fly during its MFMAs.  (Two tiles in flight, and a 4-byte L2
+    // warm-up load per 128-byte line of the tile after next, measured slower: 123.4 vs 110.3 us.)
     double xv[ZW - 1];
     int lv = 0;
-    double xw[FM_GRAM_PF2 ? ZW - 1 : 1];
+    // unused (the second tile's buffer once): the members' layout decides the order in which
+    // the compiler zeroes acc, and dropping these two reorders those moves in every kernel
+    double xw[1];
     int lw = 0;
     double acc[NB][NI];
-    // touch loads: the previous touch's word (consumed a tile later, when it has landed) and
-    // their xor (kept live so the loads stay; never meaningful)
-    uint32_t tpend = 0, tacc = 0;
 
     __device__ __forceinline__ GramWave(const fm_gram_args& a_, int64_t r0_, int64_t r1_, int w_)
         : a(a_), r0(r0_), r1(r1_), w(w_), lane((int)threadIdx.x & (WAVE - 1)),
@@ -136,22 +110,13 @@ struct GramWave {
     // 32-bit row offset, so every load is a global_load with an SGPR base and no per-load
     // address VALU.  Lanes past the chunk end re-read its last row (masked later).  Without
     // universes the level load reads byte 0 of the panel and is masked to 0.
-    __device__ __forceinline__ void load_row(int t) { load_row_into(t, xv, lv); }
-
-    template <int N>
-    __device__ __forceinline__ void load_row_into(int t, double (&xv)[N], int& lv) {
+    __device__ __forceinline__ void load_row(int t) {
         typedef const __attribute__((address_space(1))) char* gptr;   // global_load, not flat_load
         const int64_t t0 = r0 + (int64_t)t * TR;
         const int64_t last = r1 - 1 - t0;
         const uint32_t lo = last < 0 ? 0u : (last < lane ? (uint32_t)last : (uint32_t)lane);
         const int64_t tb = last < 0 ? r1 - 1 : t0;   // wave-uniform tile base (clamped)
         const double* cb = a.cols + tb;               // column 0; s_add per column
-        if (FM_AB_GRAM_NOLOAD) {
-#pragma unroll
-            for (int c = 0; c < ZW - 1; ++c) xv[c] = (double)(lo + t) * 0.001 + c;
-            lv = (int)(lo & 3);
-            return;
-        }
         if constexpr (PL) {
             // the split panel: high and low words from their planes (4-byte loads, the same
             // SGPR-base + lane-offset addressing), joined in registers
@@ -184,37 +149,8 @@ struct GramWave {
         lv = *((gptr)(a.level ? lvbase + tb : lvbase) + (a.level ? lo : 0u));
     }
 
-    // Warm the L2 for tile t: lane l loads one 4-byte word of 128-byte line (l & 3) of column
-    // l >> 2 (FP64 columns: 16 rows a line; planes: 32 rows, lanes 0-1 the high plane, 2-3 the
-    // low one), so ONE load instruction covers the tile's 60 lines; its data is consumed a tile
-    // later.  The wave's own loads of tile t, issued a tile after, then hit the L2 instead of
-    // waiting a loaded-HBM round trip with one tile in flight.
-    __device__ __forceinline__ void touch(int t) {
-        if constexpr (FM_GRAM_TOUCH == 0) return;
-        tacc ^= tpend;
-        if (t >= ntile) return;   // wave-uniform
-        typedef const __attribute__((address_space(1))) uint32_t* gptr32;
-        const int64_t t0 = r0 + (int64_t)t * TR;
-        const int c = lane >> 2, q = lane & 3;
-        const int cc = c < a.ncols ? c : a.ncols - 1;
-        int64_t row = t0 + (PL ? (q & 1) * 32 : q * 16);
-        row = row < r1 - 1 ? row : r1 - 1;
-        const uint32_t* p;
-        if constexpr (PL) p = (q < 2 ? a.hi_plane : a.lo_plane) + (int64_t)cc * a.plane_stride + row;
-        else p = (const uint32_t*)(a.cols + (int64_t)cc * a.col_stride + row);
-        tpend = *(gptr32)p;
-    }
-    __device__ __forceinline__ void touch_sink() {
-        if constexpr (FM_GRAM_TOUCH == 0) return;
-        tacc ^= tpend;
-        if (tacc == 0x9E3779B9u && a.nseg == -7) a.flags[lane] = tacc;   // never true: keeps the loads
-    }
-
     __device__ __forceinline__ void prefetch() {
-        touch(w + NWV);
         if (w < ntile) load_row(w);
-        if constexpr (FM_GRAM_PF2 != 0)
-            if (w + NWV < ntile) load_row_into(w + NWV, xw, lw);
     }
 
     // prm: LDS [4][32] = lo, hi, shift, inv_scale per column; lut: LDS pattern table.
@@ -246,7 +182,7 @@ struct GramWave {
         for (int m = 0; m < FM_MAX_MODELS; ++m)
             mm[m] = (uint32_t)__builtin_amdgcn_readlane(mmv, m < nmodels ? m : 0);
 
-        auto tile_step = [&](auto& xv, int& lv, int t, int tnext) {
+        auto tile_step = [&](int t, int tnext) {
             const int64_t row = r0 + (int64_t)t * TR + lane;
             // validity bits of the raw values (NaN = missing; clipping never makes or
             // removes a NaN: pandas clip ignores NaN bounds)
@@ -289,7 +225,7 @@ struct GramWave {
             // Gram entries it pollutes are never read by fm_solve.  clip = hardware max/min:
             // a NaN bound is ignored, a NaN x gives a don't-care value.  Dropped rows are not
             // stored.
-            if (valid && !FM_AB_GRAM_NOSCATTER) {
+            if (valid) {
                 double* dst = wt + dest * RS;
                 dst[0] = 1.0;
                 if (scaled) {
@@ -302,10 +238,8 @@ struct GramWave {
                         dst[1 + c] = hw_min(hw_max(xv[c], prm[0][c]), prm[1][c]) - prm[2][c];
                 }
             }
-            // this tile's values are consumed: the next tile's loads fly during the MFMAs, and
-            // the one after next is touched into the L2
-            if (tnext < ntile) load_row_into(tnext, xv, lv);
-            touch(tnext + NWV);
+            // this tile's values are consumed: the next tile's loads fly during the MFMAs
+            if (tnext < ntile) load_row(tnext);
             // the operand reads below read other lanes' rows of this wave: LDS executes one
             // wave's DS instructions in order, so only compiler reordering must be prevented
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -314,10 +248,6 @@ struct GramWave {
             // ---- MFMA accumulation per bucket: NI independent 4x4x4 block products per
             // 4-row group; rows past the bucket's count contribute zeros.  Per-bucket counts
             // are popcounts of the ballot masks, formed on the fly (scalar).
-            if (FM_AB_GRAM_NOMFMA) {
-                if (__popcll(bv) == 65) acc[0][0] += wt[oa[0]];   // keeps bv/dest alive
-                return;
-            }
             if constexpr (NT == 1) {
                 // ONE LDS read per group: lane (kr, q) reads z[row kr][q] = the A operand; the
                 // B operands z[kr][(q + 4k) & 15] are the same register of lane (kr, q + 4k),
@@ -383,15 +313,7 @@ struct GramWave {
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         };
-        if constexpr (FM_GRAM_PF2 != 0) {
-            for (int t = w; t < ntile; t += 2 * NWV) {
-                tile_step(xv, lv, t, t + 2 * NWV);
-                if (t + NWV < ntile) tile_step(xw, lw, t + NWV, t + 3 * NWV);
-            }
-        } else {
-            for (int t = w; t < ntile; t += NWV) tile_step(xv, lv, t, t + NWV);
-        }
-        touch_sink();
+        for (int t = w; t < ntile; t += NWV) tile_step(t, t + NWV);
     }
 
     // Cross-wave reduction and store: outp[bucket][packed upper triangle] for the nbr

@@ -27,12 +27,6 @@ FM_PROBE_BUFFER(sel)
 #ifndef FM_SELECT_STREAM_VPT
 #define FM_SELECT_STREAM_VPT 24   // values per thread above which fm_select streams the units
 #endif
-#ifndef FM_AB_LONG
-#define FM_AB_LONG 0              // timing builds only: 1 loads + count, 2 no candidate select
-#endif
-#ifndef FM_AB_SELECT_STREAM
-#define FM_AB_SELECT_STREAM 0     // timing builds only: the streaming kernel for every long unit
-#endif
 #ifndef FM_SELECT_STREAM_SB
 #define FM_SELECT_STREAM_SB 8     // loads per thread in flight in each streaming pass
 #endif
@@ -318,9 +312,8 @@ void launch_fixup(const SelArgs& a, int max_seg_len, hipStream_t st) {
     else hipLaunchKernelGGL(select_fixup_kernel<0>, dim3(g), dim3(ST), 0, st, a, zs, zl);
 }
 
-// fix-up + universe in one launch (months of <= 20 x 256 rows): the fix-up workgroups are
-// the slots the universe's months leave in one resident round (3 per CU), at least 32
-int launch_fixup_universe(const SelArgs& a, int max_seg_len, hipStream_t st) {
+// compute units of the current device (256 if the query fails), asked once
+int cu_count() {
     static int ncu = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
@@ -328,6 +321,13 @@ int launch_fixup_universe(const SelArgs& a, int max_seg_len, hipStream_t st) {
             n = 256;
         return n;
     }();
+    return ncu;
+}
+
+// fix-up + universe in one launch (months of <= 20 x 256 rows): the fix-up workgroups are
+// the slots the universe's months leave in one resident round (3 per CU), at least 32
+int launch_fixup_universe(const SelArgs& a, int max_seg_len, hipStream_t st) {
+    const int ncu = cu_count();
     const int vpt = (max_seg_len + ST - 1) / ST;
     int nfix = 3 * ncu - a.nseg;
     nfix = nfix < 32 ? 32 : (nfix > fix_grid(max_seg_len) ? fix_grid(max_seg_len) : nfix);
@@ -344,30 +344,6 @@ __global__ __launch_bounds__(ST) void select_stream_kernel(SelArgs a) {
     stream_unit(a, blockIdx.x, blockIdx.y, sm);
 }
 
-// Long segments (6,145 .. 20,480 rows: C5's 20,000-firm months, a daily panel's short
-// windows): one 512-thread workgroup per (segment, column) holds the unit in registers
-// (VPT <= 40 values per thread, ONE coalesced HBM read of the unit).  Both winsorize tails:
-//   * thresholds on the 32-bit HIGH words of the order-preserving keys: per wave the 64
-//     thread minima's high words sorted, T_w = the wave's q-th smallest, q = ceil((k+1)/8)
-//     for the largest needed rank k; c(T) = the valid thread minima with high word <= T
-//     (ballots, summed over the waves by LDS atomics); tau = the smallest T_w with
-//     c(tau) >= k+1.  The candidates -- every value whose high word is <= tau -- are then a
-//     PREFIX of the sorted values holding at least k+1 of them, so the order statistics are
-//     ranks inside the candidates (the upper tail the same on complemented keys);
-//   * both tails' candidates (a little more than 2k values) are compacted to LDS (ballot
-//     counts per wave, one barrier for the wave offsets); each wave sorts one 64-key run of each tail and every candidate finds its
-//     merged rank by binary searches in the other runs, so the whole workgroup works on the
-//     order statistics (no single-wave sort of hundreds of keys).
-// Units it cannot finish (ranks >= 512, > 512 candidates per tail, too few valid thread
-// minima) are marked (nvalid = -1) and redone by the streaming kernel's fallback pass.  At
-// <= 128 VGPRs (4 waves per SIMD) two workgroups share a CU, so one unit's loads fly while
-// the other selects.
-#ifndef FM_AB_PAIR_MASKALL
-#define FM_AB_PAIR_MASKALL 0   // timing builds only: test every value slot against the end
-#endif
-#ifndef FM_AB_LONG_MASKALL
-#define FM_AB_LONG_MASKALL 0   // timing builds only: mask every value slot
-#endif
 // One month of get_subsets (reference src/calc_Lewellen_2014.py:69-105) by an NW-wave
 // workgroup of the long-month kernel (one more grid column of fm_select_universe): the
 // pandas-lerp q_a / q_b quantiles of the month's NYSE rows' `me` (NaN skipped) by the
@@ -459,27 +435,17 @@ constexpr int LNW = LT / WAVE;
 constexpr int LONG_VPT = 40;
 constexpr int LCAP = 8 * WAVE;   // candidates per tail
 
-struct LongSmem {
-    double cand[2 * LCAP];       // lower-tail candidates, then upper-tail ones at LCAP
-    SelSmemT<LNW> hs;            // hist_select scratch (and the block reductions)
-    uint32_t tw[2][LNW];         // per-wave thresholds T_w (high words)
-    int tot[2][LNW];             // c(T_w), summed over the waves
-    int wc[2][LNW];              // per-wave candidate counts
-    uint64_t res[4];             // keys of the four order statistics
-};
-
-// MID: any ranks (pandas' 20% / 50% NYSE breakpoints, row masks): the adaptive histogram
-// select runs over the register-held values directly (no tail thresholds).
-template <int VPT, bool MID>
-__global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a) {
-    __shared__ LongSmem sm;
-    const int tid = (int)threadIdx.x, lane = lane_id();
-    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+// Long segments (6,145 .. 20,480 rows: C5's 20,000-firm months, a daily panel's short
+// windows) with middle ranks or a row mask (pandas' 20% / 50% NYSE breakpoints): one
+// 512-thread workgroup per (segment, column) holds the unit in registers as FP64 (VPT <= 40
+// values per thread, ONE coalesced HBM read of the unit) and the adaptive histogram select
+// runs over the register-held values directly.  Tail ranks without a mask take
+// select_long_hk_kernel below.
+template <int VPT>
+__global__ __launch_bounds__(LT, 3) void select_long_mid_kernel(SelArgs a) {
+    __shared__ SelSmemT<LNW> sm;   // hist_select scratch (and the block reductions)
+    const int tid = (int)threadIdx.x;
     const int s = blockIdx.x, c = blockIdx.y;
-    if (!MID && c == a.ncols) {   // fm_select_universe: the month's NYSE breakpoints + levels
-        universe_month_wg<LNW, HB, HCAP>(a, s, sm.hs);
-        return;
-    }
     const int64_t o = (int64_t)c * a.nseg + s;
     const int64_t r0 = a.seg_off[s];
     const int L = (int)(a.seg_off[s + 1] - r0);
@@ -489,7 +455,7 @@ __global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a)
     uint32_t lb = (uint32_t)tid * 8u;
     asm volatile("" : "+v"(lb));
     double xv[VPT];
-    if (!MID || a.mask == nullptr) {   // block-uniform
+    if (a.mask == nullptr) {   // block-uniform
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads
             const uint32_t off = lb + (uint32_t)(v * LT * 8);
@@ -497,7 +463,7 @@ __global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a)
         }
         // masked after, and only the slots past the block's full rows of values (a scalar
         // branch per slot; the volatile asm keeps it a branch, not three selects per value)
-        const int vf = FM_AB_LONG_MASKALL ? 0 : L / LT;
+        const int vf = L / LT;
 #pragma unroll
         for (int v = 0; v < VPT; ++v)
             if (v >= vf) {
@@ -525,15 +491,9 @@ __global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a)
         mn = hw_min(mn, xv[v]);
         mx = hw_max(mx, xv[v]);
     }
-    if (tid < 2 * LNW) sm.tot[tid / LNW][tid % LNW] = 0;
-    const int n = block_sum<LNW>(cnt, sm.hs.ints);
+    const int n = block_sum<LNW>(cnt, sm.ints);
     double lo = NAN, hi = NAN;
-    if (FM_AB_LONG == 1) {   // timing builds only: the load + count floor
-        if (tid == 0) a.nvalid[o] = n, a.lo[o] = mn, a.hi[o] = mx;
-        return;
-    }
-    bool ok = true;
-    if (MID && n >= a.min_count && n > 0) {   // block-uniform
+    if (n >= a.min_count && n > 0) {   // block-uniform
         int rk[4];
         double g0, g1;
         qranks(n, a.q_lo, a.lerp_mode, rk[0], rk[1], g0);
@@ -546,158 +506,22 @@ __global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a)
                 kmn = k < kmn ? k : kmn;
                 kmx = k > kmx ? k : kmx;
             }
-        kmn = block_min_u64<LNW>(kmn, sm.hs.u64s);
-        kmx = block_max_u64<LNW>(kmx, sm.hs.u64s + LNW);
+        kmn = block_min_u64<LNW>(kmn, sm.u64s);
+        kmx = block_max_u64<LNW>(kmx, sm.u64s + LNW);
         uint64_t ko[4];
         hist_select_t<LNW, HB, HCAP>([&](auto&& f) {
 #pragma unroll
             for (int v = 0; v < VPT; ++v) f(xv[v]);
-        }, 4, rk, kmn, kmx, ko, sm.hs);
+        }, 4, rk, kmn, kmx, ko, sm);
         lo = qlerp(kval(ko[0]), kval(ko[1]), g0, a.lerp_mode);
         hi = qlerp(kval(ko[2]), kval(ko[3]), g1, a.lerp_mode);
-    } else if (!MID && n >= a.min_count && n > 0) {   // block-uniform
-        int i0, j0, i1, j1;
-        double g0, g1;
-        qranks(n, a.q_lo, a.lerp_mode, i0, j0, g0);
-        qranks(n, a.q_hi, a.lerp_mode, i1, j1, g1);
-        const int kl = j0, ku = n - 1 - i1;        // largest ranks needed from either end
-        const int ql = kl / LNW + 1, qu = ku / LNW + 1;
-        ok = ql <= WAVE && qu <= WAVE;
-        uint32_t tl = 0xFFFFFFFFu, tu = 0xFFFFFFFFu;
-        if (ok) {
-            // high words of the thread extrema's keys (NaN thread: 0xFFFFFFFF, above every
-            // valid key's high word)
-            uint32_t ha[1] = {isnan(mn) ? 0xFFFFFFFFu : (uint32_t)(dkey(mn) >> 32)};
-            uint32_t hb[1] = {isnan(mx) ? 0xFFFFFFFFu : (uint32_t)(~dkey(mx) >> 32)};
-            const uint32_t ua = ha[0], ub = hb[0];
-            wave_sort32<1>(ha);
-            wave_sort32<1>(hb);
-            if (lane == 0) {
-                sm.tw[0][w] = (uint32_t)__builtin_amdgcn_readlane((int)ha[0], ql - 1);
-                sm.tw[1][w] = (uint32_t)__builtin_amdgcn_readlane((int)hb[0], qu - 1);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < LNW; ++q) {
-                const uint32_t Ta = sm.tw[0][q], Tb = sm.tw[1][q];
-                const int ca = (int)__popcll(__ballot(ua != 0xFFFFFFFFu && ua <= Ta));
-                const int cb = (int)__popcll(__ballot(ub != 0xFFFFFFFFu && ub <= Tb));
-                if (lane == 0) {
-                    atomicAdd(&sm.tot[0][q], ca);
-                    atomicAdd(&sm.tot[1][q], cb);
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < LNW; ++q) {
-                const uint32_t Ta = sm.tw[0][q], Tb = sm.tw[1][q];
-                if (Ta != 0xFFFFFFFFu && sm.tot[0][q] >= kl + 1 && Ta < tl) tl = Ta;
-                if (Tb != 0xFFFFFFFFu && sm.tot[1][q] >= ku + 1 && Tb < tu) tu = Tb;
-            }
-            ok = tl != 0xFFFFFFFFu && tu != 0xFFFFFFFFu;
-        }
-        int clo = 0, chi = 0;
-        if (ok) {
-            // candidates by value compares against the largest / smallest double of the
-            // threshold high word (+-inf at the ends, where the next keys would be NaNs);
-            // value compares also take the other zero of a +-0 boundary, which keeps the
-            // candidates a prefix / suffix of the sorted values
-            const uint64_t kla = ((uint64_t)tl << 32) | 0xFFFFFFFFull;
-            const uint64_t kub = ~(((uint64_t)tu << 32) | 0xFFFFFFFFull);
-            const double tlo = kla >= dkey(INFINITY) ? INFINITY : kval(kla);
-            const double thi = kub <= dkey(-INFINITY) ? -INFINITY : kval(kub);
-            // wave totals from ballots (compares straight into lane masks, scalar counts),
-            // then each wave's offset from the other waves' totals (one barrier)
-            int wl = 0, wh = 0;
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) {
-                wl += (int)__popcll(__ballot(xv[v] <= tlo));
-                wh += (int)__popcll(__ballot(xv[v] >= thi));
-                // counts in order: otherwise the compiler forms all 2 x VPT ballot masks first
-                // and spills them to VGPR lanes (~300 writelane / readlane VALU per wave)
-                asm volatile("" : "+s"(wl), "+s"(wh));
-            }
-            if (lane == 0) {
-                sm.wc[0][w] = wl;
-                sm.wc[1][w] = wh;
-            }
-            __syncthreads();
-            int ol = 0, oh = LCAP;
-#pragma unroll
-            for (int q = 0; q < LNW; ++q) {
-                const int a0 = sm.wc[0][q], a1 = sm.wc[1][q];
-                ol += q < w ? a0 : 0;
-                oh += q < w ? a1 : 0;
-                clo += a0;
-                chi += a1;
-            }
-            // caps, and the rare overlap of the two sets (massive ties): redone by the fallback
-            ok = clo <= LCAP && chi <= LCAP && clo + chi <= n && clo > kl && chi > ku;
-            if (ok) {
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    double x = xv[v];
-                    asm volatile("" : "+v"(x));   // recompute (no SGPR masks kept from the count)
-                    const uint64_t ml = __ballot(x <= tlo), mh = __ballot(x >= thi);
-                    if (ml) {   // wave-uniform: most value slots hold no candidate
-                        if (x <= tlo) sm.cand[ol + mask_rank(ml)] = x;
-                        ol += (int)__popcll(ml);
-                    }
-                    if (mh) {
-                        if (x >= thi) sm.cand[oh + mask_rank(mh)] = x;
-                        oh += (int)__popcll(mh);
-                    }
-                }
-                __syncthreads();
-                // the four order statistics among the candidates: wave w sorts run w of each
-                // tail (64 keys; the upper tail on complemented keys, so both count from their
-                // end), then every candidate's merged rank = its run position + the entries
-                // of the other runs before it (binary searches, ties by run); the lanes at
-                // the target ranks store their keys
-                uint64_t* ck = reinterpret_cast<uint64_t*>(sm.cand);
-                const int e = w * WAVE + lane;
-                uint64_t ka[1] = {e < clo ? dkey(sm.cand[e]) : SENT};
-                uint64_t kb[1] = {e < chi ? ~dkey(sm.cand[LCAP + e]) : SENT};
-                const int nrl = __builtin_amdgcn_readfirstlane((clo + WAVE - 1) / WAVE);
-                const int nru = __builtin_amdgcn_readfirstlane((chi + WAVE - 1) / WAVE);
-                // only the waves holding candidates sort (an all-sentinel run is sorted);
-                // block-uniform counts, so the sorts run with the whole wave active
-                if (FM_AB_LONG != 2 && w < nrl) wave_sort<1>(ka);
-                if (FM_AB_LONG != 2 && w < nru) wave_sort<1>(kb);
-                ck[e] = ka[0];   // in place: wave w owns entries [64 w, 64 w + 64) of each list
-                ck[LCAP + e] = kb[0];
-                if (tid < 4) sm.res[tid] = SENT;
-                __syncthreads();
-                if (ka[0] != SENT) {
-                    int r = lane;
-                    for (int u = 0; u < nrl; ++u)
-                        if (u != w) r += merge_count(ck + u * WAVE, ka[0], u < w);
-                    if (r == i0) sm.res[0] = ka[0];
-                    if (r == j0) sm.res[1] = ka[0];
-                }
-                if (kb[0] != SENT) {
-                    int r = lane;
-                    for (int u = 0; u < nru; ++u)
-                        if (u != w) r += merge_count(ck + LCAP + u * WAVE, kb[0], u < w);
-                    if (r == n - 1 - i1) sm.res[2] = ~kb[0];
-                    if (r == n - 1 - j1) sm.res[3] = ~kb[0];
-                }
-                __syncthreads();
-                lo = qlerp(kval(sm.res[0]), kval(sm.res[1]), g0, a.lerp_mode);
-                hi = qlerp(kval(sm.res[2]), kval(sm.res[3]), g1, a.lerp_mode);
-            }
-        }
-    }
-    if (!ok) {   // redone by the fix-up kernel
-        if (tid == 0) sel_mark(a, o);
-        return;
     }
     if (a.center != nullptr) {
         // Gram pivot: the midpoint of the cuts, else of the finite range, else 0
         double cen = 0.5 * (lo + hi);
         if (!isfinite(cen)) {   // block-uniform
-            const uint64_t m1 = block_min_u64<LNW>(isfinite(mn) ? dkey(mn) : SENT, sm.hs.u64s);
-            const uint64_t m2 = block_min_u64<LNW>(isfinite(mx) ? ~dkey(mx) : SENT, sm.hs.u64s + LNW);
+            const uint64_t m1 = block_min_u64<LNW>(isfinite(mn) ? dkey(mn) : SENT, sm.u64s);
+            const uint64_t m2 = block_min_u64<LNW>(isfinite(mx) ? ~dkey(mx) : SENT, sm.u64s + LNW);
             cen = m1 == SENT || m2 == SENT ? 0.0 : 0.5 * (kval(m1) + kval(~m2));
             if (!isfinite(cen)) cen = 0.0;
         }
@@ -713,8 +537,9 @@ __global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a)
 
 // ---- High-key tail kernel (the default for tail ranks without a row mask).
 //
-// The FP64 kernel above holds a unit's values in 80 VGPRs per thread, so only two 512-thread
-// workgroups fit a CU and the chip idles its HBM while both compute.  The tails need far less:
+// Holding a unit's values as FP64 (select_long_mid_kernel above) takes 80 VGPRs per thread, so
+// only two 512-thread workgroups fit a CU and the chip idles its HBM while both compute (the
+// tails ran on such a kernel before).  The tails need far less:
 // every step before the final candidate sort works on the HIGH 32 bits of the values' order
 // keys (thread extrema, per-wave thresholds, ballot counts, compaction), and only the
 // candidates' full values are gathered back from memory (a few hundred per unit).  40 VGPRs
@@ -735,27 +560,6 @@ __global__ __launch_bounds__(LT, MID ? 3 : 4) void select_long_kernel(SelArgs a)
 // wrap past the top).  The one thing a high word cannot tell is +-inf from a NaN whose payload
 // is all in the low word (high word 0x7FF00000 / 0xFFF00000): units holding either key
 // (thread min 0 / thread max HK_MAX) are marked and redone by the exact streaming kernel.
-#ifndef FM_HK_ABL
-#define FM_HK_ABL 0   // timing ablations only (wrong cuts): 1 = stop after the thresholds, 2 = before the gather, 3 = after the counts
-#endif
-#ifndef FM_PAIR_KTH
-#define FM_PAIR_KTH 1   // pair select: the tail threshold by bisection over unsorted lane extremes
-#endif
-#ifndef FM_HK_KTH
-#define FM_HK_KTH 1   // per-wave thresholds by bit bisection (not a sort of the thread keys)
-#endif
-#ifndef FM_HK_WAVELIST
-#define FM_HK_WAVELIST 1   // long-month candidates written straight into per-wave runs (no count pass)
-#endif
-#ifndef FM_HK_RIDE
-#define FM_HK_RIDE 1   // a universe rides the high-key kernel's launch (one more grid column)
-#endif
-#ifndef FM_AB_NOFB
-#define FM_AB_NOFB 0   // timing / probe builds only: no fallback launch after the long kernel
-#endif
-#ifndef FM_AB_LONG_F64
-#define FM_AB_LONG_F64 0   // timing builds only: 1 = tails on the FP64-register kernel above
-#endif
 constexpr uint32_t HK_MAX = 0xFFE00001u;
 constexpr uint32_t HK_NONE = 0xFFFFFFFFu;   // thread / threshold sentinel (no valid value)
 __device__ __forceinline__ uint32_t hkey(uint32_t hi) {
@@ -774,63 +578,35 @@ struct LongHkSmem {
 };
 
 // The high words of a unit into hk (raw; hkey is applied by the unit's own pass).  Slot v of
-// thread t holds row hk_row(v, t): with FM_HK_X4, four consecutive rows per 16-byte load
-// (row 4 LT (v / 4) + 4 t + v % 4: one descriptor per unit, a quarter of the load issue);
-// otherwise row LT v + t, one 4-byte load per slot.  Rows past the month end read 0 through
-// the descriptor's range check (checked per dword; masked later).
-#ifndef FM_HK_X4
-#define FM_HK_X4 1
-#endif
-__device__ __forceinline__ int hk_row(int v, int t) {
-    return FM_HK_X4 ? (v >> 2) * (4 * LT) + 4 * t + (v & 3) : v * LT + t;
-}
+// thread t holds row hk_row(v, t): four consecutive rows per 16-byte load (row
+// 4 LT (v / 4) + 4 t + v % 4: one descriptor per unit, a quarter of the load issue of one
+// 4-byte load per slot).  Rows past the month end read 0 through the descriptor's range check
+// (checked per dword; masked later).
+__device__ __forceinline__ int hk_row(int v, int t) { return (v >> 2) * (4 * LT) + 4 * t + (v & 3); }
 
 template <int VPT>
 __device__ __forceinline__ void hk_load(const double* col, int L, uint32_t (&hk)[VPT]) {
-    if constexpr (FM_HK_X4) {
-        static_assert(VPT % 4 == 0, "hk_load: 16-byte slots");
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)col, 0, L * 8, 0x00020000);
-        const uint32_t lb = (uint32_t)threadIdx.x * 32u + 4u;   // little-endian: byte 4 = high word
+    static_assert(VPT % 4 == 0, "hk_load: 16-byte slots");
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)col, 0, L * 8, 0x00020000);
+    const uint32_t lb = (uint32_t)threadIdx.x * 32u + 4u;   // little-endian: byte 4 = high word
 #pragma unroll
-        for (int v = 0; v < VPT; ++v)
-            hk[v] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, lb + (uint32_t)(v & 3) * 8u,
-                                                                  (v >> 2) * (4 * LT * 8), 0);
-    } else {
-        const uint32_t lb = (uint32_t)threadIdx.x * 8u + 4u;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            const int rem = L - v * LT;   // rows from this slot's first row to the month end
-            const int nrec = rem > 0 ? (rem < LT ? rem : LT) * 8 : 0;
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(col + (rem > 0 ? v * LT : 0)), 0, nrec,
-                                                              0x00020000);
-            hk[v] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, lb, 0, 0);
-        }
-    }
+    for (int v = 0; v < VPT; ++v)
+        hk[v] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, lb + (uint32_t)(v & 3) * 8u,
+                                                              (v >> 2) * (4 * LT * 8), 0);
 }
 
 // ... or from the high-word plane (4 bytes per value read instead of 8)
 template <int VPT>
 __device__ __forceinline__ void hk_load_plane(const uint32_t* hp, int L, uint32_t (&hk)[VPT]) {
-    if constexpr (FM_HK_X4) {
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)hp, 0, L * 4, 0x00020000);
-        const uint32_t lb = (uint32_t)threadIdx.x * 16u;
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)hp, 0, L * 4, 0x00020000);
+    const uint32_t lb = (uint32_t)threadIdx.x * 16u;
 #pragma unroll
-        for (int v = 0; v < VPT / 4; ++v) {
-            const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs, lb, v * (4 * LT * 4), 0);
-            hk[4 * v] = q[0];
-            hk[4 * v + 1] = q[1];
-            hk[4 * v + 2] = q[2];
-            hk[4 * v + 3] = q[3];
-        }
-    } else {
-        const uint32_t lb = (uint32_t)threadIdx.x * 4u;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            const int rem = L - v * LT;
-            const int nrec = rem > 0 ? (rem < LT ? rem : LT) * 4 : 0;
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(hp + (rem > 0 ? v * LT : 0)), 0, nrec, 0x00020000);
-            hk[v] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, lb, 0, 0);
-        }
+    for (int v = 0; v < VPT / 4; ++v) {
+        const auto q = __builtin_amdgcn_raw_buffer_load_b128(rs, lb, v * (4 * LT * 4), 0);
+        hk[4 * v] = q[0];
+        hk[4 * v + 1] = q[1];
+        hk[4 * v + 2] = q[2];
+        hk[4 * v + 3] = q[3];
     }
 }
 
@@ -886,12 +662,7 @@ __device__ __forceinline__ void hk_unit(const SelArgs& a, int s, int c, uint32_t
     bool cand = false, fast_done = false;   // fast_done: the candidates are in per-wave runs
     int i0 = 0, j0 = 0, i1 = 0, j1 = 0, clo = 0, chi = 0;
     double g0 = 0.0, g1 = 0.0;
-#if FM_HK_ABL == 3
-    lo = -1.0; hi = 1.0;
-    if (false) {
-#else
     if (ok && n >= a.min_count && n > 0) {   // block-uniform
-#endif
         qranks(n, a.q_lo, a.lerp_mode, i0, j0, g0);
         qranks(n, a.q_hi, a.lerp_mode, i1, j1, g1);
         const int kl = j0, ku = n - 1 - i1;        // largest ranks needed from either end
@@ -899,22 +670,12 @@ __device__ __forceinline__ void hk_unit(const SelArgs& a, int s, int c, uint32_t
         ok = ql <= WAVE && qu <= WAVE;
         uint32_t tl = HK_NONE, tu = HK_NONE;
         if (ok) {
-#if FM_HK_KTH
             uint32_t ta, tb;   // the ql-th / qu-th smallest lane key, by bisection
             wave_kth_u32x2(ua, ql, ub, qu, ta, tb);
             if (lane == 0) {
                 sm.tw[0][w] = ta;
                 sm.tw[1][w] = tb;
             }
-#else
-            uint32_t ha[1] = {ua}, hb[1] = {ub};
-            wave_sort32<1>(ha);
-            wave_sort32<1>(hb);
-            if (lane == 0) {
-                sm.tw[0][w] = (uint32_t)__builtin_amdgcn_readlane((int)ha[0], ql - 1);
-                sm.tw[1][w] = (uint32_t)__builtin_amdgcn_readlane((int)hb[0], qu - 1);
-            }
-#endif
             __syncthreads();
             // this wave's count under each wave's threshold, lane q holding threshold q's, one
             // LDS add per lane (a threshold of HK_NONE is never taken: its count is moot)
@@ -939,12 +700,7 @@ __device__ __forceinline__ void hk_unit(const SelArgs& a, int s, int c, uint32_t
             }
             ok = tl != HK_NONE && tu != HK_NONE;
         }
-#if FM_HK_ABL == 1
-        if (ok) { lo = -1.0; hi = 1.0; fast_done = true; }
-        if (false) {
-#else
-        if (ok && FM_HK_WAVELIST) {
-#endif
+        if (ok) {
             // candidates straight into per-wave lists: wave w writes its lower-tail rows to
             // cidx[64 w ..] and its upper-tail rows to cidx[LCAP + 64 w ..] (re-indexed into
             // 64-candidate runs at the gather below), no count pass for list offsets first.  A
@@ -1075,9 +831,6 @@ __device__ __forceinline__ void hk_unit(const SelArgs& a, int s, int c, uint32_t
             }
         }
     }
-#if FM_HK_ABL == 2
-    if (cand) { lo = -1.0; hi = 1.0; cand = false; }
-#endif
     if (cand) {   // block-uniform
         // gather the candidates' full values (a few hundred rows of the unit just read); wave
         // w sorts run w of each tail (64 keys; the upper tail on complemented keys), then every
@@ -1176,7 +929,7 @@ template <int VPT>
 __global__ __launch_bounds__(LT, 6) void select_long_hk_kernel(SelArgs a) {
     __shared__ LongHkSmem sm;
     const int s = blockIdx.x, c = blockIdx.y;
-    if (FM_HK_RIDE && c == a.ncols) {   // fm_select_universe: the month's NYSE breakpoints + levels
+    if (c == a.ncols) {   // fm_select_universe: the month's NYSE breakpoints + levels
         universe_month_wg<LNW, HB, HCAP>(a, s, sm.hs);
         return;
     }
@@ -1192,10 +945,7 @@ __global__ __launch_bounds__(LT, 6) void select_long_hk_kernel(SelArgs a) {
 template <int VPT>
 void launch_long(const SelArgs& a, hipStream_t st, bool mid) {
     if (mid)
-        hipLaunchKernelGGL((select_long_kernel<VPT, true>), dim3(a.nseg, a.ncols), dim3(LT), 0, st, a);
-    else if (FM_AB_LONG_F64 || FM_AB_LONG != 0)   // with a universe (a.ume), one more grid column
-        hipLaunchKernelGGL((select_long_kernel<VPT, false>), dim3(a.nseg, a.ncols + (a.ume ? 1 : 0)), dim3(LT), 0,
-                           st, a);
+        hipLaunchKernelGGL((select_long_mid_kernel<VPT>), dim3(a.nseg, a.ncols), dim3(LT), 0, st, a);
     else   // with a universe (a.ume), one more grid column: its months' NYSE breakpoints
         hipLaunchKernelGGL((select_long_hk_kernel<VPT>), dim3(a.nseg, a.ncols + (a.ume ? 1 : 0)), dim3(LT), 0, st, a);
 }
@@ -1240,11 +990,10 @@ __device__ __forceinline__ int load_unit(const SelArgs& a, int64_t u, double (&x
     return L;
 }
 
-// Persistent waves, software-pipelined over units u = gw, gw + nwaves, ...: the loads of the
-// next unit are issued as soon as this unit's candidates are compacted into LDS, so they
-// overlap the candidate sorts, the lerp and the stores (without the moments pass, which
-// needs the values; then they are issued after it).
-template <int VPL, bool EARLY>
+// Persistent waves over units u = gw, gw + nwaves, ... with the moments pass (the cuts alone
+// take the two-wave kernels below): the moments need the unit's values, so the next unit's
+// loads are issued after them.
+template <int VPL>
 __global__ __launch_bounds__(ST, 2) void select_wave_kernel(SelArgs a) {
     __shared__ double cbuf[SNW][2][WCAP];   // per wave: lower / upper tail candidates
     const int lane = lane_id();
@@ -1258,7 +1007,6 @@ __global__ __launch_bounds__(ST, 2) void select_wave_kernel(SelArgs a) {
     int64_t k = (int64_t)blockIdx.x * SNW + w;
     if (k >= nunits) return;   // wave-uniform; no block barriers below
     int64_t u = unit_of(a, k);
-    constexpr bool early = EARLY;   // no moments pass: prefetch right after compaction
     double xv[VPL];
     int L = load_unit<VPL>(a, u, xv);
     __builtin_amdgcn_sched_barrier(0);
@@ -1268,10 +1016,7 @@ __global__ __launch_bounds__(ST, 2) void select_wave_kernel(SelArgs a) {
         const int64_t kn = k + nwt;
         const bool more = kn < nunits;
         const int64_t un = more ? unit_of(a, kn) : 0;
-        int Ln = 0;
-        const WaveCut r = wave_cut<VPL>(xv, L, a.q_lo, a.q_hi, a.min_count, a.lerp_mode, Ll, Lh, [&] {
-            if (early && more) Ln = load_unit<VPL>(a, un, xv);
-        });
+        const WaveCut r = wave_cut<VPL>(xv, L, a.q_lo, a.q_hi, a.min_count, a.lerp_mode, Ll, Lh);
         const double lo = r.lo, hi = r.hi, mn = r.mn;
         const int n = r.n;
         const bool ok = r.ok;
@@ -1279,46 +1024,44 @@ __global__ __launch_bounds__(ST, 2) void select_wave_kernel(SelArgs a) {
             if (lane == 0) sel_mark(a, u);   // redone by the fix-up kernel
         } else {
             if (a.center != nullptr && lane == 0) a.center[u] = r.cen;
-            if (!early) {
-                // moments of the clipped values about a pivot inside the data (see
-                // select_unit_wg)
-                double p = isfinite(lo) ? lo : (isfinite(hi) ? hi : 0.0);
-                if (!isfinite(lo) && !isfinite(hi)) {
-                    double m2 = isfinite(mn) ? mn : NAN;
+            // moments of the clipped values about a pivot inside the data (see
+            // select_unit_wg)
+            double p = isfinite(lo) ? lo : (isfinite(hi) ? hi : 0.0);
+            if (!isfinite(lo) && !isfinite(hi)) {
+                double m2 = isfinite(mn) ? mn : NAN;
 #pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) m2 = fmin(m2, __shfl_xor(m2, o, WAVE));
-                    p = isfinite(m2) ? m2 : 0.0;
+                for (int o = 32; o > 0; o >>= 1) m2 = fmin(m2, __shfl_xor(m2, o, WAVE));
+                p = isfinite(m2) ? m2 : 0.0;
+            }
+            double s1 = 0.0, s2 = 0.0;
+            if (isfinite(lo) && !isnan(hi)) {
+                // p == lo: hardware max/min send a NaN (absent) value to lo, so it adds
+                // d == 0 exactly; the same d as the general loop for every present value
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) {
+                    const double d = hw_min(hw_max(xv[v], lo), hi) - lo;
+                    s1 += d;
+                    s2 = fma(d, d, s2);
                 }
-                double s1 = 0.0, s2 = 0.0;
-                if (isfinite(lo) && !isnan(hi)) {
-                    // p == lo: hardware max/min send a NaN (absent) value to lo, so it adds
-                    // d == 0 exactly; the same d as the general loop for every present value
+            } else {
 #pragma unroll
-                    for (int v = 0; v < VPL; ++v) {
-                        const double d = hw_min(hw_max(xv[v], lo), hi) - lo;
-                        s1 += d;
-                        s2 = fma(d, d, s2);
-                    }
-                } else {
-#pragma unroll
-                    for (int v = 0; v < VPL; ++v) {
-                        double x = xv[v];
-                        if (x < lo) x = lo;
-                        if (x > hi) x = hi;
-                        const double d = isnan(x) ? 0.0 : x - p;
-                        s1 += d;
-                        s2 = fma(d, d, s2);
-                    }
+                for (int v = 0; v < VPL; ++v) {
+                    double x = xv[v];
+                    if (x < lo) x = lo;
+                    if (x > hi) x = hi;
+                    const double d = isnan(x) ? 0.0 : x - p;
+                    s1 += d;
+                    s2 = fma(d, d, s2);
                 }
-                s1 = wave_sum(s1);
-                s2 = wave_sum(s2);
-                if (lane == 0) {
-                    a.mean[u] = n > 0 ? p + s1 / (double)n : NAN;
-                    if (a.sd) {
-                        double var = n > 1 ? (s2 - s1 * (s1 / (double)n)) / (double)(n - 1) : NAN;
-                        if (var < 0.0) var = 0.0;
-                        a.sd[u] = n > 1 ? sqrt(var) : NAN;
-                    }
+            }
+            s1 = wave_sum(s1);
+            s2 = wave_sum(s2);
+            if (lane == 0) {
+                a.mean[u] = n > 0 ? p + s1 / (double)n : NAN;
+                if (a.sd) {
+                    double var = n > 1 ? (s2 - s1 * (s1 / (double)n)) / (double)(n - 1) : NAN;
+                    if (var < 0.0) var = 0.0;
+                    a.sd[u] = n > 1 ? sqrt(var) : NAN;
                 }
             }
             if (lane == 0) {
@@ -1329,10 +1072,9 @@ __global__ __launch_bounds__(ST, 2) void select_wave_kernel(SelArgs a) {
             }
         }
         if (!more) break;
-        if (!early) Ln = load_unit<VPL>(a, un, xv);
+        L = load_unit<VPL>(a, un, xv);
         k = kn;
         u = un;
-        L = Ln;
     }
 }
 
@@ -1432,7 +1174,7 @@ __global__ __launch_bounds__(2 * WAVE) void select_pair_kernel(SelArgs a) {
         double mn4[4] = {NAN, NAN, NAN, NAN}, mx4[4] = {NAN, NAN, NAN, NAN};
         // slots past the segment end -> NaN; only the slots past the unit's full 128-row
         // groups can hold such rows (a scalar branch per slot, kept a branch by the asm)
-        const int vf = FM_AB_PAIR_MASKALL ? 0 : L / (2 * WAVE);
+        const int vf = L / (2 * WAVE);
 #pragma unroll
         for (int v = 0; v < VPH; ++v) {
             if (v >= vf) {
@@ -1615,14 +1357,6 @@ __global__ __launch_bounds__(2 * WAVE) void select_pair_kernel(SelArgs a) {
 #ifndef FM_PAIR_HK_WGS
 #define FM_PAIR_HK_WGS 0   // 0: by VPH
 #endif
-// 1: the next unit's loads are issued before the pick (its keys then stay live through it)
-#ifndef FM_PAIR_HK_PF
-#define FM_PAIR_HK_PF 1
-#endif
-// 1: the valid-key count as a per-lane carry count and one wave sum (0: a ballot per value)
-#ifndef FM_PAIR_HK_LANECNT
-#define FM_PAIR_HK_LANECNT 1
-#endif
 constexpr int pair_hk_wgs(int vph) {
     return FM_PAIR_HK_WGS > 0 ? FM_PAIR_HK_WGS : (vph <= 16 ? 12 : (vph <= 24 ? 10 : 8));
 }
@@ -1786,9 +1520,7 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
         const int row0 = h * WAVE + lane;
         // ---- 1. keys (rows past the month end -> HK_NONE), count, lane min / max keys
         const int lim = L - row0;
-        int nh = 0;
         uint32_t kmn = HK_NONE, kmx2 = 0;
-#if FM_PAIR_HK_LANECNT
         // invalid keys counted per lane from the wrap of the max's offset add (one add with
         // carry per value), one wave sum after the loop instead of a ballot per value
         int nbad = 0;
@@ -1814,30 +1546,13 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             kmx2 = max(kmx2, max(kx[0], kx[1]));
             asm volatile("" : "+v"(kmn), "+v"(kmx2));
         }
-        nh = VPH * WAVE - wave_sum(nbad);
-#else
-#pragma unroll
-        for (int v = 0; v < VPH; ++v) {
-            const uint32_t kk = v * 2 * WAVE < lim ? hkey(xk[v]) : HK_NONE;
-            xk[v] = kk;
-            nh += (int)__popcll(__ballot(kk <= HK_MAX));
-            kmn = min(kmn, kk);
-            kmx2 = max(kmx2, kk + 0x1FFFFEu);   // NaN / absent keys wrap below every valid one
-            asm volatile("" : "+s"(nh), "+v"(kmn), "+v"(kmx2));
-        }
-#endif
+        const int nh = VPH * WAVE - wave_sum(nbad);
         const bool tvalid = kmn <= HK_MAX;
         const uint32_t kmx = kmx2 - 0x1FFFFEu;
         const bool amb = tvalid && (kmn == 0u || kmx == HK_MAX);
-        {
-            uint32_t ta[1] = {tvalid ? kmn : HK_NONE}, tb[1] = {tvalid ? HK_MAX - kmx : HK_NONE};
-#if !FM_PAIR_KTH
-            wave_sort32<1>(ta);
-            wave_sort32<1>(tb);
-#endif
-            sm.sk[h][0][lane] = ta[0];
-            sm.sk[h][1][lane] = tb[0];
-        }
+        // unsorted lane extremes (the threshold below bisects over them)
+        sm.sk[h][0][lane] = tvalid ? kmn : HK_NONE;
+        sm.sk[h][1][lane] = tvalid ? HK_MAX - kmx : HK_NONE;
         const int ambw = (int)__popcll(__ballot(amb));
         if (lane == 0) {
             sm.ni[h][0] = nh;
@@ -1859,19 +1574,8 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             const int t = h;
             const int kr = t == 0 ? j0 : n - 1 - i1;
             uint32_t T = HK_NONE;
-#if FM_PAIR_KTH
             // (unsorted lane extremes of both halves; the (kr+1)-th smallest by bisection)
             if (kr < 2 * WAVE) T = wave_kth_u32_of2(sm.sk[0][t][lane], sm.sk[1][t][lane], kr + 1);
-#else
-            if (kr < 2 * WAVE) {
-                const uint32_t mine = sm.sk[0][t][lane], other = sm.sk[1][t][lane];
-                const int q0 = lane + count_below_u32(sm.sk[1][t], mine, false);
-                const int q1 = lane + count_below_u32(sm.sk[0][t], other, true);
-                const uint64_t m0 = __ballot(q0 == kr), m1 = __ballot(q1 == kr);
-                if (m0) T = (uint32_t)__builtin_amdgcn_readlane((int)mine, __builtin_ctzll(m0));
-                else if (m1) T = (uint32_t)__builtin_amdgcn_readlane((int)other, __builtin_ctzll(m1));
-            }
-#endif
             if (lane == 0) {
                 sm.tv[h] = T;
                 sm.okv[h] = T <= HK_MAX ? 1 : 0;
@@ -1907,8 +1611,8 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
                 sm.ni[h][2] = chi;
             }
             // xk is dead from here on: the next unit's loads fly during the sorts and gathers
-            if (FM_PAIR_HK_PF && more) Ln = load(s_nx, c_nx);
-            prefetched = FM_PAIR_HK_PF != 0;
+            if (more) Ln = load(s_nx, c_nx);
+            prefetched = true;
             __syncthreads();
             // ---- 4. one tail per wave over both halves' candidates
             const int t = h;
@@ -1969,13 +1673,7 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
 }
 
 int select_wave_grid(int64_t nunits) {
-    static int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
+    const int ncu = cu_count();
     const int64_t need = (nunits + SNW - 1) / SNW;
     const int64_t cap = (int64_t)ncu * 2;   // two resident workgroups per CU
     return (int)(need < cap ? need : cap);
@@ -1990,13 +1688,7 @@ void launch_select_pair(const SelArgs& a, hipStream_t st) {
         launch_select_pair_hk<VPH>(a, st);
         return;
     }
-    static int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
+    const int ncu = cu_count();
     const int64_t nunits = (int64_t)a.nseg * a.ncols;
     const int64_t cap = (int64_t)ncu * 8;   // eight 2-wave workgroups per CU (4 waves / SIMD)
     hipLaunchKernelGGL((select_pair_kernel<VPH>), dim3((unsigned)(nunits < cap ? nunits : cap)), dim3(2 * WAVE),
@@ -2005,13 +1697,7 @@ void launch_select_pair(const SelArgs& a, hipStream_t st) {
 
 template <int VPH>
 void launch_select_pair_hk(const SelArgs& a, hipStream_t st) {
-    static int ncu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
+    const int ncu = cu_count();
     const int64_t nunits = (int64_t)a.nseg * a.ncols;
     const int64_t cap = (int64_t)ncu * pair_hk_wgs(VPH);
     hipLaunchKernelGGL((select_pair_hk_kernel<VPH>), dim3((unsigned)(nunits < cap ? nunits : cap)), dim3(2 * WAVE),
@@ -2033,22 +1719,10 @@ int launch_select_pair_vph(const SelArgs& a, int max_seg_len, hipStream_t st) {
     return FM_OK;
 }
 
-// A/B switch for timing builds only (-DFM_AB_SELECT_ONE_WAVE=1): the one-wave kernel
-bool getenv_flag_one_wave() {
-#ifdef FM_AB_SELECT_ONE_WAVE
-    return FM_AB_SELECT_ONE_WAVE != 0;
-#else
-    return false;
-#endif
-}
-
 template <int VPL>
 void launch_select_wave(const SelArgs& a, hipStream_t st) {
     const int64_t nunits = (int64_t)a.nseg * a.ncols;
-    if (a.mean == nullptr)
-        hipLaunchKernelGGL((select_wave_kernel<VPL, true>), dim3((unsigned)select_wave_grid(nunits)), dim3(ST), 0, st, a);
-    else
-        hipLaunchKernelGGL((select_wave_kernel<VPL, false>), dim3((unsigned)select_wave_grid(nunits)), dim3(ST), 0, st, a);
+    hipLaunchKernelGGL((select_wave_kernel<VPL>), dim3((unsigned)select_wave_grid(nunits)), dim3(ST), 0, st, a);
 }
 
 // get_subsets' NYSE breakpoints AND the nested universe levels in one launch (reference
@@ -2057,12 +1731,6 @@ void launch_select_wave(const SelArgs& a, hipStream_t st) {
 // finds the pandas groupby.quantile(q_a, q_b) order statistics of the NYSE rows (NaN me
 // skipped) by the adaptive histogram select, lerps them the pandas way, and writes every
 // row's level (me >= me_20) + (me >= me_50) from the same registers (NaN compares False).
-#ifndef FM_AB_UNI_APART
-#define FM_AB_UNI_APART 0   // timing builds only: the universe in its own launch before the select
-#endif
-#ifndef FM_AB_UNI_NOSELECT
-#define FM_AB_UNI_NOSELECT 0   // timing builds only (tools/build_variant.sh): skip the order statistics
-#endif
 template <int VPT>
 __device__ __forceinline__ void universe_month(const double* __restrict__ me, const uint8_t* __restrict__ nyse,
                                                const int64_t* __restrict__ seg_off, double qa, double qb,
@@ -2134,7 +1802,7 @@ __device__ __forceinline__ void universe_month(const double* __restrict__ me, co
         qranks(n, qa, 1, rk[0], rk[1], g0);
         qranks(n, qb, 1, rk[2], rk[3], g1);
         uint64_t ko[4] = {kmn, kmn, kmx, kmx};
-        if (!FM_AB_UNI_NOSELECT) hist_select(for_each, 4, rk, kmn, kmx, ko, sm);
+        hist_select(for_each, 4, rk, kmn, kmx, ko, sm);
         a = qlerp(kval(ko[0]), kval(ko[1]), g0, 1);
         b = qlerp(kval(ko[2]), kval(ko[3]), g1, 1);
     }
@@ -2289,31 +1957,30 @@ int select_impl(const fm_select_args* args, const fm_universe_args* u, void* str
     hipStream_t st = (hipStream_t)stream;
     const int vpt = (max_seg_len + ST - 1) / ST;
     const bool long_path = vpt > FM_SELECT_STREAM_VPT && max_seg_len <= LONG_VPT * LT && x.mean == nullptr &&
-                           nvalid != nullptr && !FM_AB_SELECT_STREAM;
+                           nvalid != nullptr;
     // a universe rides the long-month kernel's launch (one more grid column) unless its tails
     // need the histogram (MID) kernel (riding the two-wave kernel's persistent workgroups
     // measured slower for short months: 118 vs 83 + 23 us on the bench panel,
     // profiles/r04/v2_kbench_fused_universe.log)
-    const bool ride = u != nullptr && long_path && !long_is_mid(a, max_seg_len) &&
-                      (FM_HK_RIDE || FM_AB_LONG_F64 || FM_AB_LONG != 0);
+    const bool ride = u != nullptr && long_path && !long_is_mid(a, max_seg_len);
     // months of <= 20 x 256 rows on the register paths: the universe shares the fix-up's launch
     // after the select (one launch less; the two are independent)
-    const bool with_fixup = u != nullptr && !ride && !long_path && vpt <= 20 && !FM_AB_UNI_APART;
+    const bool with_fixup = u != nullptr && !ride && !long_path && vpt <= 20;
     if (u != nullptr && !ride && !with_fixup) {
         const int rcu = universe_separately(x, u, stream);
         if (rcu != FM_OK) return rcu;
     }
     if (long_path) {
         // past the 256-thread paths' register budget: the 512-thread register-resident
-        // kernel (one read per unit); the streaming kernel redoes the units it marked
-        FM_REQUIRE(!no_f64 || (a.hp != nullptr && !long_is_mid(a, max_seg_len) && !FM_AB_LONG_F64 && FM_AB_LONG == 0),
+        // kernels (one read per unit); the streaming kernel redoes the units they marked
+        FM_REQUIRE(!no_f64 || (a.hp != nullptr && !long_is_mid(a, max_seg_len)),
                    "fm_select: this long-month path (row mask / middle ranks) needs FP64 columns");
         SelArgs al = a;
         if (ride) set_universe(al, u);
         const int rc = launch_select_long(al, max_seg_len, st);
         if (rc != FM_OK) return rc;
         FM_CHECK_LAUNCH("fm_select_cuts(long)");
-        if (!FM_AB_NOFB) launch_fixup(a, max_seg_len, st);
+        launch_fixup(a, max_seg_len, st);
         FM_CHECK_LAUNCH("fm_select_cuts(long fix-up)");
         // the level bytes by a streaming launch: writing them from the select kernel (a
         // re-read of the unmasked column, or unmasked registers + mask bits) measured no
@@ -2333,20 +2000,20 @@ int select_impl(const fm_select_args* args, const fm_universe_args* u, void* str
     // wave fast path: no row mask, segments of <= 96 * 64 rows, nvalid present (it carries
     // the fallback marks); the workgroup kernel then redoes the marked units only
     const int vpl = (max_seg_len + WAVE - 1) / WAVE;
-#ifdef FM_AB_SELECT_WG
-    const bool wave = false;   // A/B timing builds only: the workgroup-per-unit kernel for all
-#else
     const bool wave = row_mask == nullptr && nvalid != nullptr && vpl <= 96;
-#endif
-    (void)vpl;
-    FM_REQUIRE(!no_f64 || (wave && x.mean == nullptr && a.hp != nullptr) || !wave,
-               "fm_select: moments on a split panel need FP64 columns");
-    if (wave && x.mean == nullptr && vpl <= 96 && !getenv_flag_one_wave()) {
+    // with FP64 columns every combination is served.  A planes-only panel (no_f64, which the
+    // null-pointer check above admits only with both planes, so a.hp != nullptr in every case)
+    // is refused on one path alone, the one-wave moments kernel:
+    //   wave && mean  -> select_wave_kernel reads FP64 columns: refused
+    //   wave && !mean -> the two-wave high-key kernel (a.hp != nullptr): served
+    //   !wave         -> the workgroup kernel reads the planes (mean or not): served
+    FM_REQUIRE(!(no_f64 && wave && x.mean != nullptr), "fm_select: moments on a split panel need FP64 columns");
+    if (wave && x.mean == nullptr) {
         // two waves per unit (the common Table-2 case: no moments)
         const int rc = launch_select_pair_vph(a, max_seg_len, st);
         if (rc != FM_OK) return rc;
         FM_CHECK_LAUNCH("fm_select_cuts(pair)");
-    } else if (wave) {
+    } else if (wave) {   // with moments: one wave per unit
         if (vpl <= 16) launch_select_wave<16>(a, st);
         else if (vpl <= 32) launch_select_wave<32>(a, st);
         else if (vpl <= 48) launch_select_wave<48>(a, st);

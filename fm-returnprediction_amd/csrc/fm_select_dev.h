@@ -7,17 +7,6 @@
 
 #include "fm_common.h"
 
-// ablation knobs: timing builds only (tools/kbench.py), never the shipped library
-#ifndef FM_AB_SEL_NOSORT
-#define FM_AB_SEL_NOSORT 0
-#endif
-#ifndef FM_AB_SEL_NOCOMPACT
-#define FM_AB_SEL_NOCOMPACT 0
-#endif
-#ifndef FM_AB_SEL_NOLOAD
-#define FM_AB_SEL_NOLOAD 0
-#endif
-
 namespace fm {
 namespace {
 
@@ -1046,8 +1035,7 @@ __device__ __forceinline__ int count_below_u32(const uint32_t* L, uint32_t v, bo
 //   * those candidates (about 1.8% of n at n = 5000) are compacted by ballot + mbcnt into
 //     the wave's LDS lists Ll / Lh (WCAP each) and sorted by a 128-key wave bitonic sort;
 //     the order statistics are read at wave-uniform positions.
-// `freed()` runs as soon as xv is no longer needed (the caller's prefetch of its next
-// unit).  ok == false (ranks >= 64, more than WCAP candidates, fewer lanes with a valid
+// ok == false (ranks >= 64, more than WCAP candidates, fewer lanes with a valid
 // value than the rank): nothing is decided, the caller takes an exact fallback.  The
 // pivot `cen` is the midpoint of the cuts, else of the finite range, else 0.
 struct WaveCut {
@@ -1056,10 +1044,9 @@ struct WaveCut {
     bool ok;
 };
 
-template <int VPL, typename F>
+template <int VPL>
 __device__ __forceinline__ WaveCut wave_cut(double (&xv)[VPL], int L, double q_lo, double q_hi,
-                                            int min_count, int lerp_mode, double* Ll, double* Lh,
-                                            F&& freed) {
+                                            int min_count, int lerp_mode, double* Ll, double* Lh) {
     const int lane = lane_id();
     // min / max with 4 independent accumulators each (the chains would otherwise serialize
     // on the f64 latency); the count is scalar: ballot + popcount per row, no VALU
@@ -1115,7 +1102,6 @@ __device__ __forceinline__ WaveCut wave_cut(double (&xv)[VPL], int L, double q_l
                 // wave-uniform running counts; overflow is checked once
 #pragma unroll
                 for (int v = 0; v < VPL; ++v) {
-                    if (FM_AB_SEL_NOCOMPACT) break;
                     const bool bl = xv[v] < tlo, bh = xv[v] > thi;
                     const uint64_t ml = __ballot(bl), mh = __ballot(bh);
                     if (ml) {
@@ -1131,7 +1117,6 @@ __device__ __forceinline__ WaveCut wave_cut(double (&xv)[VPL], int L, double q_l
             }
         }
     }
-    freed();   // xv is free from here on
     if (apply && r.ok) {
         double v0, v1, v2, v3;
         const int ci = n - 1 - j1, cj = n - 1 - i1;
@@ -1142,10 +1127,7 @@ __device__ __forceinline__ WaveCut wave_cut(double (&xv)[VPL], int L, double q_l
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // the candidates are never NaN: sort them as doubles (hardware min/max; equal values,
         // +0 / -0 included, are interchangeable for the result)
-        if (FM_AB_SEL_NOSORT) {
-            v0 = v1 = tlo;
-            v2 = v3 = -thi;
-        } else if (clo <= 2 * WAVE && chi <= 2 * WAVE) {
+        if (clo <= 2 * WAVE && chi <= 2 * WAVE) {
             pick_tail<2>(Ll, clo, i0, j0, tlo, v0, v1);
             pick_tail<2>(Lh, chi, ci, cj, -thi, v3, v2);
         } else {   // heavy tails: rare, 256 candidates
@@ -1189,10 +1171,7 @@ __device__ __forceinline__ void load_seg_col(const double* src, int L, double (&
 #pragma unroll
     for (int v = 0; v < VPL; ++v) {
         const uint32_t off = lb + (uint32_t)(v * WAVE * 8);
-        if (FM_AB_SEL_NOLOAD)
-            xv[v] = (double)((off * 2654435761u) >> 12) * 1e-6 + (double)(size_t)src * 1e-30;
-        else
-            xv[v] = *(const __attribute__((address_space(1))) double*)(b + (off < lastb ? off : lastb));
+        xv[v] = *(const __attribute__((address_space(1))) double*)(b + (off < lastb ? off : lastb));
     }
 }
 

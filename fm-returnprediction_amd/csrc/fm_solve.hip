@@ -36,15 +36,6 @@ constexpr double EIG_REL = 1e-12;
 // the 1e-9 contract, so the problem is flagged FM_ST_REFIT and re-solved from its rows by
 // fm_solve_fixup (Householder QR + SVD of R: error ~eps * cond(X), as statsmodels' SVD).
 constexpr double REFIT_REL = 1e-6;
-#ifndef FM_AB_SOLVE_STOP
-#define FM_AB_SOLVE_STOP 0    // timing builds only: 1 stop after the bucket sums, 2 after the centering
-#endif
-#ifndef FM_AB_SOLVE_MOMROW
-#define FM_AB_SOLVE_MOMROW 0  // timing builds only: the moments stored one S row per lane
-#endif
-#ifndef FM_AB_SOLVE_NOMOM
-#define FM_AB_SOLVE_NOMOM 0   // timing builds only (tools/build_variant.sh): skip the moments store
-#endif
 
 template <int MD>
 struct WaveScratch {
@@ -374,9 +365,6 @@ __global__ __launch_bounds__(VT) void solve_kernel(fm_solve_args a) {
 // factorizations run in the time of one.  Rank-deficient problems (rare) take the Jacobi
 // pseudo-inverse path one at a time.
 
-#ifndef FM_SOLVE_RSQ
-#define FM_SOLVE_RSQ 1
-#endif
 // 1 / sqrt(x) for a positive normal x: v_rsq_f64 refined by two Newton steps
 __device__ __forceinline__ double rsq_nr(double x) {
     double y = __builtin_amdgcn_rsq(x);
@@ -478,10 +466,6 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
     }
     __syncthreads();
     FM_PROBE_AT(solve, 2);
-    if (FM_AB_SOLVE_STOP == 1) {
-        if (tid == 0) a.status[(int64_t)s * a.nprob] = (uint32_t)bs[0];
-        return;
-    }
     const int g = lane >> 4, i = lane & 15;
     const int rs = a.pmax + 2;
     double* T = wsc[w] + g * TT;
@@ -557,7 +541,7 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
             if (i == 0) a.status[(int64_t)s * a.nprob + pp] = t_st[pp] = FM_ST_SKIPPED;
         }
         const bool act0 = live && !skip;
-        if (act0 && a.moments && !FM_AB_SOLVE_NOMOM) {
+        if (act0 && a.moments) {
             double* mo = a.moments + ((int64_t)s * a.nprob + pp) * a.mom_stride;
             if (i == 0) mo[0] = n;
             if (srow) {
@@ -568,18 +552,11 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
                 // strides K1 doubles between lanes)
 #pragma unroll
                 for (int c = 0; c < G16 - 1; ++c)
-                    if (c < K1) {
-                        if (FM_AB_SOLVE_MOMROW) mo[1 + K1 + (i - 1) * K1 + c] = row[c];
-                        else mo[1 + K1 + c * K1 + (i - 1)] = row[c];
-                    }
+                    if (c < K1) mo[1 + K1 + c * K1 + (i - 1)] = row[c];
             }
         }
         if (act0 && (t_flags[pp] & 1) != 0) {
             if ((__ballot(i >= 1 && i <= K && !(sii > 1e-10 * gdiag)) & gm) != 0) st |= FM_ST_CONST_SUSPECT;
-        }
-        if (FM_AB_SOLVE_STOP == 2) {
-            if (live && i == 0) a.rec[ro] = row[0] + row[1] + mu;
-            continue;
         }
         FM_PROBE_AT(solve, 5);
         // ---- augmented Cholesky of S (pivot r = k sits in lane k + 1)
@@ -595,15 +572,10 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
             const bool bad = act && (!(orig > 0.0) || !(piv > CHOL_REL * orig));
             if (bad) ok = false;
             const bool go = act && !bad;
-#if FM_SOLVE_RSQ
             // 1 / sqrt(piv) by the hardware estimate and two Newton steps (error ~1 ulp), sqrt
             // as piv times it: no IEEE sqrt and division sequences on the pivot chain
             const double rinv = rsq_nr(piv);
             const double lkk = piv * rinv;
-#else
-            const double lkk = sqrt(piv);
-            const double rinv = 1.0 / lkk;
-#endif
             const double lik = row[k] * rinv;
             // unguarded: the entries a guard would keep are never read again -- columns past
             // the problem's K (and, once k >= K, everything this step touches) are not used by

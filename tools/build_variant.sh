@@ -1,6 +1,10 @@
 #!/bin/bash
-# Timing variants of libfm_hip.so for tools/kbench.py A/B runs (never shipped):
+# Probe and tuning variants of libfm_hip.so (never shipped):
 #   tools/build_variant.sh <name> "<extra hipcc flags>" source.hip [source.hip ...]
+# The flags the sources still take: -DFM_PROBE=1 (tools/tail_probe.py), -DFM_GRAM_WGTIME=1
+# (tools/gram_wgtime.py) and the numeric parameters (FM_GRAM_MINW, FM_STD_T / _R / _LP,
+# FM_TS_RROWS, FM_SELECT_STREAM_VPT / _SB, FM_PAIR_HK_WGS, FM_NP_MOM_DEPTH) for
+# tools/kbench.py A/B runs.  The sources hold no ablation or strategy switches any more.
 # Reuses the in-tree objects and recompiles only the listed sources with the extra flags
 # into build_variants/<name>/libfm_hip.so.
 set -e
