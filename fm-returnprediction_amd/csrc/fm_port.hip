@@ -1,0 +1,460 @@
+// fm_portfolio_sort: forecast-sorted portfolios (build-defined extension A12; paper Table 5).
+// One workgroup per month, four phases:
+//   1. every thread loads its rows' forecast / level / NYSE byte once (wave w owns the rows
+//      [w * VPT * 64, (w + 1) * VPT * 64), so row order = (wave, v, lane) order) and keeps the
+//      eligible forecasts in registers, with a bit per breakpoint row;
+//   2. the 2 (nport - 1) exact order statistics of the breakpoint rows' order-preserving keys:
+//      months of more than 2,048 such rows by a sample select (splitters from a sorted sample,
+//      a counting pass over the buckets, then only the buckets that hold a target rank are
+//      gathered and sorted), shorter months and months whose target buckets overfill (heavy
+//      ties) by an LDS bitonic sort of all keys; then the numpy 'linear' breakpoints (qranks /
+//      qlerp, mode 0).  Both ways give the same keys, so which one ran never shows;
+//   3. every row is binned against the breakpoints in LDS, its portfolio byte written, and a
+//      stable partition (ballot ranks; per-wave counts prefixed over the waves) gives each row
+//      its place in its portfolio's list, in row order;
+//   4. the rows' owners read return and weight (coalesced, once) and stage one term at a time
+//      at the rows' list places in the LDS the keys have left; wave k sums portfolio k's
+//      stretch (lane l takes entries l, l + 64, ...) and reduces with the fixed butterfly:
+//      every sum's order depends on the month's rows alone, not on the grid, the thread count
+//      or the other months.
+// Forecast, return, weight, level and NYSE byte are each read from HBM once (months of more
+// than 5,120 rows re-read return and weight per term, from the cache).
+#include <math.h>
+
+#include "fm_common.h"
+#include "fm_select_dev.h"
+
+// phase marks of port_kernel (probe builds only, fm_common.h): 0 start, 1 rows loaded and
+// counted, 2 sample sorted, 3 buckets counted and targets located, 4 order statistics,
+// 5 rows partitioned, 6 sums, 7 end
+FM_PROBE_BUFFER(port)
+
+namespace fm {
+namespace {
+
+constexpr int PORT_MAX_ROWS = 16384;   // 16 rows per thread of a 1024-thread workgroup
+
+constexpr int PSLOTS = 2 * (FM_MAX_PORTS - 1);   // order statistics per month
+constexpr int PCAP = 2 * WAVE;         // keys per candidate bucket (one wave sorts it)
+constexpr int PORT_FAST_MIN = 2048;    // more breakpoint rows: the sample select
+
+__host__ __device__ inline int pow2_ceil(int n) {
+    int p = 2;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+// In-place ascending bitonic sort of buf[0..P) (P a power of two) by the NT-thread workgroup;
+// ends with a barrier.
+template <int NT>
+__device__ __forceinline__ void lds_bitonic(uint64_t* buf, int P) {
+    const int tid = threadIdx.x;
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += NT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const uint64_t x = buf[i], y = buf[l];
+                if ((x > y) == ((i & k) == 0)) {
+                    buf[i] = y;
+                    buf[l] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <int NT, int VPT>
+__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_args a) {
+    constexpr int NW = NT / WAVE;
+    extern __shared__ uint64_t pbuf[];   // the keys; after the breakpoints the row lists
+    __shared__ double s_bp[FM_MAX_PORTS];
+    __shared__ double s_rec[FM_MAX_PORTS][4];
+    __shared__ double s_sum[FM_MAX_PORTS][6];
+    __shared__ int s_wcnt[NW][FM_MAX_PORTS], s_wbase[NW][FM_MAX_PORTS];
+    __shared__ int s_start[FM_MAX_PORTS + 1];
+    __shared__ double s_g[FM_MAX_PORTS];
+    __shared__ uint64_t s_okey[PSLOTS];
+    __shared__ int s_trank[PSLOTS], s_tslot[PSLOTS], s_tbase[PSLOTS], s_ccnt[PSLOTS];
+    __shared__ int s_iscr[NW];
+    __shared__ int s_n, s_over;
+    const int s = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int nport = a.nport, nm1 = nport - 1;
+    const int64_t r0 = a.seg_off[s];
+    int L = (int)(a.seg_off[s + 1] - r0);
+    L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
+    const double* __restrict__ F = a.forecast + r0;
+
+    FM_PROBE_AT(port, 0);
+    // ---- 1. load, eligibility, breakpoint rows -------------------------------------------
+    double fe[VPT];     // the eligible rows' forecasts, NaN otherwise
+    uint32_t bpm = 0;   // bit v: row v of this thread is a breakpoint row
+    if (L > 0) {        // block-uniform
+        const int last = L - 1;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
+            const int idx = (w * VPT + v) * WAVE + lane;
+            const int ci = idx < L ? idx : last;
+            const double f = F[ci];
+            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
+            const int ny = a.nyse != nullptr ? (int)a.nyse[r0 + ci] : 1;
+            const bool elig = idx < L && isfinite(f) && lv >= a.min_level;
+            fe[v] = elig ? f : NAN;
+            bpm |= (elig && (a.nyse_breakpoints == 0 || ny != 0)) ? 1u << v : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) fe[v] = NAN;
+    }
+    const int n = block_sum<NW>((int)__popc(bpm), s_iscr);
+    FM_PROBE_AT(port, 1);
+    uint8_t* port = a.port != nullptr ? a.port + r0 : nullptr;
+    double* rec = a.rec + (int64_t)s * (nport + 1) * 4;
+    int32_t* cnt = a.cnt + (int64_t)s * nport;
+
+    if (n < a.min_count) {   // block-uniform: the month is unsorted
+        if (tid == 0) a.status[s] = 0u;
+        if (tid < nm1 && a.bp != nullptr) a.bp[(int64_t)s * nm1 + tid] = NAN;
+        if (tid < (nport + 1) * 4) rec[tid] = NAN;
+        if (tid < nport) cnt[tid] = 0;
+        if (port != nullptr) {
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) {
+                const int idx = (w * VPT + v) * WAVE + lane;
+                if (idx < L) port[idx] = 255;
+            }
+        }
+        return;
+    }
+
+    // ---- 2. the 2 (nport - 1) order statistics, breakpoints ----------------------------------
+    const int nt = 2 * nm1;   // targets: ranks (i, j) of each level
+    if (tid < nm1) {
+        int i, j;
+        double g;
+        qranks(n, a.q[tid], 0, i, j, g);
+        s_trank[2 * tid] = i;
+        s_trank[2 * tid + 1] = j;
+        s_g[tid] = g;
+    }
+    if (tid == 0) {
+        s_n = 0;
+        s_over = 0;
+    }
+    bool have = false;   // block-uniform: s_okey holds the keys at the target ranks
+    if constexpr (NT >= 512) {
+        if (n > PORT_FAST_MIN) {
+            // Sample select: NT sample keys (each thread's first breakpoint row) sorted into
+            // splitters; every key is bucketed by binary search, the buckets counted and
+            // scanned, and only the buckets that hold a target rank are gathered (<= PCAP keys
+            // each, else the full sort below) and sorted, one wave per bucket.  Exact whatever
+            // the sample: a poor one only overfills a bucket.
+            uint64_t* samp = pbuf;
+            uint32_t* hist = reinterpret_cast<uint32_t*>(samp + NT);
+            uint8_t* slot = reinterpret_cast<uint8_t*>(hist + NT);
+            uint64_t* cand = reinterpret_cast<uint64_t*>(slot + NT);
+            {
+                const int first = bpm != 0u ? __ffs((int)bpm) - 1 : -1;
+                uint64_t key = SENT;
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) key = v == first ? dkey(fe[v]) : key;
+                samp[tid] = key;
+                hist[tid] = 0u;
+                if (tid < PSLOTS) s_ccnt[tid] = 0;
+            }
+            __syncthreads();
+            lds_bitonic<NT>(samp, NT);
+            FM_PROBE_AT(port, 2);
+            int bk[VPT];   // min(#{samples <= key}, NT - 1): monotone in the key
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) bk[v] = 0;
+            // all rows in step (VPT reads in flight) where the registers allow, else row by row
+            constexpr int SG = VPT <= 10 ? VPT : 1;
+#pragma unroll
+            for (int v0 = 0; v0 < VPT; v0 += SG) {
+                if (SG == 1 && !((bpm >> v0) & 1u)) continue;
+#pragma unroll
+                for (int step = NT / 2; step > 0; step >>= 1) {
+#pragma unroll
+                    for (int v = v0; v < v0 + SG; ++v) {
+                        const uint64_t key = ((bpm >> v) & 1u) ? dkey(fe[v]) : SENT;
+                        bk[v] += samp[bk[v] + step - 1] <= key ? step : 0;
+                    }
+                }
+                if (SG == 1) atomicAdd(&hist[bk[v0]], 1u);
+            }
+            if (SG > 1) {
+#pragma unroll
+                for (int v = 0; v < VPT; ++v)
+                    if ((bpm >> v) & 1u) atomicAdd(&hist[bk[v]], 1u);
+            }
+            __syncthreads();
+            const int x = (int)hist[tid];
+            int tot;
+            const int excl = block_excl_scan<NW>(x, s_iscr, &tot);
+            const int trv = lane < nt ? s_trank[lane] : -1;   // lane t: target rank t
+            int flag = 0;
+            for (int t = 0; t < nt; ++t) {
+                const int r = __builtin_amdgcn_readlane(trv, t);
+                flag |= (r >= excl && r < excl + x) ? 1 : 0;
+            }
+            int nslots;
+            const int sid = block_excl_scan<NW>(flag, s_iscr, &nslots);
+            slot[tid] = flag ? (uint8_t)sid : (uint8_t)255;
+            if (flag) {
+                if (x > PCAP) s_over = 1;
+                for (int t = 0; t < nt; ++t) {
+                    const int r = s_trank[t];   // (divergent here: no readlane)
+                    if (r >= excl && r < excl + x) {
+                        s_tslot[t] = sid;
+                        s_tbase[t] = excl;
+                    }
+                }
+            }
+            __syncthreads();
+            FM_PROBE_AT(port, 3);
+            if (s_over == 0) {   // block-uniform
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    if ((bpm >> v) & 1u) {
+                        const int sl = slot[bk[v]];
+                        if (sl != 255) cand[sl * PCAP + atomicAdd(&s_ccnt[sl], 1)] = dkey(fe[v]);
+                    }
+                }
+                __syncthreads();
+                for (int sl = w; sl < nslots; sl += NW) wave_sort_lds<PCAP / WAVE>(cand + sl * PCAP, s_ccnt[sl]);
+                __syncthreads();
+                if (tid < nt) s_okey[tid] = cand[s_tslot[tid] * PCAP + s_trank[tid] - s_tbase[tid]];
+                have = true;
+            }
+        }
+    }
+    if (!have) {
+        // Full sort (short months, or an overfull bucket: heavy ties): the keys compacted into
+        // LDS (ballot + one integer LDS add per wave; their order does not matter), padded to a
+        // power of two, bitonic-sorted.
+        __syncthreads();
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const bool isbp = (bpm >> v) & 1u;
+            const uint64_t m = __ballot(isbp);
+            const int c = (int)__popcll(m);
+            int base = 0;
+            if (lane == 0 && c > 0) base = atomicAdd(&s_n, c);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (isbp) pbuf[base + mask_rank(m)] = dkey(fe[v]);
+        }
+        const int P = pow2_ceil(n);
+        for (int i = n + tid; i < P; i += NT) pbuf[i] = SENT;
+        __syncthreads();
+        lds_bitonic<NT>(pbuf, P);
+        if (tid < nt) s_okey[tid] = pbuf[s_trank[tid]];
+    }
+    __syncthreads();
+    if (tid < nm1) {
+        const double b = qlerp(kval(s_okey[2 * tid]), kval(s_okey[2 * tid + 1]), s_g[tid], 0);
+        s_bp[tid] = b;
+        if (a.bp != nullptr) a.bp[(int64_t)s * nm1 + tid] = b;
+    }
+    FM_PROBE_AT(port, 4);
+    __syncthreads();   // the keys are dead from here: pbuf becomes the row lists
+
+    // ---- 3. bin the rows, stable partition by portfolio ------------------------------------
+    int pt[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) pt[v] = 0;
+    constexpr int BG = VPT <= 10 ? VPT : VPT / 2;   // rows binned against one LDS read of a breakpoint
+#pragma unroll
+    for (int v0 = 0; v0 < VPT; v0 += BG) {
+        for (int j = 0; j < nm1; ++j) {
+            const double b = s_bp[j];
+#pragma unroll
+            for (int v = v0; v < v0 + BG; ++v) pt[v] += fe[v] > b ? 1 : 0;
+        }
+    }
+    int pos[VPT];   // the row's place in its portfolio's list (row order), -1: in no portfolio
+    int cvec = 0;   // lane k: this wave's rows of portfolio k so far
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const int idx = (w * VPT + v) * WAVE + lane;
+        const int p = isnan(fe[v]) ? 255 : pt[v];
+        if (port != nullptr && idx < L) port[idx] = (uint8_t)p;
+        int pp = -1;   // (place among this wave's rows of p) << 8 | p
+        for (int k = 0; k < nport; ++k) {
+            const uint64_t m = __ballot(p == k);
+            const int before = __builtin_amdgcn_readlane(cvec, k);
+            if (p == k) pp = ((before + mask_rank(m)) << 8) | k;
+            cvec += lane == k ? (int)__popcll(m) : 0;
+        }
+        pos[v] = pp;
+    }
+    if (lane < nport) s_wcnt[w][lane] = cvec;
+    __syncthreads();
+    {
+        int before = 0, tot = 0;
+        if (lane < nport) {
+#pragma unroll
+            for (int q = 0; q < NW; ++q) {
+                const int c = s_wcnt[q][lane];
+                before += q < w ? c : 0;
+                tot += c;
+            }
+        }
+        const int incl = wave_incl_scan(tot);
+        if (lane < nport) s_wbase[w][lane] = incl - tot + before;   // this wave's first place in list k
+        if (w == 0) {
+            if (lane < nport) s_start[lane] = incl - tot;
+            if (lane == nm1) s_start[nport] = incl;
+        }
+    }
+    wave_sync();
+#pragma unroll
+    for (int v = 0; v < VPT; ++v)
+        if (pos[v] >= 0) pos[v] = (pos[v] >> 8) + s_wbase[w][pos[v] & 255];
+
+    FM_PROBE_AT(port, 5);
+    // ---- 4. per-portfolio sums ----------------------------------------------------------------
+    // return and weight: read once, coalesced, by the rows' owners; kept in registers where the
+    // budget allows (HOLD), else re-read per term from the cache
+    constexpr bool HOLD = VPT <= 10;
+    const double* __restrict__ R = a.ret + r0;
+    const double* __restrict__ W = a.weight != nullptr ? a.weight + r0 : nullptr;
+    double r[HOLD ? VPT : 1], x[HOLD ? VPT : 1];
+    if constexpr (HOLD) {
+        const int last = L - 1;   // L > 0: the month is sorted
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = (w * VPT + v) * WAVE + lane;
+            const int ci = idx < L ? idx : last;
+            r[v] = R[ci];
+            x[v] = W != nullptr ? W[ci] : NAN;
+        }
+    }
+    // One term at a time: every row's term is staged at its list position (pbuf, 8 bytes a row),
+    // then wave k sums portfolio k's stretch (lane l takes entries l, l + 64, ...; the fixed
+    // butterfly across lanes).  Rows that do not count stage 0.  Pass 0 stages the two counts as
+    // one exact double: 1 for a finite return + 2^20 for a usable weight as well.
+    double* stage = reinterpret_cast<double*>(pbuf);
+    const int npass = W != nullptr ? 6 : 3;
+#pragma unroll 1
+    for (int t = 0; t < npass; ++t) {   // block-uniform
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            if (pos[v] >= 0) {
+                const int idx = (w * VPT + v) * WAVE + lane;   // < L: the row is eligible
+                double rr, ww;
+                if constexpr (HOLD) {
+                    rr = r[v];
+                    ww = x[v];
+                } else {
+                    rr = R[idx];
+                    ww = W != nullptr ? W[idx] : NAN;
+                }
+                const bool okr = isfinite(rr), okw = okr && isfinite(ww) && ww > 0.0;
+                // term t = 1: r, 2: f, 3: w, 4: w r, 5: w f (a factor 1.0 is exact); selected by t
+                // here, so that nothing is hoisted out of the pass loop into registers
+                const double m1 = (t == 1 || t == 4) ? rr : ((t == 2 || t == 5) ? fe[v] : 1.0);
+                const double m2 = t >= 3 ? ww : 1.0;
+                double y = (t >= 3 ? okw : okr) ? m1 * m2 : 0.0;
+                if (t == 0) y = (okr ? 1.0 : 0.0) + (okw ? 1048576.0 : 0.0);
+                stage[pos[v]] = y;
+            }
+        }
+        __syncthreads();
+        for (int k = w; k < nport; k += NW) {   // wave-uniform
+            const int beg = s_start[k], end = s_start[k + 1];
+            double acc = 0.0;
+            for (int p0 = beg; p0 < end; p0 += 4 * WAVE) {   // four reads in flight, added in order
+                double y[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int p = p0 + u * WAVE + lane;
+                    const double z = stage[p < end ? p : end - 1];
+                    y[u] = p < end ? z : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc += y[u];
+            }
+            acc = wave_sum(acc);
+            if (lane == 0) s_sum[k][t] = acc;
+        }
+        __syncthreads();
+    }
+    FM_PROBE_AT(port, 6);
+    if (tid < nport) {
+        const int k = tid;
+        const int64_t both = (int64_t)s_sum[k][0];
+        const int c = (int)(both & 1048575), cw = (int)(both >> 20);
+        const double e0 = c > 0 ? s_sum[k][1] / (double)c : NAN, e1 = c > 0 ? s_sum[k][2] / (double)c : NAN;
+        const double v0 = cw > 0 ? s_sum[k][4] / s_sum[k][3] : NAN, v1 = cw > 0 ? s_sum[k][5] / s_sum[k][3] : NAN;
+        s_rec[k][0] = e0;
+        s_rec[k][1] = e1;
+        s_rec[k][2] = v0;
+        s_rec[k][3] = v1;
+        rec[k * 4 + 0] = e0;
+        rec[k * 4 + 1] = e1;
+        rec[k * 4 + 2] = v0;
+        rec[k * 4 + 3] = v1;
+        cnt[k] = c;
+    }
+    __syncthreads();
+    if (tid < 4) rec[nport * 4 + tid] = s_rec[nm1][tid] - s_rec[0][tid];   // NaN if an end is NaN
+    FM_PROBE_AT(port, 7);
+    if (tid == 0) a.status[s] = 1u;
+}
+
+template <int NT, int VPT>
+int launch_port(const fm_port_args& a, size_t lds, hipStream_t st) {
+    if (lds >= 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in (once)
+        static bool attr_set = false;
+        if (!attr_set) {
+            if (hipFuncSetAttribute((const void*)port_kernel<NT, VPT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    8 * pow2_ceil(NT * VPT)) != hipSuccess) {
+                set_error("fm_portfolio_sort: cannot raise the dynamic LDS limit");
+                return FM_EHIP;
+            }
+            attr_set = true;
+        }
+    }
+    hipLaunchKernelGGL((port_kernel<NT, VPT>), dim3(a.nseg), dim3(NT), lds, st, a);
+    return FM_OK;
+}
+
+}  // namespace
+}  // namespace fm
+
+extern "C" int fm_portfolio_sort(const fm_port_args* args, void* stream) {
+    using namespace fm;
+    FM_REQUIRE(args != nullptr, "fm_portfolio_sort: null args");
+    const fm_port_args& a = *args;
+    FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0, "fm_portfolio_sort: bad sizes");
+    FM_REQUIRE(a.nport >= 2 && a.nport <= FM_MAX_PORTS, "fm_portfolio_sort: nport must be 2..%d", FM_MAX_PORTS);
+    for (int j = 0; j < a.nport - 1; ++j) {
+        const double lo = j == 0 ? 0.0 : a.q[j - 1];
+        FM_REQUIRE(a.q[j] > lo && a.q[j] < 1.0, "fm_portfolio_sort: q must be strictly ascending in (0, 1)");
+    }
+    FM_REQUIRE(a.nyse_breakpoints == 0 || a.nyse != nullptr, "fm_portfolio_sort: nyse_breakpoints needs nyse");
+    FM_REQUIRE(a.min_count >= 1, "fm_portfolio_sort: min_count must be >= 1");
+    FM_REQUIRE(a.min_level >= 0 && a.min_level <= 255, "fm_portfolio_sort: min_level must be 0..255");
+    if (a.max_seg_len > PORT_MAX_ROWS) {
+        set_error("fm_portfolio_sort: %d-row months exceed %d", a.max_seg_len, PORT_MAX_ROWS);
+        return FM_ETOOBIG;
+    }
+    if (a.nseg == 0) return FM_OK;
+    FM_REQUIRE(a.forecast && a.ret && a.seg_off && a.rec && a.cnt && a.status, "fm_portfolio_sort: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    // the keys of the full sort; months that can reach the sample select hold its tables instead
+    size_t lds = 8 * (size_t)pow2_ceil(a.max_seg_len);
+    const size_t fast = 13 * (size_t)(a.max_seg_len <= 512 * 10 ? 512 : 1024) + (size_t)PSLOTS * PCAP * 8;
+    if (a.max_seg_len > PORT_FAST_MIN && lds < fast) lds = fast;
+    int rc;
+    if (a.max_seg_len <= 256 * 4) rc = launch_port<256, 4>(a, lds, st);
+    else if (a.max_seg_len <= 512 * 10) rc = launch_port<512, 10>(a, lds, st);
+    else rc = launch_port<1024, 16>(a, lds, st);
+    if (rc != FM_OK) return rc;
+    FM_CHECK_LAUNCH("fm_portfolio_sort");
+    return FM_OK;
+}

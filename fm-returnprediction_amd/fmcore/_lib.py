@@ -25,6 +25,7 @@ FM_ST_REFIT = 0x80
 FM_MAX_COLS = 31
 FM_MAX_MODELS = 6
 FM_MAX_LEVELS = 3
+FM_MAX_PORTS = 20
 FM_TS_FUSED_MAX_LDS = 128 * 1024
 
 _p = C.c_void_p
@@ -102,6 +103,15 @@ class CharsArgs(C.Structure):
     _fields_ = [("ids", _p), ("n", _i64), ("field", _p * FM_NFIELDS), ("out", _p * FM_NCHARS)]
 
 
+class PortArgs(C.Structure):
+    _fields_ = [
+        ("forecast", _p), ("ret", _p), ("weight", _p), ("level", _p), ("nyse", _p), ("seg_off", _p),
+        ("nseg", _i32), ("max_seg_len", _i32), ("nport", _i32), ("min_level", _i32),
+        ("nyse_breakpoints", _i32), ("min_count", _i32), ("q", _f64 * (FM_MAX_PORTS - 1)),
+        ("bp", _p), ("port", _p), ("rec", _p), ("cnt", _p), ("status", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -139,6 +149,7 @@ _SIGS = {
     "fm_ts_fused": (_i32, [C.POINTER(TsArgs), _p]),
     "fm_ts_fused_lds_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "fm_forecast": (_i32, [_p, _i64, _i32, _p, _i32, _i64, _p, _i32, _p, _p]),
+    "fm_portfolio_sort": (_i32, [C.POINTER(PortArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -153,7 +164,8 @@ _SIGS = {
 
 EXPORTED = tuple(_SIGS)
 _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_args": SelectArgs,
-            "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs}
+            "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs,
+            "fm_port_args": PortArgs}
 
 _lib = None
 

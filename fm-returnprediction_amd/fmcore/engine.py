@@ -1144,6 +1144,81 @@ def forecast(panel: DevicePanel, coef, cols=None):
     return out
 
 
+PORT_MAX_ROWS = 16384   # fm_portfolio_sort's month limit (one workgroup per month, keys in LDS)
+
+
+@dataclass
+class Portfolios:
+    bp: torch.Tensor       # [T, nport-1] float64 breakpoints (NaN: unsorted month)
+    port: torch.Tensor     # [rows] uint8 portfolio 0..nport-1, 255 = none
+    rec: torch.Tensor      # [T, nport+1, 4] float64: ew ret, ew forecast, vw ret, vw forecast; last = H-L
+    cnt: torch.Tensor      # [T, nport] int32 rows with a finite return
+    status: torch.Tensor   # [T] int32: 1 = sorted month
+
+
+def _row_vector(t, dtype, n, dev, what):
+    if t is None:
+        return None
+    if t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or t.device != dev:
+        raise ValueError(f"portfolio_sort: {what} must be a {dtype} [{n}] tensor on {dev}")
+    return t.contiguous()
+
+
+def portfolio_sort(seg_off, forecast, ret, weight=None, level=None, nyse=None, nport=10, q=None,
+                   min_level=0, nyse_breakpoints=False, min_count=None, max_seg_len=None):
+    """A12: per month (``seg_off`` int64 [T+1] device, rows sorted by month) sort the rows into
+    ``nport`` portfolios by ``forecast`` and average each portfolio's ``ret`` and forecast,
+    equal- and ``weight``-weighted, plus the high-minus-low spread (fm_portfolio_sort; the
+    definition is in fm_hip.h).  Plain device tensors in, ``Portfolios`` of device tensors out.
+    ``q``: the nport-1 breakpoint levels (default k / nport); ``max_seg_len``: the longest
+    month if the caller knows it (otherwise read from ``seg_off``, one host sync)."""
+    dev = forecast.device
+    n = int(forecast.shape[0])
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("portfolio_sort: seg_off must be an int64 [T+1] tensor on the forecast's device")
+    seg_off = seg_off.contiguous()
+    T = int(seg_off.shape[0]) - 1
+    forecast = _row_vector(forecast, torch.float64, n, dev, "forecast")
+    ret = _row_vector(ret, torch.float64, n, dev, "ret")
+    weight = _row_vector(weight, torch.float64, n, dev, "weight")
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    nyse = _row_vector(nyse, torch.uint8, n, dev, "nyse")
+    nport = int(nport)
+    if max_seg_len is None:
+        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    a = L.PortArgs()
+    a.forecast, a.ret, a.weight, a.level, a.nyse = _ptr(forecast), _ptr(ret), _ptr(weight), _ptr(level), _ptr(nyse)
+    a.seg_off, a.nseg, a.max_seg_len = seg_off.data_ptr(), T, int(max_seg_len)
+    a.nport, a.min_level, a.nyse_breakpoints = nport, int(min_level), int(bool(nyse_breakpoints))
+    a.min_count = nport if min_count is None else int(min_count)
+    qs = list(q) if q is not None else [k / nport for k in range(1, max(nport, 1))]
+    if q is not None and len(qs) != nport - 1:
+        raise ValueError(f"portfolio_sort: q must hold nport - 1 = {nport - 1} levels, got {len(qs)}")
+    for j, v in enumerate(qs[:L.FM_MAX_PORTS - 1]):
+        a.q[j] = float(v)
+    np_ = min(max(nport, 2), L.FM_MAX_PORTS)   # output shapes of a call the library will refuse
+    out = Portfolios(bp=torch.empty((T, np_ - 1), dtype=torch.float64, device=dev),
+                     port=torch.empty(n, dtype=torch.uint8, device=dev),
+                     rec=torch.empty((T, np_ + 1, 4), dtype=torch.float64, device=dev),
+                     cnt=torch.empty((T, np_), dtype=torch.int32, device=dev),
+                     status=torch.empty(T, dtype=torch.int32, device=dev))
+    a.bp, a.port, a.rec, a.cnt, a.status = (out.bp.data_ptr(), out.port.data_ptr(), out.rec.data_ptr(),
+                                             out.cnt.data_ptr(), out.status.data_ptr())
+    _kcall("fm_portfolio_sort", "fm_portfolio_sort", L.C.byref(a), _stream())
+    _remember("fm_portfolio_sort", "fm_portfolio_sort", a, seg_off, forecast, ret, weight, level, nyse, out)
+    return out
+
+
+def portfolio_summary(p: Portfolios, nw_lags=4):
+    """FM mean, Newey-West s.e., t and nobs of the (nport+1) * 4 monthly series of ``p.rec`` over
+    the sorted months (status 1), NaN entries dropped per series -> ``Summary`` with
+    [nport+1, 4] tensors."""
+    T, n1, k = p.rec.shape
+    ix = ts_compact(p.status.view(T, 1), 1, 1, T, 1)
+    s = ts_summary(p.rec, n1 * k, n1 * k, ix, T, 1, n1 * k, nw_lags)
+    return Summary(s.mean.view(n1, k), s.se.view(n1, k), s.tstat.view(n1, k), s.nobs.view(n1, k))
+
+
 def segment_moments(panel: DevicePanel, level=None, min_level=0, finite_only=True, cols=None):
     """Per (column, month) count, mean and ddof=1 std of the non-missing values."""
     src = panel.values() if cols is None else cols

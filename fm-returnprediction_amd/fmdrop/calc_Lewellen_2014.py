@@ -9,7 +9,7 @@ Mirrored (same names, signatures, return types and row/column/index order):
   create_figure_1  reference :871-957   F1 OLS + 120-month rolling means on device
 Extensions the north star names (not in the reference; parity unpinned):
   standardize, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
-  predictive_slope_regressions, lewellen_pipeline.
+  predictive_slope_regressions, forecast_sorted_portfolios, lewellen_pipeline.
 Firm-axis characteristic builders (§8(f) row 2; one fused device pass, fm_firm_chars):
   calc_log_size, calc_log_bm, calc_return_12_2, calc_accruals, calc_roa,
   calc_log_assets_growth, calc_dy, calc_log_return_13_36, calc_log_issues_12,
@@ -625,6 +625,57 @@ def predictive_slope_regressions(df: pd.DataFrame, forecast, return_col: str = "
                       "forecast": np.asarray(forecast, dtype=np.float64)})
     cs = run_monthly_cs_regressions(d, return_col, ["forecast"], date_col)
     return cs, fama_macbeth_summary(cs, ["forecast"], date_col, nw_lags)
+
+
+PORTFOLIO_COLUMNS = ["ew_ret", "ew_pred", "vw_ret", "vw_pred"]
+_UNIVERSE_LEVEL = {None: 0, "all_but_tiny": 1, "large": 2}
+
+
+def forecast_sorted_portfolios(df: pd.DataFrame, forecast, return_col: str = "retx", weight_col: str = None,
+                               nport: int = 10, breakpoints=None, universe: str = None,
+                               nyse_breakpoints: bool = False, date_col: str = "mthcaldt", nw_lags: int = 4):
+    """A12 (paper Table 5): each month, sort the stocks into ``nport`` portfolios by ``forecast``
+    (right-closed bins at the np.quantile levels ``breakpoints``, default k / nport; with
+    ``nyse_breakpoints`` from the NYSE rows only) and average each portfolio's realised return
+    and forecast, equal- and ``weight_col``-weighted (None: no value weights, NaN columns), on
+    the device (fm_portfolio_sort).  ``universe`` in {None, "all_but_tiny", "large"} keeps the
+    rows of that get_subsets universe (from ``me`` and ``primaryexch``).
+    Returns (monthly, summary): ``monthly`` is indexed by (month, portfolio 0..nport-1 and
+    "H-L") with columns ew_ret, ew_pred, vw_ret, vw_pred, n (rows with a return; for "H-L" of
+    both ends), sorted months only; ``summary`` is indexed by portfolio with columns
+    (column, mean / tstat / nobs): the FM mean and its Newey-West(nw_lags) t-statistic."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    f = np.asarray(forecast, dtype=np.float64)
+    if f.shape != (len(df),):
+        raise ValueError("forecast must hold one value per row of df")
+    order = np.lexsort((df["permno"].to_numpy(), df[date_col].to_numpy()))
+    d = df.iloc[order]
+    names = ["forecast", return_col] + ([weight_col] if weight_col is not None else [])
+    arrays = [f[order], _api.as_f64(d[return_col])] + ([_api.as_f64(d[weight_col])] if weight_col is not None else [])
+    need_nyse = nyse_breakpoints or universe is not None
+    me = _api.as_f64(d["me"]) if universe is not None else None
+    nyse = (d["primaryexch"] == "N").to_numpy().astype(np.uint8) if need_nyse else None
+    panel = _E.panel_from_arrays(arrays, names, d[date_col].values, me=me, nyse=nyse)
+    level = _E.universe(panel)[2] if universe is not None else None
+    p = _E.portfolio_sort(panel.seg_off, panel.cols[0], panel.cols[1],
+                          weight=panel.cols[2] if weight_col is not None else None, level=level, nyse=panel.nyse,
+                          nport=nport, q=breakpoints, min_level=_UNIVERSE_LEVEL[universe],
+                          nyse_breakpoints=nyse_breakpoints, max_seg_len=panel.max_seg_len)
+    s = _E.portfolio_summary(p, nw_lags)
+    labels = list(range(nport)) + ["H-L"]
+    srt = p.status.cpu().numpy() == 1
+    rec = p.rec.cpu().numpy()[srt]
+    cnt = p.cnt.cpu().numpy()[srt].astype(np.int64)
+    n = np.concatenate([cnt, cnt[:, :1] + cnt[:, -1:]], axis=1)
+    index = pd.MultiIndex.from_product([np.asarray(panel.months)[srt], labels], names=[date_col, "portfolio"])
+    monthly = pd.DataFrame(rec.reshape(-1, 4), index=index, columns=PORTFOLIO_COLUMNS)
+    monthly["n"] = n.reshape(-1)
+    mean, tstat, nobs = s.mean.cpu().numpy(), s.tstat.cpu().numpy(), s.nobs.cpu().numpy()
+    summary = pd.DataFrame({(c, stat): v[:, j] for j, c in enumerate(PORTFOLIO_COLUMNS)
+                            for stat, v in (("mean", mean), ("tstat", tstat), ("nobs", nobs))},
+                           index=pd.Index(labels, name="portfolio"))
+    return monthly, summary
 
 
 def lewellen_pipeline(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):

@@ -42,6 +42,8 @@
  *   fm_ts_fused     <- fm_ts_compact + fm_ts_summary + fm_rolling_mean + fm_predictive in
  *                      one launch (src/regressions.py:78-131; src/calc_Lewellen_2014.py:926)
  *   fm_forecast     <- build-defined extension A7: per-row F = a_{t-1} + b_{t-1}'x_t
+ *   fm_portfolio_sort <- build-defined extension: forecast-sorted portfolios, paper Table 5;
+ *                      no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -187,7 +189,7 @@ const char* fm_version(void);
 const char* fm_last_error(void);
 int fm_abi_sizes(int32_t* gram_args, int32_t* solve_args);
 /* sizeof the named argument struct ("fm_gram_args", "fm_solve_args", "fm_select_args",
- * "fm_universe_args", "fm_ts_args", "fm_chars_args"); -1 for an unknown name.  Bindings
+ * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args"); -1 for an unknown name.  Bindings
  * check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
 int fm_device_arch(char* buf, int32_t len);
@@ -404,6 +406,49 @@ int fm_ts_fused(const fm_ts_args* args, void* stream);
 int fm_forecast(const double* cols, int64_t col_stride, int32_t K, const int64_t* seg_off,
                 int32_t nseg, int64_t nrows, const double* coef, int32_t coef_stride,
                 double* out, void* stream);
+
+/* fm_portfolio_sort: per month, sort the stocks into nport portfolios by forecast and average
+ * each portfolio's realised return and forecast (build-defined extension A12; no reference
+ * line).  Rows sorted by (month, permno), months seg_off[nseg+1] of at most 16,384 rows
+ * (longer: FM_ETOOBIG before any launch).  Per month t:
+ *   eligible rows:   isfinite(forecast) and level >= min_level (level NULL: every row);
+ *   breakpoint rows: the eligible rows; with nyse_breakpoints those with nyse != 0;
+ *   fewer than min_count breakpoint rows: status[t] = 0, bp NaN, every port byte 255, rec NaN,
+ *     cnt 0; otherwise status[t] = 1 and
+ *   bp[t][j]   = numpy 'linear' quantile q[j] of the breakpoint rows' forecasts (exact order
+ *                statistics; the sign of an exactly-zero breakpoint is not specified);
+ *   port[row]  = #{ j : forecast > bp[t][j] } (right-closed bins) for eligible rows, else 255;
+ *   cnt[t][k]  = rows of portfolio k with a finite return; over those rows
+ *   rec[t][k]  = { mean return, mean forecast, sum(w ret) / sum(w), sum(w forecast) / sum(w) },
+ *                the last two over the rows that also have a finite weight > 0 (weight NULL:
+ *                NaN); an empty set gives NaN;
+ *   rec[t][nport] = rec[t][nport-1] - rec[t][0] (high minus low; NaN if either end is).
+ * Every output of a month depends on that month's rows alone, summed in a fixed order: two
+ * calls, or a month-sharded call, give the same bits.  Zero-initialize the struct (it grows
+ * at the end). */
+#define FM_MAX_PORTS 20
+typedef struct fm_port_args {
+    const double* forecast;      /* [rows] */
+    const double* ret;           /* [rows] */
+    const double* weight;        /* [rows] or NULL */
+    const uint8_t* level;        /* [rows] universe level or NULL */
+    const uint8_t* nyse;         /* [rows] nonzero = NYSE row, or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int32_t nseg;
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t nport;               /* 2 .. FM_MAX_PORTS */
+    int32_t min_level;
+    int32_t nyse_breakpoints;    /* nonzero: breakpoints from the NYSE rows only */
+    int32_t min_count;           /* >= 1 */
+    double q[FM_MAX_PORTS - 1];  /* [nport-1] levels, strictly ascending in (0, 1) */
+    double* bp;                  /* [nseg][nport-1] or NULL */
+    uint8_t* port;               /* [rows] or NULL */
+    double* rec;                 /* [nseg][nport+1][4] */
+    int32_t* cnt;                /* [nseg][nport] */
+    uint32_t* status;            /* [nseg] */
+} fm_port_args;
+
+int fm_portfolio_sort(const fm_port_args* args, void* stream);
 
 int fm_segment_moments(const double* cols, int64_t col_stride, int32_t ncols,
                        const int64_t* seg_off, int32_t nseg, const uint8_t* level,
