@@ -358,6 +358,489 @@ __global__ __launch_bounds__(VT) void solve_kernel(fm_solve_args a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// The statsmodels fix-ups of flagged (month, problem) pairs.  They run inside solve16_kernel
+// (zw == 16) or as the separate fm_solve_fixup / fm_const_check launches, and all read the
+// same things, held in one context: the panel rows (CA: FP64 columns or the two planes), the
+// per-(column, month) transforms, the problem tables and the solve's outputs.
+template <class CA>
+struct FixCtx {
+    CA cols; int64_t stride; const int64_t* seg_off; int nseg;   // rows of month s: seg_off[s..s+1]
+    const double *lo, *hi;                       // [ncols][nseg] clip bounds (both or neither)
+    const double *shift, *inv_scale, *add_back;  // [ncols][nseg] x -> (x - shift) * inv_scale (+ add_back)
+    const uint8_t* level;                        // per-row universe level, or null
+    int nprob; const int32_t *prob_level, *prob_z, *prob_nz;
+    const double* moments; int mom_stride;       // the solve's n, means and centered moments
+    int pmax; double* rec; uint32_t* status;
+    int check_const;
+};
+
+// Exact nonzero-constant test for problems flagged CONST_SUSPECT (statsmodels
+// add_constant(has_constant='skip'): np.ptp(x)==0 & all(x != 0), src/regressions.py:50).
+template <int NT = VT, class CA = F64Cols>
+__device__ __forceinline__ void const_pair(int s, int p, uint64_t* red, const FixCtx<CA>& fx) {
+    const int nz = fx.prob_nz[p], K = nz - 2, u = fx.prob_level[p];
+    const int* zi = fx.prob_z + p * 32;
+    const int64_t r0 = fx.seg_off[s], r1 = fx.seg_off[s + 1];
+    bool any_const = false;
+    for (int j = 0; j < K; ++j) {
+        const int cx = zi[1 + j] - 1;
+        uint64_t kmin = SENT, kmax = 0;
+        bool allnz = true;
+        for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
+            if (fx.level && (int)fx.level[r] < u) continue;
+            bool ok = true;
+            double xv = 0.0;
+            for (int q = 1; q < nz; ++q) {
+                const int c = zi[q] - 1;
+                double x = fx.cols[(int64_t)c * fx.stride + r];
+                if (fx.lo) {
+                    const double l = fx.lo[(int64_t)c * fx.nseg + s], h = fx.hi[(int64_t)c * fx.nseg + s];
+                    if (x < l) x = l;
+                    if (x > h) x = h;
+                }
+                if (isnan(x)) ok = false;
+                if (c == cx) xv = x;
+            }
+            if (!ok) continue;
+            const uint64_t k = dkey(xv == 0.0 ? 0.0 : xv);
+            kmin = k < kmin ? k : kmin;
+            kmax = k > kmax ? k : kmax;
+            if (xv == 0.0) allnz = false;
+        }
+        kmin = block_min_u64<NT / WAVE>(kmin, red);
+        kmax = block_max_u64<NT / WAVE>(kmax, red);
+        const int nzr = block_sum<NT / WAVE>(allnz ? 0 : 1, (int*)red);
+        if (kmin != SENT && kmin == kmax && nzr == 0) any_const = true;
+    }
+    if (threadIdx.x == 0 && any_const) fx.status[(int64_t)s * fx.nprob + p] |= FM_ST_CONST_COL;
+}
+
+// inf in y (statsmodels keeps the month): params = pinv(X) @ y, so each coefficient is the
+// IEEE sum of pinv[j,i] * y_i; with y_i = +-inf the finite rows do not matter and the
+// result is +inf, -inf or NaN (mixed signs, or 0*inf).  pinv[:,i] for the slopes is
+// Sxx^{-1}(x_i - xbar) and for the intercept 1/n - xbar'Sxx^{-1}(x_i - xbar).  One
+// workgroup per flagged (month, problem); R^2 becomes NaN as in statsmodels.
+struct InfySmem {
+    double Lm[32 * 32];
+    double mu[32], xb[32];
+    unsigned bits[32];
+    int okf;
+};
+
+template <int NT = VT, int NC = 32, class CA = F64Cols>
+__device__ __forceinline__ void infy_pair(int s, int p, InfySmem& sm, const FixCtx<CA>& fx) {
+    double* Lm = sm.Lm;
+    double* mu = sm.mu;
+    double* xb = sm.xb;
+    unsigned* bits = sm.bits;
+    int& okf = sm.okf;
+    const int nz = fx.prob_nz[p], K = nz - 2, K1 = K + 1, u = fx.prob_level[p];
+    const int* zi = fx.prob_z + p * 32;
+    const double* mo = fx.moments + ((int64_t)s * fx.nprob + p) * fx.mom_stride;
+    const double n = mo[0];
+    for (int e = threadIdx.x; e < K * K; e += NT) Lm[(e / K) * 32 + e % K] = mo[1 + K1 + (e / K) * K1 + e % K];
+    if (threadIdx.x < K1) mu[threadIdx.x] = mo[1 + threadIdx.x];
+    if (threadIdx.x < 32) bits[threadIdx.x] = 0u;
+    __syncthreads();
+    if (threadIdx.x < K) {
+        const int c = zi[1 + threadIdx.x] - 1;
+        xb[threadIdx.x] = mu[threadIdx.x] + (fx.add_back ? fx.add_back[(int64_t)c * fx.nseg + s] : 0.0);
+    }
+    if (threadIdx.x == 0) {
+        int ok = 1;
+        for (int k = 0; k < K && ok; ++k) {
+            double d = Lm[k * 32 + k];
+            for (int j = 0; j < k; ++j) d -= Lm[k * 32 + j] * Lm[k * 32 + j];
+            if (!(d > 0.0)) { ok = 0; break; }
+            d = sqrt(d);
+            Lm[k * 32 + k] = d;
+            for (int i = k + 1; i < K; ++i) {
+                double t = Lm[i * 32 + k];
+                for (int j = 0; j < k; ++j) t -= Lm[i * 32 + j] * Lm[k * 32 + j];
+                Lm[i * 32 + k] = t / d;
+            }
+        }
+        okf = ok;
+    }
+    __syncthreads();
+    if (!okf) return;   // rank-deficient with an inf y: left as computed (NaN)
+    const int64_t r0 = fx.seg_off[s], r1 = fx.seg_off[s + 1];
+    if constexpr (NC <= 16) {
+        // register arrays (fully unrolled, statically indexed: no scratch, which would throttle
+        // the waves of the solve kernel these fix-ups ride); the opaque zero keeps the factor's
+        // LDS reads inside the row loop instead of hoisted into ~120 live registers
+        for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
+            if (fx.level && (int)fx.level[r] < u) continue;
+            int zo = 0;
+            asm volatile("" : "+v"(zo));
+            double d[NC];
+            double y = 0.0;
+            bool valid = true;
+#pragma unroll
+            for (int q = 1; q <= NC; ++q) {
+                if (q < nz) {
+                    const int c = zi[q] - 1;
+                    double x = fx.cols[(int64_t)c * fx.stride + r];
+                    if (fx.lo) {
+                        const double l = fx.lo[(int64_t)c * fx.nseg + s], h = fx.hi[(int64_t)c * fx.nseg + s];
+                        if (x < l) x = l;
+                        if (x > h) x = h;
+                    }
+                    if (isnan(x)) valid = false;
+                    if (q == nz - 1) {
+                        y = x;
+                    } else {
+                        if (fx.shift) x -= fx.shift[(int64_t)c * fx.nseg + s];
+                        if (fx.inv_scale) x *= fx.inv_scale[(int64_t)c * fx.nseg + s];
+                        d[q - 1] = x - mu[q - 1 + zo];
+                    }
+                }
+            }
+            if (!valid || !isinf(y)) continue;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {          // L w = d
+                if (i < K) {
+                    double t = d[i];
+#pragma unroll
+                    for (int j = 0; j < i; ++j) t -= Lm[i * 32 + j + zo] * d[j];
+                    d[i] = t / Lm[i * 32 + i + zo];
+                }
+            }
+#pragma unroll
+            for (int i = NC - 1; i >= 0; --i) {     // L' c = w
+                if (i < K) {
+                    double t = d[i];
+#pragma unroll
+                    for (int j = i + 1; j < NC; ++j)
+                        if (j < K) t -= Lm[j * 32 + i + zo] * d[j];
+                    d[i] = t / Lm[i * 32 + i + zo];
+                }
+            }
+            double c0 = 1.0 / n;
+#pragma unroll
+            for (int j = 0; j < NC; ++j)
+                if (j < K) c0 -= xb[j + zo] * d[j];
+#pragma unroll
+            for (int j = 0; j <= NC; ++j) {
+                if (j <= K) {
+                    const double term = (j == 0 ? c0 : d[j == 0 ? 0 : j - 1]) * y;
+                    const unsigned b = isnan(term) ? 4u : (term > 0.0 ? 1u : 2u);
+                    atomicOr(&bits[j], b);
+                }
+            }
+        }
+    } else
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
+        if (fx.level && (int)fx.level[r] < u) continue;
+        double v[32];
+        bool valid = true;
+        for (int q = 1; q < nz; ++q) {
+            const int c = zi[q] - 1;
+            double x = fx.cols[(int64_t)c * fx.stride + r];
+            if (fx.lo) {
+                const double l = fx.lo[(int64_t)c * fx.nseg + s], h = fx.hi[(int64_t)c * fx.nseg + s];
+                if (x < l) x = l;
+                if (x > h) x = h;
+            }
+            if (isnan(x)) valid = false;
+            v[q - 1] = x;
+        }
+        if (!valid || !isinf(v[K])) continue;
+        const double y = v[K];
+        double d[32];
+        for (int j = 0; j < K; ++j) {
+            const int c = zi[1 + j] - 1;
+            double x = v[j];
+            if (fx.shift) x -= fx.shift[(int64_t)c * fx.nseg + s];
+            if (fx.inv_scale) x *= fx.inv_scale[(int64_t)c * fx.nseg + s];
+            d[j] = x - mu[j];
+        }
+        for (int i = 0; i < K; ++i) {          // L w = d
+            double t = d[i];
+            for (int j = 0; j < i; ++j) t -= Lm[i * 32 + j] * d[j];
+            d[i] = t / Lm[i * 32 + i];
+        }
+        for (int i = K - 1; i >= 0; --i) {     // L' c = w
+            double t = d[i];
+            for (int j = i + 1; j < K; ++j) t -= Lm[j * 32 + i] * d[j];
+            d[i] = t / Lm[i * 32 + i];
+        }
+        double c0 = 1.0 / n;
+        for (int j = 0; j < K; ++j) c0 -= xb[j] * d[j];
+        for (int j = 0; j <= K; ++j) {
+            const double term = (j == 0 ? c0 : d[j - 1]) * y;
+            const unsigned b = isnan(term) ? 4u : (term > 0.0 ? 1u : 2u);
+            atomicOr(&bits[j], b);
+        }
+    }
+    __syncthreads();
+    const int64_t ro = ((int64_t)s * fx.nprob + p) * (fx.pmax + 2);
+    if (threadIdx.x <= K) {
+        const unsigned b = bits[threadIdx.x];
+        if (b != 0u) {
+            double val = NAN;
+            if (!(b & 4u) && b != 3u) val = (b & 1u) ? INFINITY : -INFINITY;
+            fx.rec[ro + threadIdx.x] = val;
+        }
+    }
+    if (threadIdx.x == 0) fx.rec[ro + fx.pmax] = NAN;
+}
+
+// ---------------------------------------------------------------------------------------
+// Row-level refit of FM_ST_REFIT problems (ill-conditioned or rank-deficient Sxx), so that
+// statsmodels' pinv semantics hold where the normal equations cannot: pinv_extended takes
+// the SVD of the UNCENTERED design X = [1, x_1..x_K] (rcond 1e-15) and returns
+// params = V S^+ U' y (min-norm over [1, X]), rsquared = 1 - SSR / centered TSS.
+//   1. Householder TSQR of [X | y] over the problem's rows (the Gram's row set: universe
+//      level >= u, every model column non-NaN after the clip), each wave absorbing 64-row
+//      tiles into its own triangular factor, the four factors then merged by wave 0.
+//      Backward stable: the factor's error is ~eps * |X|, not eps * |X|^2.
+//   2. One-sided (Hestenes) Jacobi SVD of R_xx, cut at SVD_REL * sigma_max, and
+//      beta = V S^+ U' r_y with r_y = Q'y.  SSR = |r_y - R_xx beta|^2 + rho^2 (rho = y's
+//      diagonal of R), centered TSS = sum_{i >= 1} r_y[i]^2 + rho^2 (column 0 is the
+//      constant, so Q's first column is 1/sqrt(n)).
+// SVD_REL is 1e-13, not statsmodels' 1e-15: an exact dependence (a zero column, x2 = 2 x1,
+// a regressor constant within the month) leaves a singular value at the QR's rounding
+// floor (~N eps sigma_max), which must be cut; genuine near-dependences down to 1e-13 are
+// kept (DESIGN.md §2).
+constexpr double SVD_REL = 1e-13;
+
+__device__ __forceinline__ double wave_sum_dpp(double v) {
+    v += xor_lanes_f64(v, 1);
+    v += xor_lanes_f64(v, 2);
+    v += xor_lanes_f64(v, 4);
+    v += xor_lanes_f64(v, 8);
+    v += xor_lanes_f64(v, 16);
+    v += xor_lanes_f64(v, 32);
+    return v;
+}
+
+template <int NC, int NW = VNW>
+struct RefitSmem {
+    double R[NW][NC][NC + 1];    // per-wave triangular factors of [1, x, y]
+    double Ac[NC][NC + 1];       // Jacobi: rotated columns of R_xx, Ac[j][i] = (R_xx V)[i][j]
+    double Vc[NC][NC + 1];       // Jacobi: V[i][j] at Vc[j][i]
+    double bv[NC];
+};
+
+// Absorb one 64-row tile (lane = row, a[] = its NC values, zero rows allowed) into the
+// wave's triangular factor R: Householder reflections over [R row k; tile column k].
+template <int NC>
+__device__ __forceinline__ void hh_absorb(double (&a)[NC], double (*R)[NC + 1], int nzc) {
+    const int lane = lane_id();
+    static_for<0, NC>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        if (k < nzc) {
+            const double ss = wave_sum_dpp(a[k] * a[k]);
+            if (ss != 0.0) {   // wave-uniform: a zero tile column leaves R as it is
+                const double alpha = R[k][k];
+                const double nrm = sqrt(alpha * alpha + ss);
+                const double beta = alpha > 0.0 ? -nrm : nrm;
+                const double v0 = alpha - beta;
+                const double tau = -v0 / beta;
+                const double vl = a[k] / v0;   // v = (1, a[:,k] / v0)
+                double w[NC];
+                static_for<k + 1, NC>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value;
+                    w[j] = vl * a[j];
+                });
+                static_for<k + 1, NC>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value;
+                    w[j] = wave_sum_dpp(w[j]) + R[k][j];
+                });
+                static_for<k + 1, NC>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value;
+                    a[j] -= (tau * w[j]) * vl;
+                });
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (lane == 0) {
+                    R[k][k] = beta;
+                    static_for<k + 1, NC>([&](auto jc) {
+                        constexpr int j = decltype(jc)::value;
+                        R[k][j] -= tau * w[j];
+                    });
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                a[k] = 0.0;
+            }
+        }
+    });
+}
+
+template <int NC, int NT = VT, class CA = F64Cols>
+__device__ void refit_pair(int s, int p, RefitSmem<NC, NT / WAVE>& sm, const FixCtx<CA>& fx) {
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const int nz = fx.prob_nz[p], P = nz - 1, u = fx.prob_level[p];
+    const int* zi = fx.prob_z + p * 32;
+    constexpr int NW = NT / WAVE;
+    for (int e = tid; e < NW * NC * (NC + 1); e += NT) (&sm.R[0][0][0])[e] = 0.0;
+    __syncthreads();
+    int zc[NC];   // panel column of z index q (q >= 1)
+    static_for<0, NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        zc[q] = (q >= 1 && q < nz) ? zi[q] - 1 : 0;
+    });
+    const int64_t r0 = fx.seg_off[s], r1 = fx.seg_off[s + 1];
+    for (int64_t base = r0 + (int64_t)w * WAVE; base < r1; base += NT) {
+        const int64_t r = base + lane;
+        bool valid = r < r1 && !(fx.level && (int)fx.level[r] < u);
+        double a[NC];
+        static_for<0, NC>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            double v = 0.0;
+            if constexpr (q == 0) {
+                v = 1.0;
+            } else {
+                if (valid && q < nz) {
+                    const int c = zc[q];
+                    double x = fx.cols[(int64_t)c * fx.stride + r];
+                    if (fx.lo) {
+                        const double l = fx.lo[(int64_t)c * fx.nseg + s], h = fx.hi[(int64_t)c * fx.nseg + s];
+                        if (x < l) x = l;
+                        if (x > h) x = h;
+                    }
+                    if (fx.inv_scale) {
+                        x = (x - fx.shift[(int64_t)c * fx.nseg + s]) * fx.inv_scale[(int64_t)c * fx.nseg + s];
+                        if (fx.add_back) x += fx.add_back[(int64_t)c * fx.nseg + s];
+                    }
+                    if (isnan(x)) valid = false;
+                    v = x;
+                }
+            }
+            a[q] = v;
+        });
+        static_for<0, NC>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            if (!valid) a[q] = 0.0;
+        });
+        hh_absorb<NC>(a, sm.R[w], nz);
+    }
+    __syncthreads();
+    if (w == 0) {   // merge the other waves' factors into wave 0's
+        for (int o = 1; o < NW; ++o) {
+            double a[NC];
+            static_for<0, NC>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                a[j] = (lane < NC && j >= lane) ? sm.R[o][lane < NC ? lane : 0][j] : 0.0;
+            });
+            hh_absorb<NC>(a, sm.R[0], nz);
+        }
+        // ---- one-sided Jacobi SVD of R_xx (P x P upper triangular), lane i = row i
+        double (*R)[NC + 1] = sm.R[0];
+        const bool li = lane < P;
+        const int lr = li ? lane : 0;
+        if (li)
+            for (int j = 0; j < P; ++j) {
+                sm.Ac[j][lane] = j >= lane ? R[lane][j] : 0.0;
+                sm.Vc[j][lane] = j == lane ? 1.0 : 0.0;
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int sweep = 0; sweep < 60; ++sweep) {
+            bool rotated = false;
+            for (int pc = 0; pc < P - 1; ++pc) {
+                for (int qc = pc + 1; qc < P; ++qc) {
+                    const double ap = li ? sm.Ac[pc][lr] : 0.0, aq = li ? sm.Ac[qc][lr] : 0.0;
+                    const double al = wave_sum_dpp(ap * ap);
+                    const double be = wave_sum_dpp(aq * aq);
+                    const double ga = wave_sum_dpp(ap * aq);
+                    if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;   // wave-uniform
+                    rotated = true;
+                    const double zeta = (be - al) / (2.0 * ga);
+                    const double t = fabs(zeta) > 1e150
+                                         ? 0.5 / zeta
+                                         : (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
+                    const double vp = li ? sm.Vc[pc][lr] : 0.0, vq = li ? sm.Vc[qc][lr] : 0.0;
+                    if (li) {
+                        sm.Ac[pc][lane] = c * ap - sn * aq;
+                        sm.Ac[qc][lane] = sn * ap + c * aq;
+                        sm.Vc[pc][lane] = c * vp - sn * vq;
+                        sm.Vc[qc][lane] = sn * vp + c * vq;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
+            }
+            if (!rotated) break;
+        }
+        // ---- beta = V S^+ (R_xx V)' r_y; singular values below SVD_REL * sigma_max cut
+        const double ry = li ? R[lane][P] : 0.0;   // Q'y
+        const double rho = R[P][P];
+        double smax = 0.0;
+        for (int j = 0; j < P; ++j) smax = fmax(smax, wave_sum_dpp(li ? sm.Ac[j][lr] * sm.Ac[j][lr] : 0.0));
+        smax = sqrt(smax);
+        double bi = 0.0;
+        bool cut = false;
+        for (int j = 0; j < P; ++j) {
+            const double aj = li ? sm.Ac[j][lr] : 0.0;
+            const double s2 = wave_sum_dpp(aj * aj);
+            if (!(sqrt(s2) > SVD_REL * smax)) {
+                cut = true;
+                continue;
+            }
+            const double cj = wave_sum_dpp(aj * ry) / s2;
+            if (li) bi += sm.Vc[j][lane] * cj;
+        }
+        if (li) sm.bv[lane] = bi;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        double fit = 0.0;
+        if (li)
+            for (int j = lane; j < P; ++j) fit += R[lane][j] * sm.bv[j];
+        const double e = li ? ry - fit : 0.0;
+        const double ssr = wave_sum_dpp(e * e) + rho * rho;
+        const double tss = wave_sum_dpp((li && lane >= 1) ? ry * ry : 0.0) + rho * rho;
+        const int64_t ro = ((int64_t)s * fx.nprob + p) * (fx.pmax + 2);
+        if (li) fx.rec[ro + lane] = bi;
+        if (lane == 0) {
+            fx.rec[ro + fx.pmax] = 1.0 - ssr / tss;
+            const uint32_t st = fx.status[(int64_t)s * fx.nprob + p];
+            fx.status[(int64_t)s * fx.nprob + p] = (st & ~FM_ST_RANK_DEF) | (cut ? FM_ST_RANK_DEF : 0u);
+        }
+    }
+}
+
+// statsmodels fix-ups after fm_solve, one workgroup per flagged (month, problem):
+// CONST_SUSPECT (with check_const) -> const_pair; FITTED|INF_IN_Y -> infy_pair;
+// FITTED|REFIT (no inf) -> refit_pair.
+template <int NC, int NT>
+union FixSmem {
+    InfySmem infy;
+    RefitSmem<NC, NT / WAVE> refit;
+    uint64_t red[NT / WAVE];
+};
+inline __device__ bool fix_wanted(uint32_t st, int check_const) {
+    return (check_const && (st & FM_ST_CONST_SUSPECT)) ||
+           ((st & FM_ST_FITTED) && (st & (FM_ST_INF_IN_Y | FM_ST_REFIT)));
+}
+// The fix-ups of one flagged (month, problem) whose solve status is `st`, by the whole
+// NT-thread workgroup (block-uniform; ends with the workgroup synchronized)
+template <int NC, int NT, class CA>
+__device__ __forceinline__ void fix_one(int s, int p, uint32_t st, FixSmem<NC, NT>& sm, const FixCtx<CA>& fx) {
+    if (fx.check_const && (st & FM_ST_CONST_SUSPECT)) {
+        const_pair<NT>(s, p, sm.red, fx);
+        __syncthreads();
+    }
+    if (!(st & FM_ST_FITTED)) return;
+    if (st & FM_ST_INF_IN_Y) {
+        infy_pair<NT, NC>(s, p, sm.infy, fx);
+    } else if ((st & FM_ST_REFIT) && !(st & FM_ST_INF_IN_X) && fx.prob_nz[p] <= NC) {
+        refit_pair<NC, NT>(s, p, sm.refit, fx);
+    } else {
+        return;
+    }
+    __syncthreads();   // sm is reused by the next pair
+}
+
+// ---------------------------------------------------------------------------------------
 // zw == 16 (<= 15 panel columns): four problems per wave.  A problem owns one 16-lane row of
 // the wave and lane i holds row i of its Gram (row 0 = the intercept, rows 1..K+1 = the
 // centered moments S of x_1..x_K, y), so the pivot-row broadcasts of the Cholesky are DPP
@@ -389,17 +872,6 @@ __device__ __forceinline__ double rowsum(double v) { return row16_sum(v); }
 
 constexpr int G16 = 16;   // lanes per problem
 
-template <int NC, int NT>
-union FixSmem;
-inline __device__ bool fix_wanted(uint32_t st, int check_const);
-template <int NC, int NT, class CA>
-__device__ __forceinline__ void fix_one(int s, int p, uint32_t st, FixSmem<NC, NT>& sm, CA cols, int64_t stride,
-                        const int64_t* seg_off, int nseg, const double* lo, const double* hi,
-                        const double* shift, const double* inv_scale, const double* add_back,
-                        const uint8_t* level, int nprob, const int32_t* prob_level, const int32_t* prob_z,
-                        const int32_t* prob_nz, const double* moments, int mom_stride, int pmax, double* rec,
-                        uint32_t* status, int check_const);
-
 // 192 threads (three waves, twelve problems at a time: a Table-2 month's 11 problems in ONE
 // round, so no wave factors twice) at two waves per SIMD: 256 VGPRs (the factorization's
 // register rows and columns fit without spills); every month of a 600-month panel is
@@ -414,6 +886,7 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
     constexpr int TT = G16 * (G16 + 1);
     static_assert(sizeof(WaveScratch<16>) <= 4 * TT * sizeof(double), "scratch union");
     __shared__ double wsc[S16W][4 * TT];
+    static_assert(sizeof(FixSmem<G16, S16T>) <= sizeof(wsc), "solve16's inline fix-ups reuse its per-wave scratch");
     const int s = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
@@ -690,557 +1163,53 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
     // instantiation per layout (a per-access branch raised the kernel to 231 VGPRs)
     auto fix_all = [&](auto cols) {
         __syncthreads();
-        const int ckc = a.fix_check_const;
+        FixCtx<decltype(cols)> fx{};
+        fx.check_const = a.fix_check_const;
+        fx.cols = cols, fx.stride = a.fix_stride, fx.seg_off = a.fix_seg_off, fx.nseg = a.nseg;
+        fx.lo = a.fix_lo, fx.hi = a.fix_hi;
+        fx.shift = a.fix_shift, fx.inv_scale = a.fix_inv_scale, fx.add_back = a.add_back;
+        fx.level = a.fix_level;
+        fx.nprob = a.nprob, fx.prob_level = a.prob_level, fx.prob_z = a.prob_z, fx.prob_nz = a.prob_nz;
+        fx.moments = a.moments, fx.mom_stride = a.mom_stride;
+        fx.pmax = a.pmax, fx.rec = a.rec, fx.status = a.status;
         for (int q = 0; q < a.nprob; ++q) {
             const uint32_t st = t_st[q];
-            if (!fix_wanted(st, ckc)) continue;   // block-uniform
-            fix_one<G16, S16T>(s, q, st, *reinterpret_cast<FixSmem<G16, S16T>*>(&wsc[0][0]), cols,
-                               a.fix_stride, a.fix_seg_off, a.nseg, a.fix_lo, a.fix_hi, a.fix_shift,
-                               a.fix_inv_scale, a.add_back, a.fix_level, a.nprob, a.prob_level, a.prob_z,
-                               a.prob_nz, a.moments, a.mom_stride, a.pmax, a.rec, a.status, ckc);
+            if (!fix_wanted(st, fx.check_const)) continue;   // block-uniform
+            fix_one<G16, S16T>(s, q, st, *reinterpret_cast<FixSmem<G16, S16T>*>(&wsc[0][0]), fx);
         }
     };
     if (a.fix_cols != nullptr) fix_all(F64Cols{a.fix_cols});   // block-uniform
     else if (a.fix_hi_plane != nullptr) fix_all(PlaneCols{a.fix_hi_plane, (int64_t)(a.fix_lo_plane - a.fix_hi_plane)});
 }
 
-// Exact nonzero-constant test for problems flagged CONST_SUSPECT (statsmodels
-// add_constant(has_constant='skip'): np.ptp(x)==0 & all(x != 0), src/regressions.py:50).
-template <int NT = VT, class CA = F64Cols>
-__device__ __forceinline__ void const_pair(int s, int p, uint64_t* red, CA cols, int64_t stride,
-                                           const int64_t* seg_off, int nseg, const double* lo,
-                                           const double* hi, const uint8_t* level, int nprob,
-                                           const int32_t* prob_level, const int32_t* prob_z,
-                                           const int32_t* prob_nz, uint32_t* status) {
-    const int nz = prob_nz[p], K = nz - 2, u = prob_level[p];
-    const int* zi = prob_z + p * 32;
-    const int64_t r0 = seg_off[s], r1 = seg_off[s + 1];
-    bool any_const = false;
-    for (int j = 0; j < K; ++j) {
-        const int cx = zi[1 + j] - 1;
-        uint64_t kmin = SENT, kmax = 0;
-        bool allnz = true;
-        for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
-            if (level && (int)level[r] < u) continue;
-            bool ok = true;
-            double xv = 0.0;
-            for (int q = 1; q < nz; ++q) {
-                const int c = zi[q] - 1;
-                double x = cols[(int64_t)c * stride + r];
-                if (lo) {
-                    const double l = lo[(int64_t)c * nseg + s], h = hi[(int64_t)c * nseg + s];
-                    if (x < l) x = l;
-                    if (x > h) x = h;
-                }
-                if (isnan(x)) ok = false;
-                if (c == cx) xv = x;
-            }
-            if (!ok) continue;
-            const uint64_t k = dkey(xv == 0.0 ? 0.0 : xv);
-            kmin = k < kmin ? k : kmin;
-            kmax = k > kmax ? k : kmax;
-            if (xv == 0.0) allnz = false;
-        }
-        kmin = block_min_u64<NT / WAVE>(kmin, red);
-        kmax = block_max_u64<NT / WAVE>(kmax, red);
-        const int nzr = block_sum<NT / WAVE>(allnz ? 0 : 1, (int*)red);
-        if (kmin != SENT && kmin == kmax && nzr == 0) any_const = true;
-    }
-    if (threadIdx.x == 0 && any_const) status[(int64_t)s * nprob + p] |= FM_ST_CONST_COL;
-}
-
-__global__ __launch_bounds__(VT) void const_kernel(F64Cols cols, int64_t stride, int ncols,
-                                                   const int64_t* seg_off, int nseg,
-                                                   const double* lo, const double* hi,
-                                                   const uint8_t* level, int nprob,
-                                                   const int32_t* prob_level, const int32_t* prob_z,
-                                                   const int32_t* prob_nz, const int32_t* pairs,
-                                                   int npairs, uint32_t* status) {
+__global__ __launch_bounds__(VT) void const_kernel(FixCtx<F64Cols> fx, const int32_t* pairs, int npairs) {
     __shared__ uint64_t red[VNW];
     // npairs < 0: scan every (month, problem) and take those the solve flagged, so the
     // check needs no host round trip; else the listed pairs.
-    const int total = npairs < 0 ? nseg * nprob : npairs;
+    const int total = npairs < 0 ? fx.nseg * fx.nprob : npairs;
     for (int e = blockIdx.x; e < total; e += gridDim.x) {
         int s, p;
         if (npairs < 0) {
-            s = e / nprob;
-            p = e - s * nprob;
-            if (!(status[e] & FM_ST_CONST_SUSPECT)) continue;
+            s = e / fx.nprob;
+            p = e - s * fx.nprob;
+            if (!(fx.status[e] & FM_ST_CONST_SUSPECT)) continue;
         } else {
             s = pairs[2 * e];
             p = pairs[2 * e + 1];
         }
-        const_pair(s, p, red, cols, stride, seg_off, nseg, lo, hi, level, nprob, prob_level, prob_z,
-                   prob_nz, status);
+        const_pair(s, p, red, fx);
     }
-}
-
-// inf in y (statsmodels keeps the month): params = pinv(X) @ y, so each coefficient is the
-// IEEE sum of pinv[j,i] * y_i; with y_i = +-inf the finite rows do not matter and the
-// result is +inf, -inf or NaN (mixed signs, or 0*inf).  pinv[:,i] for the slopes is
-// Sxx^{-1}(x_i - xbar) and for the intercept 1/n - xbar'Sxx^{-1}(x_i - xbar).  One
-// workgroup per flagged (month, problem); R^2 becomes NaN as in statsmodels.
-struct InfySmem {
-    double Lm[32 * 32];
-    double mu[32], xb[32];
-    unsigned bits[32];
-    int okf;
-};
-
-template <int NT = VT, int NC = 32, class CA = F64Cols>
-__device__ __forceinline__ void infy_pair(int s, int p, InfySmem& sm, CA cols, int64_t stride,
-                                          const int64_t* seg_off, int nseg, const double* lo,
-                                          const double* hi, const double* shift,
-                                          const double* inv_scale, const double* add_back,
-                                          const uint8_t* level, int nprob,
-                                          const int32_t* prob_level, const int32_t* prob_z,
-                                          const int32_t* prob_nz, const double* moments,
-                                          int mom_stride, int pmax, double* rec) {
-    double* Lm = sm.Lm;
-    double* mu = sm.mu;
-    double* xb = sm.xb;
-    unsigned* bits = sm.bits;
-    int& okf = sm.okf;
-    const int nz = prob_nz[p], K = nz - 2, K1 = K + 1, u = prob_level[p];
-    const int* zi = prob_z + p * 32;
-    const double* mo = moments + ((int64_t)s * nprob + p) * mom_stride;
-    const double n = mo[0];
-    for (int e = threadIdx.x; e < K * K; e += NT) Lm[(e / K) * 32 + e % K] = mo[1 + K1 + (e / K) * K1 + e % K];
-    if (threadIdx.x < K1) mu[threadIdx.x] = mo[1 + threadIdx.x];
-    if (threadIdx.x < 32) bits[threadIdx.x] = 0u;
-    __syncthreads();
-    if (threadIdx.x < K) {
-        const int c = zi[1 + threadIdx.x] - 1;
-        xb[threadIdx.x] = mu[threadIdx.x] + (add_back ? add_back[(int64_t)c * nseg + s] : 0.0);
-    }
-    if (threadIdx.x == 0) {
-        int ok = 1;
-        for (int k = 0; k < K && ok; ++k) {
-            double d = Lm[k * 32 + k];
-            for (int j = 0; j < k; ++j) d -= Lm[k * 32 + j] * Lm[k * 32 + j];
-            if (!(d > 0.0)) { ok = 0; break; }
-            d = sqrt(d);
-            Lm[k * 32 + k] = d;
-            for (int i = k + 1; i < K; ++i) {
-                double t = Lm[i * 32 + k];
-                for (int j = 0; j < k; ++j) t -= Lm[i * 32 + j] * Lm[k * 32 + j];
-                Lm[i * 32 + k] = t / d;
-            }
-        }
-        okf = ok;
-    }
-    __syncthreads();
-    if (!okf) return;   // rank-deficient with an inf y: left as computed (NaN)
-    const int64_t r0 = seg_off[s], r1 = seg_off[s + 1];
-    if constexpr (NC <= 16) {
-        // register arrays (fully unrolled, statically indexed: no scratch, which would throttle
-        // the waves of the solve kernel these fix-ups ride); the opaque zero keeps the factor's
-        // LDS reads inside the row loop instead of hoisted into ~120 live registers
-        for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
-            if (level && (int)level[r] < u) continue;
-            int zo = 0;
-            asm volatile("" : "+v"(zo));
-            double d[NC];
-            double y = 0.0;
-            bool valid = true;
-#pragma unroll
-            for (int q = 1; q <= NC; ++q) {
-                if (q < nz) {
-                    const int c = zi[q] - 1;
-                    double x = cols[(int64_t)c * stride + r];
-                    if (lo) {
-                        const double l = lo[(int64_t)c * nseg + s], h = hi[(int64_t)c * nseg + s];
-                        if (x < l) x = l;
-                        if (x > h) x = h;
-                    }
-                    if (isnan(x)) valid = false;
-                    if (q == nz - 1) {
-                        y = x;
-                    } else {
-                        if (shift) x -= shift[(int64_t)c * nseg + s];
-                        if (inv_scale) x *= inv_scale[(int64_t)c * nseg + s];
-                        d[q - 1] = x - mu[q - 1 + zo];
-                    }
-                }
-            }
-            if (!valid || !isinf(y)) continue;
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {          // L w = d
-                if (i < K) {
-                    double t = d[i];
-#pragma unroll
-                    for (int j = 0; j < i; ++j) t -= Lm[i * 32 + j + zo] * d[j];
-                    d[i] = t / Lm[i * 32 + i + zo];
-                }
-            }
-#pragma unroll
-            for (int i = NC - 1; i >= 0; --i) {     // L' c = w
-                if (i < K) {
-                    double t = d[i];
-#pragma unroll
-                    for (int j = i + 1; j < NC; ++j)
-                        if (j < K) t -= Lm[j * 32 + i + zo] * d[j];
-                    d[i] = t / Lm[i * 32 + i + zo];
-                }
-            }
-            double c0 = 1.0 / n;
-#pragma unroll
-            for (int j = 0; j < NC; ++j)
-                if (j < K) c0 -= xb[j + zo] * d[j];
-#pragma unroll
-            for (int j = 0; j <= NC; ++j) {
-                if (j <= K) {
-                    const double term = (j == 0 ? c0 : d[j == 0 ? 0 : j - 1]) * y;
-                    const unsigned b = isnan(term) ? 4u : (term > 0.0 ? 1u : 2u);
-                    atomicOr(&bits[j], b);
-                }
-            }
-        }
-    } else
-    for (int64_t r = r0 + threadIdx.x; r < r1; r += NT) {
-        if (level && (int)level[r] < u) continue;
-        double v[32];
-        bool valid = true;
-        for (int q = 1; q < nz; ++q) {
-            const int c = zi[q] - 1;
-            double x = cols[(int64_t)c * stride + r];
-            if (lo) {
-                const double l = lo[(int64_t)c * nseg + s], h = hi[(int64_t)c * nseg + s];
-                if (x < l) x = l;
-                if (x > h) x = h;
-            }
-            if (isnan(x)) valid = false;
-            v[q - 1] = x;
-        }
-        if (!valid || !isinf(v[K])) continue;
-        const double y = v[K];
-        double d[32];
-        for (int j = 0; j < K; ++j) {
-            const int c = zi[1 + j] - 1;
-            double x = v[j];
-            if (shift) x -= shift[(int64_t)c * nseg + s];
-            if (inv_scale) x *= inv_scale[(int64_t)c * nseg + s];
-            d[j] = x - mu[j];
-        }
-        for (int i = 0; i < K; ++i) {          // L w = d
-            double t = d[i];
-            for (int j = 0; j < i; ++j) t -= Lm[i * 32 + j] * d[j];
-            d[i] = t / Lm[i * 32 + i];
-        }
-        for (int i = K - 1; i >= 0; --i) {     // L' c = w
-            double t = d[i];
-            for (int j = i + 1; j < K; ++j) t -= Lm[j * 32 + i] * d[j];
-            d[i] = t / Lm[i * 32 + i];
-        }
-        double c0 = 1.0 / n;
-        for (int j = 0; j < K; ++j) c0 -= xb[j] * d[j];
-        for (int j = 0; j <= K; ++j) {
-            const double term = (j == 0 ? c0 : d[j - 1]) * y;
-            const unsigned b = isnan(term) ? 4u : (term > 0.0 ? 1u : 2u);
-            atomicOr(&bits[j], b);
-        }
-    }
-    __syncthreads();
-    const int64_t ro = ((int64_t)s * nprob + p) * (pmax + 2);
-    if (threadIdx.x <= K) {
-        const unsigned b = bits[threadIdx.x];
-        if (b != 0u) {
-            double val = NAN;
-            if (!(b & 4u) && b != 3u) val = (b & 1u) ? INFINITY : -INFINITY;
-            rec[ro + threadIdx.x] = val;
-        }
-    }
-    if (threadIdx.x == 0) rec[ro + pmax] = NAN;
-}
-
-// ---------------------------------------------------------------------------------------
-// Row-level refit of FM_ST_REFIT problems (ill-conditioned or rank-deficient Sxx), so that
-// statsmodels' pinv semantics hold where the normal equations cannot: pinv_extended takes
-// the SVD of the UNCENTERED design X = [1, x_1..x_K] (rcond 1e-15) and returns
-// params = V S^+ U' y (min-norm over [1, X]), rsquared = 1 - SSR / centered TSS.
-//   1. Householder TSQR of [X | y] over the problem's rows (the Gram's row set: universe
-//      level >= u, every model column non-NaN after the clip), each wave absorbing 64-row
-//      tiles into its own triangular factor, the four factors then merged by wave 0.
-//      Backward stable: the factor's error is ~eps * |X|, not eps * |X|^2.
-//   2. One-sided (Hestenes) Jacobi SVD of R_xx, cut at SVD_REL * sigma_max, and
-//      beta = V S^+ U' r_y with r_y = Q'y.  SSR = |r_y - R_xx beta|^2 + rho^2 (rho = y's
-//      diagonal of R), centered TSS = sum_{i >= 1} r_y[i]^2 + rho^2 (column 0 is the
-//      constant, so Q's first column is 1/sqrt(n)).
-// SVD_REL is 1e-13, not statsmodels' 1e-15: an exact dependence (a zero column, x2 = 2 x1,
-// a regressor constant within the month) leaves a singular value at the QR's rounding
-// floor (~N eps sigma_max), which must be cut; genuine near-dependences down to 1e-13 are
-// kept (DESIGN.md §2).
-constexpr double SVD_REL = 1e-13;
-
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-    v += xor_lanes_f64(v, 1);
-    v += xor_lanes_f64(v, 2);
-    v += xor_lanes_f64(v, 4);
-    v += xor_lanes_f64(v, 8);
-    v += xor_lanes_f64(v, 16);
-    v += xor_lanes_f64(v, 32);
-    return v;
-}
-
-template <int NC, int NW = VNW>
-struct RefitSmem {
-    double R[NW][NC][NC + 1];    // per-wave triangular factors of [1, x, y]
-    double Ac[NC][NC + 1];       // Jacobi: rotated columns of R_xx, Ac[j][i] = (R_xx V)[i][j]
-    double Vc[NC][NC + 1];       // Jacobi: V[i][j] at Vc[j][i]
-    double bv[NC];
-};
-
-// Absorb one 64-row tile (lane = row, a[] = its NC values, zero rows allowed) into the
-// wave's triangular factor R: Householder reflections over [R row k; tile column k].
-template <int NC>
-__device__ __forceinline__ void hh_absorb(double (&a)[NC], double (*R)[NC + 1], int nzc) {
-    const int lane = lane_id();
-    static_for<0, NC>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        if (k < nzc) {
-            const double ss = wave_sum_dpp(a[k] * a[k]);
-            if (ss != 0.0) {   // wave-uniform: a zero tile column leaves R as it is
-                const double alpha = R[k][k];
-                const double nrm = sqrt(alpha * alpha + ss);
-                const double beta = alpha > 0.0 ? -nrm : nrm;
-                const double v0 = alpha - beta;
-                const double tau = -v0 / beta;
-                const double vl = a[k] / v0;   // v = (1, a[:,k] / v0)
-                double w[NC];
-                static_for<k + 1, NC>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value;
-                    w[j] = vl * a[j];
-                });
-                static_for<k + 1, NC>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value;
-                    w[j] = wave_sum_dpp(w[j]) + R[k][j];
-                });
-                static_for<k + 1, NC>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value;
-                    a[j] -= (tau * w[j]) * vl;
-                });
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (lane == 0) {
-                    R[k][k] = beta;
-                    static_for<k + 1, NC>([&](auto jc) {
-                        constexpr int j = decltype(jc)::value;
-                        R[k][j] -= tau * w[j];
-                    });
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                a[k] = 0.0;
-            }
-        }
-    });
-}
-
-template <int NC, int NT = VT, class CA = F64Cols>
-__device__ void refit_pair(int s, int p, RefitSmem<NC, NT / WAVE>& sm, CA cols, int64_t stride,
-                           const int64_t* seg_off, int nseg, const double* lo, const double* hi,
-                           const double* shift, const double* inv_scale, const double* add_back,
-                           const uint8_t* level, int nprob, const int32_t* prob_level,
-                           const int32_t* prob_z, const int32_t* prob_nz, int pmax, double* rec,
-                           uint32_t* status) {
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
-    const int nz = prob_nz[p], P = nz - 1, u = prob_level[p];
-    const int* zi = prob_z + p * 32;
-    constexpr int NW = NT / WAVE;
-    for (int e = tid; e < NW * NC * (NC + 1); e += NT) (&sm.R[0][0][0])[e] = 0.0;
-    __syncthreads();
-    int zc[NC];   // panel column of z index q (q >= 1)
-    static_for<0, NC>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        zc[q] = (q >= 1 && q < nz) ? zi[q] - 1 : 0;
-    });
-    const int64_t r0 = seg_off[s], r1 = seg_off[s + 1];
-    for (int64_t base = r0 + (int64_t)w * WAVE; base < r1; base += NT) {
-        const int64_t r = base + lane;
-        bool valid = r < r1 && !(level && (int)level[r] < u);
-        double a[NC];
-        static_for<0, NC>([&](auto qc) {
-            constexpr int q = decltype(qc)::value;
-            double v = 0.0;
-            if constexpr (q == 0) {
-                v = 1.0;
-            } else {
-                if (valid && q < nz) {
-                    const int c = zc[q];
-                    double x = cols[(int64_t)c * stride + r];
-                    if (lo) {
-                        const double l = lo[(int64_t)c * nseg + s], h = hi[(int64_t)c * nseg + s];
-                        if (x < l) x = l;
-                        if (x > h) x = h;
-                    }
-                    if (inv_scale) {
-                        x = (x - shift[(int64_t)c * nseg + s]) * inv_scale[(int64_t)c * nseg + s];
-                        if (add_back) x += add_back[(int64_t)c * nseg + s];
-                    }
-                    if (isnan(x)) valid = false;
-                    v = x;
-                }
-            }
-            a[q] = v;
-        });
-        static_for<0, NC>([&](auto qc) {
-            constexpr int q = decltype(qc)::value;
-            if (!valid) a[q] = 0.0;
-        });
-        hh_absorb<NC>(a, sm.R[w], nz);
-    }
-    __syncthreads();
-    if (w == 0) {   // merge the other waves' factors into wave 0's
-        for (int o = 1; o < NW; ++o) {
-            double a[NC];
-            static_for<0, NC>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                a[j] = (lane < NC && j >= lane) ? sm.R[o][lane < NC ? lane : 0][j] : 0.0;
-            });
-            hh_absorb<NC>(a, sm.R[0], nz);
-        }
-        // ---- one-sided Jacobi SVD of R_xx (P x P upper triangular), lane i = row i
-        double (*R)[NC + 1] = sm.R[0];
-        const bool li = lane < P;
-        const int lr = li ? lane : 0;
-        if (li)
-            for (int j = 0; j < P; ++j) {
-                sm.Ac[j][lane] = j >= lane ? R[lane][j] : 0.0;
-                sm.Vc[j][lane] = j == lane ? 1.0 : 0.0;
-            }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int sweep = 0; sweep < 60; ++sweep) {
-            bool rotated = false;
-            for (int pc = 0; pc < P - 1; ++pc) {
-                for (int qc = pc + 1; qc < P; ++qc) {
-                    const double ap = li ? sm.Ac[pc][lr] : 0.0, aq = li ? sm.Ac[qc][lr] : 0.0;
-                    const double al = wave_sum_dpp(ap * ap);
-                    const double be = wave_sum_dpp(aq * aq);
-                    const double ga = wave_sum_dpp(ap * aq);
-                    if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;   // wave-uniform
-                    rotated = true;
-                    const double zeta = (be - al) / (2.0 * ga);
-                    const double t = fabs(zeta) > 1e150
-                                         ? 0.5 / zeta
-                                         : (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                    const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-                    const double vp = li ? sm.Vc[pc][lr] : 0.0, vq = li ? sm.Vc[qc][lr] : 0.0;
-                    if (li) {
-                        sm.Ac[pc][lane] = c * ap - sn * aq;
-                        sm.Ac[qc][lane] = sn * ap + c * aq;
-                        sm.Vc[pc][lane] = c * vp - sn * vq;
-                        sm.Vc[qc][lane] = sn * vp + c * vq;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                }
-            }
-            if (!rotated) break;
-        }
-        // ---- beta = V S^+ (R_xx V)' r_y; singular values below SVD_REL * sigma_max cut
-        const double ry = li ? R[lane][P] : 0.0;   // Q'y
-        const double rho = R[P][P];
-        double smax = 0.0;
-        for (int j = 0; j < P; ++j) smax = fmax(smax, wave_sum_dpp(li ? sm.Ac[j][lr] * sm.Ac[j][lr] : 0.0));
-        smax = sqrt(smax);
-        double bi = 0.0;
-        bool cut = false;
-        for (int j = 0; j < P; ++j) {
-            const double aj = li ? sm.Ac[j][lr] : 0.0;
-            const double s2 = wave_sum_dpp(aj * aj);
-            if (!(sqrt(s2) > SVD_REL * smax)) {
-                cut = true;
-                continue;
-            }
-            const double cj = wave_sum_dpp(aj * ry) / s2;
-            if (li) bi += sm.Vc[j][lane] * cj;
-        }
-        if (li) sm.bv[lane] = bi;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double fit = 0.0;
-        if (li)
-            for (int j = lane; j < P; ++j) fit += R[lane][j] * sm.bv[j];
-        const double e = li ? ry - fit : 0.0;
-        const double ssr = wave_sum_dpp(e * e) + rho * rho;
-        const double tss = wave_sum_dpp((li && lane >= 1) ? ry * ry : 0.0) + rho * rho;
-        const int64_t ro = ((int64_t)s * nprob + p) * (pmax + 2);
-        if (li) rec[ro + lane] = bi;
-        if (lane == 0) {
-            rec[ro + pmax] = 1.0 - ssr / tss;
-            const uint32_t st = status[(int64_t)s * nprob + p];
-            status[(int64_t)s * nprob + p] = (st & ~FM_ST_RANK_DEF) | (cut ? FM_ST_RANK_DEF : 0u);
-        }
-    }
-}
-
-// statsmodels fix-ups after fm_solve, one workgroup per flagged (month, problem):
-// CONST_SUSPECT (with check_const) -> const_pair; FITTED|INF_IN_Y -> infy_pair;
-// FITTED|REFIT (no inf) -> refit_pair.
-template <int NC, int NT>
-union FixSmem {
-    InfySmem infy;
-    RefitSmem<NC, NT / WAVE> refit;
-    uint64_t red[NT / WAVE];
-};
-static_assert(sizeof(FixSmem<G16, S16T>) <= sizeof(double) * S16W * 4 * G16 * (G16 + 1),
-              "solve16's inline fix-ups reuse its per-wave scratch");
-inline __device__ bool fix_wanted(uint32_t st, int check_const) {
-    return (check_const && (st & FM_ST_CONST_SUSPECT)) ||
-           ((st & FM_ST_FITTED) && (st & (FM_ST_INF_IN_Y | FM_ST_REFIT)));
-}
-// The fix-ups of one flagged (month, problem) whose solve status is `st`, by the whole
-// NT-thread workgroup (block-uniform; ends with the workgroup synchronized)
-template <int NC, int NT, class CA>
-__device__ __forceinline__ void fix_one(int s, int p, uint32_t st, FixSmem<NC, NT>& sm, CA cols,
-                                        int64_t stride, const int64_t* seg_off, int nseg, const double* lo,
-                                        const double* hi, const double* shift, const double* inv_scale,
-                                        const double* add_back, const uint8_t* level, int nprob,
-                                        const int32_t* prob_level, const int32_t* prob_z,
-                                        const int32_t* prob_nz, const double* moments, int mom_stride,
-                                        int pmax, double* rec, uint32_t* status, int check_const) {
-    if (check_const && (st & FM_ST_CONST_SUSPECT)) {
-        const_pair<NT>(s, p, sm.red, cols, stride, seg_off, nseg, lo, hi, level, nprob, prob_level, prob_z,
-                       prob_nz, status);
-        __syncthreads();
-    }
-    if (!(st & FM_ST_FITTED)) return;
-    if (st & FM_ST_INF_IN_Y) {
-        infy_pair<NT, NC>(s, p, sm.infy, cols, stride, seg_off, nseg, lo, hi, shift, inv_scale, add_back, level,
-                      nprob, prob_level, prob_z, prob_nz, moments, mom_stride, pmax, rec);
-    } else if ((st & FM_ST_REFIT) && !(st & FM_ST_INF_IN_X) && prob_nz[p] <= NC) {
-        refit_pair<NC, NT>(s, p, sm.refit, cols, stride, seg_off, nseg, lo, hi, shift, inv_scale, add_back,
-                           level, nprob, prob_level, prob_z, prob_nz, pmax, rec, status);
-    } else {
-        return;
-    }
-    __syncthreads();   // sm is reused by the next pair
 }
 
 template <int NC>
-__global__ __launch_bounds__(VT) void fixup_kernel(F64Cols cols, int64_t stride,
-                                                   const int64_t* seg_off, int nseg, const double* lo,
-                                                   const double* hi, const double* shift,
-                                                   const double* inv_scale, const double* add_back,
-                                                   const uint8_t* level, int nprob,
-                                                   const int32_t* prob_level, const int32_t* prob_z,
-                                                   const int32_t* prob_nz, const int32_t* pairs,
-                                                   int npairs, const double* moments, int mom_stride,
-                                                   int pmax, double* rec, uint32_t* status,
-                                                   int check_const) {
+__global__ __launch_bounds__(VT) void fixup_kernel(FixCtx<F64Cols> fx, const int32_t* pairs, int npairs) {
     __shared__ FixSmem<NC, VT> sm;
     // npairs < 0: scan every (month, problem) for the flags (no host round trip).  Each
     // workgroup reads VT status words at once and lists the flagged pairs in LDS (a
     // pair-by-pair scan would wait out one memory round trip per pair), then fixes them.
     __shared__ int flagged[VT];
     __shared__ int nflag;
-    const int total = npairs < 0 ? nseg * nprob : npairs;
+    const int total = npairs < 0 ? fx.nseg * fx.nprob : npairs;
     const int tid = threadIdx.x;
     FM_PROBE_AT(solve, 4);
     for (int base = blockIdx.x * VT; base < total; base += gridDim.x * VT) {
@@ -1251,24 +1220,22 @@ __global__ __launch_bounds__(VT) void fixup_kernel(F64Cols cols, int64_t stride,
             if (e < total) {
                 int s, p;
                 if (npairs < 0) {
-                    s = e / nprob;
-                    p = e - s * nprob;
+                    s = e / fx.nprob;
+                    p = e - s * fx.nprob;
                 } else {
                     s = pairs[2 * e];
                     p = pairs[2 * e + 1];
                 }
-                if (fix_wanted(status[(int64_t)s * nprob + p], check_const))
-                    flagged[atomicAdd(&nflag, 1)] = s * nprob + p;
+                if (fix_wanted(fx.status[(int64_t)s * fx.nprob + p], fx.check_const))
+                    flagged[atomicAdd(&nflag, 1)] = s * fx.nprob + p;
             }
         }
         __syncthreads();
         const int nf = nflag;
         for (int f = 0; f < nf; ++f) {
             const int sp = flagged[f];
-            const int s = sp / nprob, p = sp - s * nprob;
-            fix_one<NC, VT>(s, p, status[(int64_t)s * nprob + p], sm, cols, stride, seg_off, nseg, lo, hi, shift,
-                            inv_scale, add_back, level, nprob, prob_level, prob_z, prob_nz, moments, mom_stride,
-                            pmax, rec, status, check_const);
+            const int s = sp / fx.nprob, p = sp - s * fx.nprob;
+            fix_one<NC, VT>(s, p, fx.status[(int64_t)s * fx.nprob + p], sm, fx);
         }
         __syncthreads();   // the list is rebuilt for the next range
     }
@@ -1331,9 +1298,13 @@ extern "C" int fm_const_check(const double* cols, int64_t col_stride, int32_t nc
     const int64_t work = npairs < 0 ? (int64_t)nseg * nprob : npairs;
     if (work == 0) return FM_OK;
     const int grid = (int)(npairs < 0 ? (work < SCAN_GRID ? work : SCAN_GRID) : work);
-    hipLaunchKernelGGL(const_kernel, dim3(grid), dim3(VT), 0, (hipStream_t)stream, F64Cols{cols},
-                       col_stride, ncols, seg_off, nseg, lo, hi, level, nprob, prob_level, prob_z,
-                       prob_nz, pairs, npairs, status);
+    (void)ncols;            // the problems' z indices name the columns
+    FixCtx<F64Cols> fx{};   // what const_pair does not read stays zero
+    fx.cols = F64Cols{cols}, fx.stride = col_stride, fx.seg_off = seg_off, fx.nseg = nseg;
+    fx.lo = lo, fx.hi = hi, fx.level = level;
+    fx.nprob = nprob, fx.prob_level = prob_level, fx.prob_z = prob_z, fx.prob_nz = prob_nz;
+    fx.status = status;
+    hipLaunchKernelGGL(const_kernel, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx, pairs, npairs);
     FM_CHECK_LAUNCH("fm_const_check");
     return FM_OK;
 }
@@ -1355,14 +1326,17 @@ extern "C" int fm_solve_fixup(const double* cols, int64_t col_stride, const int6
     if (work == 0) return FM_OK;
     const int64_t ranges = (work + VT - 1) / VT;   // VT pairs per workgroup pass
     const int grid = (int)(ranges < SCAN_GRID ? ranges : SCAN_GRID);
+    FixCtx<F64Cols> fx{};
+    fx.cols = F64Cols{cols}, fx.stride = col_stride, fx.seg_off = seg_off, fx.nseg = nseg;
+    fx.lo = lo, fx.hi = hi, fx.level = level;
+    fx.shift = shift, fx.inv_scale = inv_scale, fx.add_back = add_back;
+    fx.nprob = nprob, fx.prob_level = prob_level, fx.prob_z = prob_z, fx.prob_nz = prob_nz;
+    fx.moments = moments, fx.mom_stride = mom_stride;
+    fx.pmax = pmax, fx.rec = rec, fx.status = status, fx.check_const = check_const;
     if (pmax + 1 <= 16)
-        hipLaunchKernelGGL(fixup_kernel<16>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, F64Cols{cols},
-                           col_stride, seg_off, nseg, lo, hi, shift, inv_scale, add_back, level, nprob, prob_level,
-                           prob_z, prob_nz, pairs, npairs, moments, mom_stride, pmax, rec, status, check_const);
+        hipLaunchKernelGGL(fixup_kernel<16>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx, pairs, npairs);
     else
-        hipLaunchKernelGGL(fixup_kernel<32>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, F64Cols{cols},
-                           col_stride, seg_off, nseg, lo, hi, shift, inv_scale, add_back, level, nprob, prob_level,
-                           prob_z, prob_nz, pairs, npairs, moments, mom_stride, pmax, rec, status, check_const);
+        hipLaunchKernelGGL(fixup_kernel<32>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx, pairs, npairs);
     FM_CHECK_LAUNCH("fm_solve_fixup");
     return FM_OK;
 }

@@ -325,47 +325,46 @@ __device__ __forceinline__ int lower_bound_i32(const int32_t* ix, int n, int v) 
     return lo;
 }
 
-// own != 0 (fm_rolling_mean_own): only the rows [ra, rb) = [first fitted row of a month >=
-// m_lo, minus lag; first fitted row of a month >= m_hi) are needed; workgroups and per-thread
+// The per-stage kernels read the fused launch's fm_ts_args (the host entry points below fill
+// the members their kernel uses; the rolling kernels write a.roll with a.kmax values per row).
+//
+// roll_own != 0 (fm_rolling_mean_own): only the rows [ra, rb) = [first fitted row of a month >=
+// seg_lo, minus lag; first fitted row of a month >= seg_hi) are needed; workgroups and per-thread
 // row blocks without such a row are skipped, the others compute exactly as in the full mode
 // (same row-to-thread map, so the same bits), and no NaN fill is written.
-__global__ __launch_bounds__(TT) void rolling_kernel(const double* rec, int64_t r_seg,
-                                                     int64_t r_prob, const int32_t* idx,
-                                                     const int32_t* count, int nseg, int kmax,
-                                                     int window, int minp, double* out, int own,
-                                                     int m_lo, int m_hi, int lag) {
+__global__ __launch_bounds__(TT) void rolling_kernel(fm_ts_args a) {
     __shared__ double xs[RSPAN * RKS];
     const int p = blockIdx.y;
     const int c0 = blockIdx.x * RCH;
-    const int cnt = count[p];
-    const int32_t* ix = idx + (int64_t)p * nseg;
+    const int cnt = a.count[p];
+    const int32_t* ix = a.idx + (int64_t)p * a.nseg;
     int ra = 0, rb = cnt;
-    if (own) {
-        ra = lower_bound_i32(ix, cnt, m_lo) - lag;
+    if (a.roll_own) {
+        ra = lower_bound_i32(ix, cnt, a.seg_lo) - a.lag;
         ra = ra < 0 ? 0 : ra;
-        rb = lower_bound_i32(ix, cnt, m_hi);
+        rb = lower_bound_i32(ix, cnt, a.seg_hi);
         if (c0 + RCH <= ra || c0 >= rb) return;   // block-uniform
     } else {
         // rows past the fitted-month count have no month: NaN (never left uninitialised)
-        const int cend = c0 + RCH < nseg ? c0 + RCH : nseg;
-        for (int e = threadIdx.x; e < (cend - c0) * kmax; e += TT) {
-            const int i = c0 + e / kmax;
-            if (i >= cnt) out[((int64_t)p * nseg + i) * kmax + (e % kmax)] = NAN;
+        const int cend = c0 + RCH < a.nseg ? c0 + RCH : a.nseg;
+        for (int e = threadIdx.x; e < (cend - c0) * a.kmax; e += TT) {
+            const int i = c0 + e / a.kmax;
+            if (i >= cnt) a.roll[((int64_t)p * a.nseg + i) * a.kmax + (e % a.kmax)] = NAN;
         }
     }
     if (c0 >= cnt) return;
-    const int lo = c0 - window + 1 < 0 ? 0 : c0 - window + 1;
+    const int lo = c0 - a.window + 1 < 0 ? 0 : c0 - a.window + 1;
     const int hi = c0 + RCH < cnt ? c0 + RCH : cnt;
-    for (int e = threadIdx.x; e < (hi - lo) * kmax; e += TT) {
-        const int j = lo + e / kmax, k = e % kmax;
-        xs[(j - lo) * RKS + k] = rec[(int64_t)ix[j] * r_seg + (int64_t)p * r_prob + k];
+    for (int e = threadIdx.x; e < (hi - lo) * a.kmax; e += TT) {
+        const int j = lo + e / a.kmax, k = e % a.kmax;
+        xs[(j - lo) * RKS + k] = a.rec[(int64_t)ix[j] * a.r_seg + (int64_t)p * a.r_prob + k];
     }
     __syncthreads();
     const int k = threadIdx.x % RKMAX, g = threadIdx.x / RKMAX;
     const int ib = c0 + g * RPT;
-    if (k >= kmax || ib >= hi) return;
-    if (own && (ib + RPT <= ra || ib >= rb)) return;   // this thread's rows are not needed
-    const int j0 = ib - window + 1 < 0 ? 0 : ib - window + 1;
+    if (k >= a.kmax || ib >= hi) return;
+    if (a.roll_own && (ib + RPT <= ra || ib >= rb)) return;   // this thread's rows are not needed
+    const int j0 = ib - a.window + 1 < 0 ? 0 : ib - a.window + 1;
     CSum sm;   // compensated: an outlier leaving the window leaves no ulp(outlier) behind
     int c = 0;
     for (int j = j0; j <= ib; ++j) {
@@ -375,14 +374,14 @@ __global__ __launch_bounds__(TT) void rolling_kernel(const double* rec, int64_t 
             ++c;
         }
     }
-    out[((int64_t)p * nseg + ib) * kmax + k] = c >= minp ? sm.value() / (double)c : NAN;
+    a.roll[((int64_t)p * a.nseg + ib) * a.kmax + k] = c >= a.min_periods ? sm.value() / (double)c : NAN;
     for (int i = ib + 1; i < ib + RPT && i < hi; ++i) {
         const double xi = xs[(i - lo) * RKS + k];
         if (isfinite(xi)) {
             sm.add(xi);
             ++c;
         }
-        const int jo = i - window;   // leaves the window
+        const int jo = i - a.window;   // leaves the window
         if (jo >= 0) {
             const double xo = xs[(jo - lo) * RKS + k];
             if (isfinite(xo)) {
@@ -391,7 +390,7 @@ __global__ __launch_bounds__(TT) void rolling_kernel(const double* rec, int64_t 
             }
         }
         if (c == 0) sm.reset();
-        out[((int64_t)p * nseg + i) * kmax + k] = c >= minp ? sm.value() / (double)c : NAN;
+        a.roll[((int64_t)p * a.nseg + i) * a.kmax + k] = c >= a.min_periods ? sm.value() / (double)c : NAN;
     }
 }
 
@@ -404,29 +403,24 @@ __global__ __launch_bounds__(TT) void rolling_kernel(const double* rec, int64_t 
 // bit, a signed zero included (v + (-0.0) == v for every v, -0.0 itself too; with +0.0
 // fillers an owner's -0.0 would come back +0.0), in any summation order.
 constexpr int PG = 16;
-__global__ __launch_bounds__(TT) void predictive_kernel(const double* mom, int mom_stride,
-                                                        int nseg, int nprob,
-                                                        const int32_t* prob_k, const int32_t* idx,
-                                                        const int32_t* count, const double* roll,
-                                                        int pmax, int lag, int seg_lo, int seg_hi,
-                                                        double* pred, uint32_t* pst) {
+__global__ __launch_bounds__(TT) void predictive_kernel(fm_ts_args a) {
     const int p = blockIdx.y, lane = threadIdx.x % PG;
     const int i = blockIdx.x * (TT / PG) + threadIdx.x / PG;
-    const bool row = i < nseg;
+    const bool row = i < a.nseg;
     const int ic = row ? i : 0;
-    double* o = pred + ((int64_t)p * nseg + ic) * 4;
-    const int cnt = count[p];
-    const int s = ic < cnt ? idx[(int64_t)p * nseg + ic] : -1;
-    const bool other = ic < cnt && (s < seg_lo || s >= seg_hi);   // another rank's month
+    double* o = a.pred + ((int64_t)p * a.nseg + ic) * 4;
+    const int cnt = a.count[p];
+    const int s = ic < cnt ? a.idx[(int64_t)p * a.nseg + ic] : -1;
+    const bool other = ic < cnt && (s < a.seg_lo || s >= a.seg_hi);   // another rank's month
     uint32_t st = 0;
     double slope = NAN, r2 = NAN, nn = NAN;
-    const int K = prob_k[p];
-    const bool own = row && !other && ic < cnt && ic >= lag;
+    const int K = a.prob_k[p];
+    const bool own = row && !other && ic < cnt && ic >= a.lag;
     double tb = 0.0, ty = 0.0, syy = 0.0, n = 0.0;
     bool bad = false;
     if (own) {
-        const double* c = roll + ((int64_t)p * nseg + (ic - lag)) * pmax;
-        const double* mo = mom + ((int64_t)(s - seg_lo) * nprob + p) * mom_stride;
+        const double* c = a.roll + ((int64_t)p * a.nseg + (ic - a.lag)) * a.pmax;
+        const double* mo = a.moments + ((int64_t)(s - a.seg_lo) * a.nprob + p) * a.mom_stride;
         const int K1 = K + 1;
         n = mo[0];
         bad = lane <= K && isnan(c[lane]);
@@ -457,13 +451,13 @@ __global__ __launch_bounds__(TT) void predictive_kernel(const double* mom, int m
     if (row && lane == 0) {
         if (other) {   // -0.0 record for the sum-combine of sharded runs (exact, signs kept)
             o[0] = o[1] = o[2] = o[3] = -0.0;
-            pst[(int64_t)p * nseg + ic] = 0;
+            a.pred_status[(int64_t)p * a.nseg + ic] = 0;
         } else {
             o[0] = slope;
             o[1] = r2;
             o[2] = nn;
             o[3] = 0.0;
-            pst[(int64_t)p * nseg + ic] = st;
+            a.pred_status[(int64_t)p * a.nseg + ic] = st;
         }
     }
 }
@@ -472,27 +466,24 @@ __global__ __launch_bounds__(TT) void predictive_kernel(const double* mom, int m
 // coefficient, chunk of WRCH output rows), each output a direct sum over its window.
 constexpr int WRCH = 1024;
 
-__global__ __launch_bounds__(TT) void rolling_kernel_wide(const double* rec, int64_t r_seg,
-                                                     int64_t r_prob, const int32_t* idx,
-                                                     const int32_t* count, int nseg, int kmax,
-                                                     int window, int minp, double* out) {
+__global__ __launch_bounds__(TT) void rolling_kernel_wide(fm_ts_args a) {
     __shared__ double xs[WRCH + RMAXW];
-    const int p = blockIdx.y / kmax, k = blockIdx.y - (blockIdx.y / kmax) * kmax;
+    const int p = blockIdx.y / a.kmax, k = blockIdx.y - (blockIdx.y / a.kmax) * a.kmax;
     const int c0 = blockIdx.x * WRCH;
-    const int cnt = count[p];
+    const int cnt = a.count[p];
     // rows past the fitted-month count have no month: NaN (never left uninitialised)
-    const int cend = c0 + WRCH < nseg ? c0 + WRCH : nseg;
+    const int cend = c0 + WRCH < a.nseg ? c0 + WRCH : a.nseg;
     for (int i = (c0 > cnt ? c0 : cnt) + threadIdx.x; i < cend; i += TT)
-        out[((int64_t)p * nseg + i) * kmax + k] = NAN;
+        a.roll[((int64_t)p * a.nseg + i) * a.kmax + k] = NAN;
     if (c0 >= cnt) return;
-    const int32_t* ix = idx + (int64_t)p * nseg;
-    const int lo = c0 - window + 1 < 0 ? 0 : c0 - window + 1;
+    const int32_t* ix = a.idx + (int64_t)p * a.nseg;
+    const int lo = c0 - a.window + 1 < 0 ? 0 : c0 - a.window + 1;
     const int hi = c0 + WRCH < cnt ? c0 + WRCH : cnt;
     for (int j = lo + threadIdx.x; j < hi; j += TT)
-        xs[j - lo] = rec[(int64_t)ix[j] * r_seg + (int64_t)p * r_prob + k];
+        xs[j - lo] = a.rec[(int64_t)ix[j] * a.r_seg + (int64_t)p * a.r_prob + k];
     __syncthreads();
     for (int i = c0 + threadIdx.x; i < hi; i += TT) {
-        const int j0 = i - window + 1 < 0 ? 0 : i - window + 1;
+        const int j0 = i - a.window + 1 < 0 ? 0 : i - a.window + 1;
         double sm = 0.0;
         int c = 0;
         for (int j = j0; j <= i; ++j) {
@@ -502,37 +493,36 @@ __global__ __launch_bounds__(TT) void rolling_kernel_wide(const double* rec, int
                 ++c;
             }
         }
-        out[((int64_t)p * nseg + i) * kmax + k] = c >= minp ? sm / (double)c : NAN;
+        a.roll[((int64_t)p * a.nseg + i) * a.kmax + k] = c >= a.min_periods ? sm / (double)c : NAN;
     }
 }
 
 // Wide problems (> 15 regressors): one wave per (problem, fitted-month row), lane a owns
 // regressor a.
-__global__ __launch_bounds__(WAVE) void predictive_kernel_wide(const double* mom, int mom_stride,
-                                                          int nseg, int nprob,
-                                                          const int32_t* prob_k, const int32_t* idx,
-                                                          const int32_t* count, const double* roll,
-                                                          int pmax, int lag, int seg_lo, int seg_hi,
-                                                          double* pred, uint32_t* pst) {
+__global__ __launch_bounds__(WAVE) void predictive_kernel_wide(fm_ts_args a) {
     const int p = blockIdx.y, i = blockIdx.x, lane = threadIdx.x;
-    double* o = pred + ((int64_t)p * nseg + i) * 4;
-    const int cnt = count[p];
-    const int s = i < cnt ? idx[(int64_t)p * nseg + i] : -1;
-    if (i < cnt && (s < seg_lo || s >= seg_hi)) {
+    double* o = a.pred + ((int64_t)p * a.nseg + i) * 4;
+    const int cnt = a.count[p];
+    const int s = i < cnt ? a.idx[(int64_t)p * a.nseg + i] : -1;
+    if (i < cnt && (s < a.seg_lo || s >= a.seg_hi)) {
         // another rank's month (sharded runs): -0.0 record for the exact sum-combine
         if (lane < 4) o[lane] = -0.0;
-        if (lane == 0) pst[(int64_t)p * nseg + i] = 0;
+        if (lane == 0) a.pred_status[(int64_t)p * a.nseg + i] = 0;
         return;
     }
     uint32_t st = 0;
     double slope = NAN, r2 = NAN, nn = NAN;
-    if (i < cnt && i >= lag) {
-        const int K = prob_k[p];
-        const double* c = roll + ((int64_t)p * nseg + (i - lag)) * pmax;
+    if (i < cnt && i >= a.lag) {
+        const int K = a.prob_k[p];
+        const double* c = a.roll + ((int64_t)p * a.nseg + (i - a.lag)) * a.pmax;
         const bool bad = lane <= K && isnan(c[lane]);
-        const double* mo = mom + ((int64_t)(s - seg_lo) * nprob + p) * mom_stride;
+        const double* mo = a.moments + ((int64_t)(s - a.seg_lo) * a.nprob + p) * a.mom_stride;
         const int K1 = K + 1;
-        const double n = mo[0];
+        double n = mo[0];
+        // n stays in vector registers: held as a scalar (the load is wave-uniform), the NaN that
+        // nn starts from is set by a 64-bit scalar move whose literal gfx950 cannot encode, and
+        // the assembler writes 0.0 in its place
+        asm volatile("" : "+v"(n));
         if (__ballot(bad) == 0 && n >= 2.0) {
             const double* S = mo + 1 + K1;
             double tb = 0.0, ty = 0.0;
@@ -556,7 +546,7 @@ __global__ __launch_bounds__(WAVE) void predictive_kernel_wide(const double* mom
         o[1] = r2;
         o[2] = nn;
         o[3] = 0.0;
-        pst[(int64_t)p * nseg + i] = st;
+        a.pred_status[(int64_t)p * a.nseg + i] = st;
     }
 }
 
@@ -635,14 +625,17 @@ extern "C" int fm_rolling_mean(const double* rec, int64_t r_seg, int64_t r_prob,
     FM_REQUIRE(window >= 1 && window <= RMAXW && min_periods >= 0,
                "fm_rolling_mean: window must be 1..%d", RMAXW);
     if (nprob == 0 || nseg == 0 || kmax == 0) return FM_OK;
+    fm_ts_args a{};   // roll_own, seg_lo, seg_hi and lag stay 0: every row
+    a.rec = rec, a.r_seg = r_seg, a.r_prob = r_prob;
+    a.idx = const_cast<int32_t*>(idx), a.count = const_cast<int32_t*>(count);   // read only
+    a.nseg = nseg, a.nprob = nprob, a.kmax = kmax;
+    a.window = window, a.min_periods = min_periods, a.roll = out;
     if (kmax <= RKMAX && window <= RSPAN - RCH + 1) {
         dim3 grid((nseg + RCH - 1) / RCH, nprob);
-        hipLaunchKernelGGL(rolling_kernel, grid, dim3(TT), 0, (hipStream_t)stream, rec, r_seg, r_prob,
-                           idx, count, nseg, kmax, window, min_periods, out, 0, 0, 0, 0);
+        hipLaunchKernelGGL(rolling_kernel, grid, dim3(TT), 0, (hipStream_t)stream, a);
     } else {
         dim3 grid((nseg + WRCH - 1) / WRCH, nprob * kmax);
-        hipLaunchKernelGGL(rolling_kernel_wide, grid, dim3(TT), 0, (hipStream_t)stream, rec, r_seg, r_prob,
-                           idx, count, nseg, kmax, window, min_periods, out);
+        hipLaunchKernelGGL(rolling_kernel_wide, grid, dim3(TT), 0, (hipStream_t)stream, a);
     }
     FM_CHECK_LAUNCH("fm_rolling_mean");
     return FM_OK;
@@ -659,9 +652,14 @@ extern "C" int fm_rolling_mean_own(const double* rec, int64_t r_seg, int64_t r_p
     FM_REQUIRE(kmax <= RKMAX && window <= RSPAN - RCH + 1,
                "fm_rolling_mean_own: kmax <= %d and window <= %d (the staged kernel)", RKMAX, RSPAN - RCH + 1);
     if (nprob == 0 || nseg == 0 || kmax == 0) return FM_OK;
+    fm_ts_args a{};
+    a.rec = rec, a.r_seg = r_seg, a.r_prob = r_prob;
+    a.idx = const_cast<int32_t*>(idx), a.count = const_cast<int32_t*>(count);   // read only
+    a.nseg = nseg, a.nprob = nprob, a.kmax = kmax;
+    a.window = window, a.min_periods = min_periods, a.roll = out;
+    a.roll_own = 1, a.seg_lo = seg_lo, a.seg_hi = seg_hi, a.lag = lag;
     dim3 grid((nseg + RCH - 1) / RCH, nprob);
-    hipLaunchKernelGGL(rolling_kernel, grid, dim3(TT), 0, (hipStream_t)stream, rec, r_seg, r_prob, idx, count,
-                       nseg, kmax, window, min_periods, out, 1, seg_lo, seg_hi, lag);
+    hipLaunchKernelGGL(rolling_kernel, grid, dim3(TT), 0, (hipStream_t)stream, a);
     FM_CHECK_LAUNCH("fm_rolling_mean_own");
     return FM_OK;
 }
@@ -676,15 +674,16 @@ extern "C" int fm_predictive(const double* moments, int32_t mom_stride, int32_t 
                "fm_predictive: null pointer");
     FM_REQUIRE(lag >= 1, "fm_predictive: lag must be >= 1");
     if (nprob == 0 || nseg == 0) return FM_OK;
+    fm_ts_args a{};
+    a.moments = moments, a.mom_stride = mom_stride, a.nseg = nseg, a.nprob = nprob, a.prob_k = prob_k;
+    a.idx = const_cast<int32_t*>(idx), a.count = const_cast<int32_t*>(count);   // read only
+    a.roll = const_cast<double*>(rolling), a.pmax = pmax;                       // read only
+    a.lag = lag, a.seg_lo = seg_lo, a.seg_hi = seg_hi, a.pred = pred, a.pred_status = pred_status;
     if (pmax <= PG) {
         dim3 grid((nseg + TT / PG - 1) / (TT / PG), nprob);
-        hipLaunchKernelGGL(predictive_kernel, grid, dim3(TT), 0, (hipStream_t)stream, moments,
-                           mom_stride, nseg, nprob, prob_k, idx, count, rolling, pmax, lag, seg_lo,
-                           seg_hi, pred, pred_status);
+        hipLaunchKernelGGL(predictive_kernel, grid, dim3(TT), 0, (hipStream_t)stream, a);
     } else {
-        hipLaunchKernelGGL(predictive_kernel_wide, dim3(nseg, nprob), dim3(WAVE), 0, (hipStream_t)stream, moments,
-                           mom_stride, nseg, nprob, prob_k, idx, count, rolling, pmax, lag, seg_lo,
-                           seg_hi, pred, pred_status);
+        hipLaunchKernelGGL(predictive_kernel_wide, dim3(nseg, nprob), dim3(WAVE), 0, (hipStream_t)stream, a);
     }
     FM_CHECK_LAUNCH("fm_predictive");
     return FM_OK;
@@ -870,18 +869,9 @@ __device__ void ts_rolling_wg(const fm_ts_args& a, int p, int chunk, const int* 
     if (a.roll_own && r0 < cnt) {
         // a sharded rank rolls only the rows its predictive records read: [first fitted row of
         // its months - lag, first fitted row past them)
-        auto lb = [&](int v) {
-            int lo = 0, hi = cnt;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (ixs[mid] < v) lo = mid + 1;
-                else hi = mid;
-            }
-            return lo;
-        };
-        int ra = lb(a.seg_lo) - (predictive ? a.lag : 0);
+        int ra = lower_bound_i32(ixs, cnt, a.seg_lo) - (predictive ? a.lag : 0);
         ra = ra < 0 ? 0 : ra;
-        const int rb = lb(a.seg_hi);
+        const int rb = lower_bound_i32(ixs, cnt, a.seg_hi);
         if (r0 + RROWS <= ra || r0 >= rb) {   // block-uniform: none of this chunk's rows needed
             if (predictive) {
                 // the chunk's predictive records are still this rank's to write: -0.0 records of

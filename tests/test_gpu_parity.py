@@ -930,6 +930,107 @@ def test_pipeline_unfitted_months_fused_equals_per_stage(E, monkeypatch):
             assert_series_close(x[k].ravel(), y[k].ravel(), f"problem {k}")
 
 
+def _wide_panel():
+    """8 months x 120 rows, y + 17 regressors (the narrowest model that leaves the 16-wide
+    kernels).  Month 0 has one +inf in y, month 2 a nonzero constant regressor, month 7 the
+    near-collinear pair of test_near_collinear_refit (x2 = x1 + 1e-7 noise); the rest are clean.
+    The inf month comes first, where the predictive stage has no record to write (it regresses
+    y itself, and defines nothing for an infinite y), the near-collinear month last, so only
+    its own records and the last rolling row carry its eps * cond error."""
+    K = 17
+    df = cases._edge_base(8, 120, K, 311)
+    months = np.sort(df["mthcaldt"].unique())
+    rng = np.random.default_rng(312)
+    df.loc[df.index[(df["mthcaldt"] == months[0]).values][5], "retx"] = np.inf
+    df.loc[df["mthcaldt"] == months[2], "x4"] = 0.5
+    last = (df["mthcaldt"] == months[7]).values
+    df.loc[last, "x2"] = df.loc[last, "x1"] + 1e-7 * rng.standard_normal(int(last.sum()))
+    return df, [f"x{k}" for k in range(K)], months
+
+
+def _wide_oracle(df, xs, months, window, min_periods):
+    """Per month pinv OLS of retx on [1, xs], rolling means of the coefficients and the
+    predictive regression of y on the previous row's rolling forecast (pipeline_arrays'
+    definitions, no winsorizing, one universe)."""
+    P, R2, N, const = [], [], [], []
+    for m in months:
+        d = df[df["mthcaldt"] == m]
+        X, y = d[xs].to_numpy(), d["retx"].to_numpy()
+        p, r2 = O.ols_pinv(np.column_stack([np.ones(len(d)), X]), y)
+        P.append(p)
+        R2.append(r2)
+        N.append(len(d))
+        const.append(O._has_nonzero_const(X))
+    P = np.array(P)
+    roll = np.column_stack([O.rolling_mean(P[:, k], window, min_periods) for k in range(P.shape[1])])
+    pred = {}
+    for i in range(1, len(months)):
+        c = roll[i - 1]
+        if np.isnan(c).any():
+            continue
+        d = df[df["mthcaldt"] == months[i]]
+        F = c[0] + d[xs].to_numpy() @ c[1:]
+        p, r2 = O.ols_pinv(np.column_stack([np.ones(len(d)), F]), d["retx"].to_numpy())
+        pred[i] = (p[1], r2, len(d))
+    return P, np.array(R2), np.array(N), np.array(const), roll, pred
+
+
+def test_wide_model_fixup_and_per_stage_vs_oracle(E, monkeypatch):
+    """17 regressors: the 32-wide solve, its separate fm_solve_fixup launch (constant check,
+    inf in y, QR + SVD refit at 32 columns) and the wide per-stage rolling / predictive
+    kernels, against the oracle.  Clean months and everything computed from them within
+    RTOL; the near-collinear month's records and the one rolling row holding them within
+    eps * cond ~ 1e-7, as in test_near_collinear_refit; status words exact."""
+    df, xs, months = _wide_panel()
+    window, min_periods = 4, 2
+    P, R2, N, const, roll, pred = _wide_oracle(df, xs, months, window, min_periods)
+    T, K = len(months), len(xs)
+    assert np.isinf(P[0]).all() and np.isfinite(P[1:]).all() and const.tolist() == [t == 2 for t in range(T)]
+    assert sorted(pred) == [3, 4, 5, 6, 7]
+
+    names = ["retx"] + xs
+    panel = E.panel_from_arrays([df[c].values for c in names], names, df["mthcaldt"].values)
+    monkeypatch.setattr(E, "ts_fused_fits", lambda *a, **k: False)
+    with E.KernelTimer() as kt:
+        res = E.fm_pass(panel, [E.Model("wide", y=0, xs=list(range(1, K + 1)))], moments=True)
+        ix, summ, roll_t, pred_t, pst_t = E.time_series_result(res, window=window, min_periods=min_periods)
+    assert {"fm_solve_fixup", "fm_rolling_mean", "fm_predictive"} <= set(kt.names())
+    assert res.pmax == K + 1 and res.pmax > 16
+
+    F = E.L
+    want = np.full(T, F.FM_ST_FITTED, dtype=np.int64)
+    want[0] |= F.FM_ST_INF_IN_Y
+    want[2] |= F.FM_ST_CONST_SUSPECT | F.FM_ST_CONST_COL | F.FM_ST_RANK_DEF | F.FM_ST_REFIT
+    want[7] |= F.FM_ST_REFIT   # re-solved from the rows with no singular value cut
+    assert np.array_equal(res.status.cpu().numpy()[:, 0], want)
+    assert ix.count.cpu().numpy().tolist() == [T] and np.array_equal(ix.idx.cpu().numpy()[0], np.arange(T))
+
+    rec = res.rec.cpu().numpy()[:, 0]
+    assert np.array_equal(rec[:, res.pmax + 1].astype(np.int64), N)
+    clean = np.arange(T) != 7
+    cols = [(rec[:, j], P[:, j], f"param {j}") for j in range(K + 1)] + [(rec[:, res.pmax], R2, "R2")]
+    for got, exp, what in cols:
+        s = float(np.sqrt(np.mean(exp[1:7] ** 2)))   # the finite, well-conditioned months
+        assert_series_close(got[clean], exp[clean], what, scale=s)
+        assert_series_close(got[~clean], exp[~clean], what + " (near-collinear)", rtol=1e-7, scale=s)
+
+    got_roll = roll_t.cpu().numpy()[0]
+    assert got_roll.shape == (T, res.pmax)
+    for j in range(K + 1):
+        s = float(np.sqrt(np.nanmean(roll[:7, j] ** 2)))
+        assert_series_close(got_roll[:7, j], roll[:7, j], f"roll {j}", scale=s)
+        assert_series_close(got_roll[7:, j], roll[7:, j], f"roll {j} (near-collinear)", rtol=1e-7, scale=s)
+
+    got_pred, pst = pred_t.cpu().numpy()[0], pst_t.cpu().numpy()[0]
+    rows = sorted(pred)
+    assert np.array_equal(np.nonzero(pst & F.FM_ST_FITTED)[0], rows) and set(pst.tolist()) <= {0, F.FM_ST_FITTED}
+    for c, what in enumerate(("pred slope", "pred R2")):
+        assert_series_close(got_pred[rows, c], np.array([pred[i][c] for i in rows]), what)
+    assert np.array_equal(got_pred[rows, 2], [pred[i][2] for i in rows])
+    unf = np.setdiff1d(np.arange(T), rows)
+    assert np.isnan(got_pred[unf, :3]).all()   # rows with no forecast: NaN slope, R2 and n
+
+
 def _degenerate_std_months(a):
     """A9 edge months: a predictor constant (exactly representable, so its std is exactly
     0) in one month and present in a single row of another: z is all-NaN there."""
