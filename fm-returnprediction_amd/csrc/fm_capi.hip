@@ -47,6 +47,7 @@ extern "C" int64_t fm_struct_size(const char* name) {
     if (n == "fm_ts_args") return (int64_t)sizeof(fm_ts_args);
     if (n == "fm_chars_args") return (int64_t)sizeof(fm_chars_args);
     if (n == "fm_port_args") return (int64_t)sizeof(fm_port_args);
+    if (n == "fm_rank_args") return (int64_t)sizeof(fm_rank_args);
     return -1;
 }
 

@@ -27,6 +27,8 @@ FM_MAX_MODELS = 6
 FM_MAX_LEVELS = 3
 FM_MAX_PORTS = 20
 FM_TS_FUSED_MAX_LDS = 128 * 1024
+FM_RANK_AVERAGE, FM_RANK_MIN, FM_RANK_MAX = 0, 1, 2
+FM_RANK_RAW, FM_RANK_PCT, FM_RANK_UNIFORM = 0, 1, 2
 
 _p = C.c_void_p
 _i32 = C.c_int32
@@ -112,6 +114,14 @@ class PortArgs(C.Structure):
     ]
 
 
+class RankArgs(C.Structure):
+    _fields_ = [
+        ("src", _p), ("src_stride", _i64), ("dst", _p), ("dst_stride", _i64), ("ncols", _i32),
+        ("nseg", _i32), ("seg_off", _p), ("max_seg_len", _i32), ("min_level", _i32), ("level", _p),
+        ("method", _i32), ("scale", _i32), ("nvalid", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -150,6 +160,7 @@ _SIGS = {
     "fm_ts_fused_lds_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "fm_forecast": (_i32, [_p, _i64, _i32, _p, _i32, _i64, _p, _i32, _p, _p]),
     "fm_portfolio_sort": (_i32, [C.POINTER(PortArgs), _p]),
+    "fm_rank_transform": (_i32, [C.POINTER(RankArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -165,7 +176,7 @@ _SIGS = {
 EXPORTED = tuple(_SIGS)
 _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_args": SelectArgs,
             "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs,
-            "fm_port_args": PortArgs}
+            "fm_port_args": PortArgs, "fm_rank_args": RankArgs}
 
 _lib = None
 

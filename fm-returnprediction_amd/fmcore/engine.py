@@ -1219,6 +1219,70 @@ def portfolio_summary(p: Portfolios, nw_lags=4):
     return Summary(s.mean.view(n1, k), s.se.view(n1, k), s.tstat.view(n1, k), s.nobs.view(n1, k))
 
 
+RANK_MAX_ROWS = 16384   # fm_rank_transform's month limit (one workgroup per (month, column), keys in LDS)
+RANK_METHODS = {"average": L.FM_RANK_AVERAGE, "min": L.FM_RANK_MIN, "max": L.FM_RANK_MAX}
+RANK_SCALES = {"raw": L.FM_RANK_RAW, "pct": L.FM_RANK_PCT, "uniform": L.FM_RANK_UNIFORM}
+
+
+def rank_transform(panel: DevicePanel, cols=None, method="average", scale="pct", level=None, min_level=0,
+                   out=None):
+    """A13: the chosen columns (names or indices; default all) replaced by their cross-sectional
+    ranks within each month (fm_rank_transform; pandas ``groupby(month)[x].rank(method,
+    pct)``, the exact definition is in fm_hip.h), every other column copied unchanged.
+    ``scale``: "raw" r, "pct" r / n, "uniform" r / (n + 1) - 0.5.  ``level`` (uint8 per row) with
+    ``min_level`` ranks within that universe and gives NaN outside it.  Returns a new f64-layout
+    ``DevicePanel`` that shares the input's segments, ``me``, ``nyse``, ``months`` and ``order``
+    (``out``: its [C, n] float64 column block, not the input's); the [len(cols), T] int32 table
+    of ranked rows per month is its ``rank_nvalid`` attribute."""
+    if method not in RANK_METHODS:
+        raise ValueError(f"rank_transform: method must be one of {sorted(RANK_METHODS)} "
+                         "('first' and 'dense' are out of scope)")
+    if scale not in RANK_SCALES:
+        raise ValueError(f"rank_transform: scale must be one of {sorted(RANK_SCALES)}")
+    src = panel.values()
+    C, n, T = panel.ncols, panel.nrows, panel.nseg
+    idx = list(range(C)) if cols is None else [panel.col(c) if isinstance(c, str) else int(c) for c in cols]
+    if any(i < 0 or i >= C for i in idx) or len(set(idx)) != len(idx):
+        raise ValueError("rank_transform: cols must be distinct columns of the panel")
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.dtype != torch.float64 or out.shape != src.shape or out.device != src.device or out.stride(1) != 1:
+        raise ValueError("rank_transform: out must be a float64 tensor of the panel's [C, n] shape on its device")
+    if out.data_ptr() == src.data_ptr():
+        raise ValueError("rank_transform: out must not be the panel's own columns")
+    if level is not None:
+        if level.dtype != torch.uint8 or level.dim() != 1 or level.shape[0] != n or level.device != src.device:
+            raise ValueError(f"rank_transform: level must be a uint8 [{n}] tensor on {src.device}")
+        level = level.contiguous()
+    for i in sorted(set(range(C)) - set(idx)):
+        out[i].copy_(src[i])
+    nvalid = torch.empty((len(idx), T), dtype=torch.int32, device=src.device)
+    # consecutive columns go in one launch (all 14 predictors of the pipeline: one)
+    runs, k = [], 0
+    while k < len(idx):
+        e = k + 1
+        while e < len(idx) and idx[e] == idx[e - 1] + 1:
+            e += 1
+        runs.append((k, e))
+        k = e
+    for k, e in runs:
+        a = L.RankArgs()
+        a.src, a.src_stride = src[idx[k]].data_ptr(), src.stride(0)
+        a.dst, a.dst_stride = out[idx[k]].data_ptr(), out.stride(0)
+        a.ncols, a.nseg, a.seg_off = e - k, T, panel.seg_off.data_ptr()
+        a.max_seg_len, a.min_level, a.level = panel.max_seg_len, int(min_level), _ptr(level)
+        a.method, a.scale = RANK_METHODS[method], RANK_SCALES[scale]
+        a.nvalid = nvalid[k].data_ptr()
+        _kcall("fm_rank_transform", "fm_rank_transform", L.C.byref(a), _stream())
+        _remember("fm_rank_transform", "fm_rank_transform", a, src, out, nvalid, level, panel.seg_off)
+    res = DevicePanel(cols=out, names=list(panel.names), seg_off=panel.seg_off, seg_off_h=panel.seg_off_h,
+                      months=panel.months, me=panel.me, nyse=panel.nyse, order=panel.order,
+                      chunk_rows=panel.chunk_rows, chunk_split=panel.chunk_split, chunk_policy=panel.chunk_policy,
+                      row_origin=panel.row_origin)
+    res.rank_nvalid = nvalid
+    return res
+
+
 def segment_moments(panel: DevicePanel, level=None, min_level=0, finite_only=True, cols=None):
     """Per (column, month) count, mean and ddof=1 std of the non-missing values."""
     src = panel.values() if cols is None else cols

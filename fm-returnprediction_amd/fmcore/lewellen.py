@@ -72,6 +72,7 @@ class PipelineConfig:
     lag: int = 1
     forecasts: bool = True
     fig1: bool = True
+    rank: Optional[str] = None     # A13: predictors -> per-month ranks, a scale name ("raw", "pct", "uniform")
 
 
 @dataclass
@@ -127,6 +128,14 @@ def local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx")
     level, bp = None, None
     nlevels = 1
     models, names = build_models(panel, model_cols, y=y, fig1=cfg.fig1, universes=cfg.universes)
+    ranked = None
+    if cfg.rank is not None:
+        # A13 (build-defined): every predictor column (never y) becomes its average-tie rank
+        # within the month's full cross-section; the ranked columns are not winsorized
+        if cfg.standardize:
+            raise ValueError("PipelineConfig: rank and standardize exclude each other")
+        ranked = sorted({i for m in models for i in m.xs} - {panel.col(y)})
+        panel = E.rank_transform(panel, cols=ranked, method="average", scale=cfg.rank)
     select = cfg.winsorize or cfg.standardize
     # get_subsets' NYSE breakpoints + level bytes come with the winsorize call
     # (fm_select_universe): on the bench's short months they share the select fix-up's launch
@@ -149,6 +158,9 @@ def local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx")
             cuts, (a, b, level) = cuts
             nlevels = 3
             bp = (a, b)
+        if ranked:
+            cuts.lo[ranked] = float("nan")
+            cuts.hi[ranked] = float("nan")
         shift = cuts.center
         if cfg.standardize:
             shift, inv_scale, add_back = _standardize_params(panel, cuts, panel.col(y))

@@ -8,7 +8,7 @@ Mirrored (same names, signatures, return types and row/column/index order):
   build_table_2    reference :674-868   9 FM passes batched into one Gram pass on device
   create_figure_1  reference :871-957   F1 OLS + 120-month rolling means on device
 Extensions the north star names (not in the reference; parity unpinned):
-  standardize, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
+  standardize, rank_transform, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
   predictive_slope_regressions, forecast_sorted_portfolios, lewellen_pipeline.
 Firm-axis characteristic builders (§8(f) row 2; one fused device pass, fm_firm_chars):
   calc_log_size, calc_log_bm, calc_return_12_2, calc_accruals, calc_roa,
@@ -78,7 +78,7 @@ def get_subsets(crsp_comp: pd.DataFrame) -> dict:
 
 
 # ------------------------------------------------------------------------------------------
-# Winsorize / standardize
+# Winsorize / standardize / rank
 # ------------------------------------------------------------------------------------------
 def _split_runs(varlist):
     runs, cur = [], []
@@ -127,6 +127,41 @@ def standardize(crsp_comp: pd.DataFrame, varlist: list, date_col: str = "mthcald
     for i, v in enumerate(varlist):
         col = np.full(len(df), np.nan)
         col[panel.order] = z[i]
+        df[v] = col
+    return df
+
+
+_UNIVERSE_LEVEL = {None: 0, "all_but_tiny": 1, "large": 2}
+
+
+def rank_transform(crsp_comp: pd.DataFrame, varlist: list, date_col: str = "mthcaldt", method: str = "average",
+                   scale: str = "pct", universe: str = None) -> pd.DataFrame:
+    """Per-month cross-sectional ranks of each variable over its non-NaN values (extension A13;
+    the reference has no rank transform): pandas' ``groupby(date_col)[v].rank(method=method)``
+    for ``scale`` "raw", with ``pct=True`` for "pct", and rank / (count + 1) - 0.5 for
+    "uniform", bit for bit, on the device (fm_rank_transform).  ``method`` in {"average", "min",
+    "max"}.  ``universe`` in {None, "all_but_tiny", "large"} ranks within that get_subsets
+    universe (from ``me`` and ``primaryexch``) and gives NaN outside it.  Returns a copy of the
+    frame in the caller's row order; rows with a missing month label get NaN."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    df = crsp_comp.copy()
+    varlist = list(varlist)
+    if not varlist:
+        return df
+    arrays = [_api.as_f64(df[v]) for v in varlist]
+    me = nyse = level = None
+    if universe is not None:
+        me = _api.as_f64(df["me"])
+        nyse = (df["primaryexch"] == "N").to_numpy().astype(np.uint8)
+    panel = _E.panel_from_arrays(arrays, varlist, df[date_col].values, me=me, nyse=nyse)
+    if universe is not None:
+        level = _E.universe(panel)[2]
+    r = _E.rank_transform(panel, method=method, scale=scale, level=level,
+                          min_level=_UNIVERSE_LEVEL[universe]).cols.cpu().numpy()
+    for i, v in enumerate(varlist):
+        col = np.full(len(df), np.nan)
+        col[panel.order] = r[i]
         df[v] = col
     return df
 
@@ -628,7 +663,6 @@ def predictive_slope_regressions(df: pd.DataFrame, forecast, return_col: str = "
 
 
 PORTFOLIO_COLUMNS = ["ew_ret", "ew_pred", "vw_ret", "vw_pred"]
-_UNIVERSE_LEVEL = {None: 0, "all_but_tiny": 1, "large": 2}
 
 
 def forecast_sorted_portfolios(df: pd.DataFrame, forecast, return_col: str = "retx", weight_col: str = None,

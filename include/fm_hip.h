@@ -44,6 +44,8 @@
  *   fm_forecast     <- build-defined extension A7: per-row F = a_{t-1} + b_{t-1}'x_t
  *   fm_portfolio_sort <- build-defined extension: forecast-sorted portfolios, paper Table 5;
  *                      no reference line
+ *   fm_rank_transform <- build-defined extension A13: per-month cross-sectional ranks of the
+ *                      characteristics (pandas groupby(month)[x].rank); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -189,7 +191,7 @@ const char* fm_version(void);
 const char* fm_last_error(void);
 int fm_abi_sizes(int32_t* gram_args, int32_t* solve_args);
 /* sizeof the named argument struct ("fm_gram_args", "fm_solve_args", "fm_select_args",
- * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args"); -1 for an unknown name.  Bindings
+ * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args", "fm_rank_args"); -1 for an unknown name.  Bindings
  * check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
 int fm_device_arch(char* buf, int32_t len);
@@ -449,6 +451,48 @@ typedef struct fm_port_args {
 } fm_port_args;
 
 int fm_portfolio_sort(const fm_port_args* args, void* stream);
+
+/* fm_rank_transform: every chosen column's cross-sectional rank within its month (build-defined
+ * extension A13; no reference line).  It is pandas' groupby(month)[x].rank(method, pct) and is
+ * pinned to it bit for bit.  Rows sorted by (month, permno), months seg_off[nseg+1] of at most
+ * 16,384 rows (longer: FM_ETOOBIG before any launch).  Per column and month:
+ *   eligible rows: the value is not NaN and, with level given, level >= min_level;
+ *   order:         +-inf are ordinary values; -0.0 and +0.0 are equal;
+ *   counts:        n = the month's eligible rows; for an eligible row, less = the eligible rows
+ *                  with a smaller value, eq = those with an equal value, itself included;
+ *   rank r:        FM_RANK_AVERAGE less + (eq + 1) / 2, FM_RANK_MIN less + 1, FM_RANK_MAX less + eq;
+ *   output:        FM_RANK_RAW r, FM_RANK_PCT r / n, FM_RANK_UNIFORM r / (n + 1) - 0.5 (two IEEE
+ *                  operations, not contracted); ineligible rows get NaN;
+ *   nvalid[c][t] = n.
+ * Every r is a multiple of 0.5 and exact in FP64, so every output is specified to the bit.  A
+ * month's outputs depend on that month's rows alone: two calls, or a month-sharded call, give
+ * the same bits.  dst == src is refused (FM_EINVAL).  pandas' methods "first" and "dense" are
+ * out of scope: the three methods above need only the two counts of a row's key, which a sort
+ * of the keys alone gives; "first" needs a stable (key, row) sort and "dense" a distinct count.
+ * Zero-initialize the struct (it grows at the end). */
+#define FM_RANK_AVERAGE 0
+#define FM_RANK_MIN 1
+#define FM_RANK_MAX 2
+#define FM_RANK_RAW 0
+#define FM_RANK_PCT 1
+#define FM_RANK_UNIFORM 2
+typedef struct fm_rank_args {
+    const double* src;           /* [ncols][src_stride], rows sorted by (month, permno) */
+    int64_t src_stride;
+    double* dst;                 /* [ncols][dst_stride] */
+    int64_t dst_stride;
+    int32_t ncols;
+    int32_t nseg;
+    const int64_t* seg_off;      /* [nseg+1] */
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t min_level;
+    const uint8_t* level;        /* [rows] universe level or NULL (every row) */
+    int32_t method;              /* FM_RANK_AVERAGE / MIN / MAX */
+    int32_t scale;               /* FM_RANK_RAW / PCT / UNIFORM */
+    int32_t* nvalid;             /* [ncols][nseg] the month's count of ranked rows, or NULL */
+} fm_rank_args;
+
+int fm_rank_transform(const fm_rank_args* args, void* stream);
 
 int fm_segment_moments(const double* cols, int64_t col_stride, int32_t ncols,
                        const int64_t* seg_off, int32_t nseg, const uint8_t* level,

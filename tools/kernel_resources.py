@@ -15,7 +15,7 @@ CS = os.path.join(ROOT, "fm-returnprediction_amd", "csrc")
 HOT = ("select_pair_hk_kernelILi40", "select_pair_kernelILi40", "select_fixup_universe_kernelILi20",
        "select_fixup_kernelILi20", "select_long_hk_kernelILi40", "universe_kernelILi20",
        "gram_kernelILi1ELi15ELi3ELb1", "gram_kernelILi1ELi15ELi3ELb0", "solve16_kernel", "ts_fused_kernel",
-       "rolling_std_kernel", "firm_chars_kernel", "split_planes_kernel", "port_kernelILi")
+       "rolling_std_kernel", "firm_chars_kernel", "split_planes_kernel", "port_kernelILi", "rank_kernelILi")
 
 
 def report(src):
@@ -41,7 +41,8 @@ def report(src):
 
 def main():
     srcs = sys.argv[1:] or [os.path.join(CS, f) for f in ("fm_select.hip", "fm_gram.hip", "fm_solve.hip",
-                                                           "fm_ts.hip", "fm_chars.hip", "fm_elem.hip", "fm_port.hip")]
+                                                           "fm_ts.hip", "fm_chars.hip", "fm_elem.hip", "fm_port.hip",
+                                                           "fm_rank.hip")]
     bad = 0
     for src in srcs:
         for name, vgpr, spill, lds, priv in report(src):
