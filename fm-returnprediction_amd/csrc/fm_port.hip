@@ -19,6 +19,14 @@
 //      or the other months.
 // Forecast, return, weight, level and NYSE byte are each read from HBM once (months of more
 // than 5,120 rows re-read return and weight per term, from the cache).
+//
+// fm_forecast_portfolio_sort runs the same four phases (the same kernel template, instantiated
+// with FusedSrc) over a grid of (month, sort), with phase 1's load replaced by the forecast itself:
+// F = c0 + sum_k c_k clip(x_k) from the panel's own layout (FP64 columns or the split planes),
+// predictor k in the outer loop (the month's c_k and cuts are wave-uniform) and the thread's
+// VPT rows in the inner one (VPT independent loads in flight), accumulated in the fe registers
+// the sort keeps anyway; phase 4 reads the return column through the same layout.  No clipped
+// panel and no forecast vector ever reach HBM.
 #include <math.h>
 
 #include "fm_common.h"
@@ -65,9 +73,39 @@ __device__ __forceinline__ void lds_bitonic(uint64_t* buf, int P) {
     }
 }
 
-template <int NT, int VPT>
-__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_args a) {
+// What a month's workgroup sorts by.  PlainSrc: the caller's forecast and return vectors
+// (fm_portfolio_sort).  FusedSrc<PL>: sort j of fm_forecast_portfolio_sort, panel values from the
+// FP64 columns or (PL) from the planes, two 4-byte loads joined in registers.
+struct PlainSrc {
+    static constexpr bool FUSED = false;
+    __device__ static PlainSrc make(const fm_port_args&) { return {}; }
+};
+
+template <bool PL>
+struct FusedSrc {
+    static constexpr bool FUSED = true;
+    const fm_fport_args& a;
+    int j;   // blockIdx.y
+    __device__ static FusedSrc make(const fm_fport_args& a) { return {a, (int)blockIdx.y}; }
+    __device__ __forceinline__ double value(int col, int64_t row) const {
+        if constexpr (PL) {
+            const int64_t o = (int64_t)col * a.plane_stride + row;
+            const uint32_t h = a.hi_plane[o], l = a.lo_plane[o];
+            return __longlong_as_double((long long)(((uint64_t)h << 32) | l));
+        } else {
+            return a.cols[(int64_t)col * a.col_stride + row];
+        }
+    }
+};
+
+// One month (of one sort) by the NT-thread workgroup: A is fm_port_args with PlainSrc,
+// fm_fport_args with FusedSrc (the fields both share have the same names).  The body stays in
+// the kernel itself: behind an inlined device function the 1024 x 16 form allocates 18 more VGPRs.
+template <int NT, int VPT, class Src = PlainSrc, class A = fm_port_args>
+__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(A a) {
     constexpr int NW = NT / WAVE;
+    constexpr bool FUSED = Src::FUSED;
+    const Src src = Src::make(a);
     extern __shared__ uint64_t pbuf[];   // the keys; after the breakpoints the row lists
     __shared__ double s_bp[FM_MAX_PORTS];
     __shared__ double s_rec[FM_MAX_PORTS][4];
@@ -86,7 +124,18 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
     const int64_t r0 = a.seg_off[s];
     int L = (int)(a.seg_off[s + 1] - r0);
     L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
-    const double* __restrict__ F = a.forecast + r0;
+    // outputs: month s of sort j at [j][s], row vectors at [j][row]
+    int64_t so = s, ro = r0;
+    int min_level;
+    if constexpr (FUSED) {
+        so += (int64_t)src.j * a.nseg;
+        ro += (int64_t)src.j * a.nrows;
+        min_level = a.sel_level[src.j];
+    } else {
+        min_level = a.min_level;
+    }
+    const double* __restrict__ F = nullptr;   // PlainSrc: the month's forecasts
+    if constexpr (!FUSED) F = a.forecast + r0;
 
     FM_PROBE_AT(port, 0);
     // ---- 1. load, eligibility, breakpoint rows -------------------------------------------
@@ -94,14 +143,53 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
     uint32_t bpm = 0;   // bit v: row v of this thread is a breakpoint row
     if (L > 0) {        // block-uniform
         const int last = L - 1;
+        if constexpr (FUSED) {
+            // the forecast: predictor k outside (c_k and the month's cuts are wave-uniform), the
+            // thread's rows inside (VPT independent loads in flight); every product and every sum
+            // rounds on its own (-ffp-contract=off), in fm_forecast's order
+            const int K = a.sel_k[src.j];
+            const double* __restrict__ c = a.coef + so * a.coef_stride;
+            const double c0 = c[0];
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) fe[v] = c0;
+#pragma unroll 1
+            for (int k = 0; k < K; ++k) {
+                const int col = a.sel_cols[src.j][k];
+                const double ck = c[1 + k];
+                const double lo = a.lo != nullptr ? a.lo[(int64_t)col * a.nseg + s] : NAN;
+                const double hi = a.hi != nullptr ? a.hi[(int64_t)col * a.nseg + s] : NAN;
+                double x[VPT];
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int idx = (w * VPT + v) * WAVE + lane;
+                    x[v] = src.value(col, r0 + (idx < L ? idx : last));
+                }
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    double y = x[v];   // fm_clip: a NaN value stays NaN, a NaN bound is ignored
+                    if (y < lo) y = lo;
+                    if (y > hi) y = hi;
+                    fe[v] = fe[v] + ck * y;
+                }
+            }
+            if (a.forecast_out != nullptr) {
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int idx = (w * VPT + v) * WAVE + lane;
+                    if (idx < L) a.forecast_out[ro + idx] = fe[v];
+                }
+            }
+        }
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
             const int idx = (w * VPT + v) * WAVE + lane;
             const int ci = idx < L ? idx : last;
-            const double f = F[ci];
+            double f;
+            if constexpr (FUSED) f = fe[v];
+            else f = F[ci];
             const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
             const int ny = a.nyse != nullptr ? (int)a.nyse[r0 + ci] : 1;
-            const bool elig = idx < L && isfinite(f) && lv >= a.min_level;
+            const bool elig = idx < L && isfinite(f) && lv >= min_level;
             fe[v] = elig ? f : NAN;
             bpm |= (elig && (a.nyse_breakpoints == 0 || ny != 0)) ? 1u << v : 0u;
         }
@@ -111,13 +199,13 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
     }
     const int n = block_sum<NW>((int)__popc(bpm), s_iscr);
     FM_PROBE_AT(port, 1);
-    uint8_t* port = a.port != nullptr ? a.port + r0 : nullptr;
-    double* rec = a.rec + (int64_t)s * (nport + 1) * 4;
-    int32_t* cnt = a.cnt + (int64_t)s * nport;
+    uint8_t* port = a.port != nullptr ? a.port + ro : nullptr;
+    double* rec = a.rec + so * (nport + 1) * 4;
+    int32_t* cnt = a.cnt + so * nport;
 
     if (n < a.min_count) {   // block-uniform: the month is unsorted
-        if (tid == 0) a.status[s] = 0u;
-        if (tid < nm1 && a.bp != nullptr) a.bp[(int64_t)s * nm1 + tid] = NAN;
+        if (tid == 0) a.status[so] = 0u;
+        if (tid < nm1 && a.bp != nullptr) a.bp[so * nm1 + tid] = NAN;
         if (tid < (nport + 1) * 4) rec[tid] = NAN;
         if (tid < nport) cnt[tid] = 0;
         if (port != nullptr) {
@@ -257,7 +345,7 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
     if (tid < nm1) {
         const double b = qlerp(kval(s_okey[2 * tid]), kval(s_okey[2 * tid + 1]), s_g[tid], 0);
         s_bp[tid] = b;
-        if (a.bp != nullptr) a.bp[(int64_t)s * nm1 + tid] = b;
+        if (a.bp != nullptr) a.bp[so * nm1 + tid] = b;
     }
     FM_PROBE_AT(port, 4);
     __syncthreads();   // the keys are dead from here: pbuf becomes the row lists
@@ -320,7 +408,8 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
     // return and weight: read once, coalesced, by the rows' owners; kept in registers where the
     // budget allows (HOLD), else re-read per term from the cache
     constexpr bool HOLD = VPT <= 10;
-    const double* __restrict__ R = a.ret + r0;
+    const double* __restrict__ R = nullptr;   // PlainSrc: the month's returns
+    if constexpr (!FUSED) R = a.ret + r0;
     const double* __restrict__ W = a.weight != nullptr ? a.weight + r0 : nullptr;
     double r[HOLD ? VPT : 1], x[HOLD ? VPT : 1];
     if constexpr (HOLD) {
@@ -329,7 +418,8 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
         for (int v = 0; v < VPT; ++v) {
             const int idx = (w * VPT + v) * WAVE + lane;
             const int ci = idx < L ? idx : last;
-            r[v] = R[ci];
+            if constexpr (FUSED) r[v] = src.value(a.ret_col, r0 + ci);   // the same layout view
+            else r[v] = R[ci];
             x[v] = W != nullptr ? W[ci] : NAN;
         }
     }
@@ -350,7 +440,8 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
                     rr = r[v];
                     ww = x[v];
                 } else {
-                    rr = R[idx];
+                    if constexpr (FUSED) rr = src.value(a.ret_col, r0 + idx);
+                    else rr = R[idx];
                     ww = W != nullptr ? W[idx] : NAN;
                 }
                 const bool okr = isfinite(rr), okw = okr && isfinite(ww) && ww > 0.0;
@@ -403,7 +494,7 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(fm_port_arg
     __syncthreads();
     if (tid < 4) rec[nport * 4 + tid] = s_rec[nm1][tid] - s_rec[0][tid];   // NaN if an end is NaN
     FM_PROBE_AT(port, 7);
-    if (tid == 0) a.status[s] = 1u;
+    if (tid == 0) a.status[so] = 1u;
 }
 
 template <int NT, int VPT>
@@ -421,6 +512,32 @@ int launch_port(const fm_port_args& a, size_t lds, hipStream_t st) {
     }
     hipLaunchKernelGGL((port_kernel<NT, VPT>), dim3(a.nseg), dim3(NT), lds, st, a);
     return FM_OK;
+}
+
+template <int NT, int VPT, bool PL>
+int launch_fport(const fm_fport_args& a, size_t lds, hipStream_t st) {
+    if (lds >= 64 * 1024) {   // each instantiation opts in on its own (once)
+        static bool attr_set = false;
+        if (!attr_set) {
+            if (hipFuncSetAttribute((const void*)port_kernel<NT, VPT, FusedSrc<PL>, fm_fport_args>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    8 * pow2_ceil(NT * VPT)) != hipSuccess) {
+                set_error("fm_forecast_portfolio_sort: cannot raise the dynamic LDS limit");
+                return FM_EHIP;
+            }
+            attr_set = true;
+        }
+    }
+    hipLaunchKernelGGL((port_kernel<NT, VPT, FusedSrc<PL>, fm_fport_args>), dim3(a.nseg, a.nsel), dim3(NT), lds, st, a);
+    return FM_OK;
+}
+
+// Dynamic LDS of a month of up to max_seg_len rows: the keys of the full sort; months that can
+// reach the sample select hold its tables instead.
+size_t port_lds_bytes(int max_seg_len) {
+    size_t lds = 8 * (size_t)pow2_ceil(max_seg_len);
+    const size_t fast = 13 * (size_t)(max_seg_len <= 512 * 10 ? 512 : 1024) + (size_t)PSLOTS * PCAP * 8;
+    if (max_seg_len > PORT_FAST_MIN && lds < fast) lds = fast;
+    return lds;
 }
 
 }  // namespace
@@ -446,15 +563,57 @@ extern "C" int fm_portfolio_sort(const fm_port_args* args, void* stream) {
     if (a.nseg == 0) return FM_OK;
     FM_REQUIRE(a.forecast && a.ret && a.seg_off && a.rec && a.cnt && a.status, "fm_portfolio_sort: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    // the keys of the full sort; months that can reach the sample select hold its tables instead
-    size_t lds = 8 * (size_t)pow2_ceil(a.max_seg_len);
-    const size_t fast = 13 * (size_t)(a.max_seg_len <= 512 * 10 ? 512 : 1024) + (size_t)PSLOTS * PCAP * 8;
-    if (a.max_seg_len > PORT_FAST_MIN && lds < fast) lds = fast;
+    const size_t lds = port_lds_bytes(a.max_seg_len);
     int rc;
     if (a.max_seg_len <= 256 * 4) rc = launch_port<256, 4>(a, lds, st);
     else if (a.max_seg_len <= 512 * 10) rc = launch_port<512, 10>(a, lds, st);
     else rc = launch_port<1024, 16>(a, lds, st);
     if (rc != FM_OK) return rc;
     FM_CHECK_LAUNCH("fm_portfolio_sort");
+    return FM_OK;
+}
+
+extern "C" int fm_forecast_portfolio_sort(const fm_fport_args* args, void* stream) {
+    using namespace fm;
+    FM_REQUIRE(args != nullptr, "fm_forecast_portfolio_sort: null args");
+    const fm_fport_args& a = *args;
+    FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0 && a.nrows >= 0, "fm_forecast_portfolio_sort: bad sizes");
+    FM_REQUIRE(a.nsel >= 0 && a.nsel <= FM_MAX_SORTS, "fm_forecast_portfolio_sort: nsel must be 0..%d", FM_MAX_SORTS);
+    FM_REQUIRE(a.nport >= 2 && a.nport <= FM_MAX_PORTS, "fm_forecast_portfolio_sort: nport must be 2..%d", FM_MAX_PORTS);
+    for (int j = 0; j < a.nport - 1; ++j) {
+        const double lo = j == 0 ? 0.0 : a.q[j - 1];
+        FM_REQUIRE(a.q[j] > lo && a.q[j] < 1.0, "fm_forecast_portfolio_sort: q must be strictly ascending in (0, 1)");
+    }
+    FM_REQUIRE(a.nyse_breakpoints == 0 || a.nyse != nullptr, "fm_forecast_portfolio_sort: nyse_breakpoints needs nyse");
+    FM_REQUIRE(a.min_count >= 1, "fm_forecast_portfolio_sort: min_count must be >= 1");
+    if (a.max_seg_len > PORT_MAX_ROWS) {
+        set_error("fm_forecast_portfolio_sort: %d-row months exceed %d", a.max_seg_len, PORT_MAX_ROWS);
+        return FM_ETOOBIG;
+    }
+    if (a.nseg == 0 || a.nsel == 0) return FM_OK;   // nothing is read: an empty panel has no pointers
+    const bool f64 = a.cols != nullptr, pl = a.hi_plane != nullptr || a.lo_plane != nullptr;
+    FM_REQUIRE(f64 != pl, "fm_forecast_portfolio_sort: exactly one of cols and the planes must be given");
+    FM_REQUIRE(!pl || (a.hi_plane != nullptr && a.lo_plane != nullptr), "fm_forecast_portfolio_sort: both planes are needed");
+    FM_REQUIRE((f64 ? a.col_stride : a.plane_stride) >= a.nrows, "fm_forecast_portfolio_sort: stride below the row count");
+    FM_REQUIRE(a.ncols >= 1 && a.ret_col >= 0 && a.ret_col < a.ncols, "fm_forecast_portfolio_sort: ret_col outside the panel");
+    FM_REQUIRE((a.lo == nullptr) == (a.hi == nullptr), "fm_forecast_portfolio_sort: lo and hi go together");
+    for (int j = 0; j < a.nsel; ++j) {
+        const int K = a.sel_k[j];
+        FM_REQUIRE(K >= 1 && K <= FM_MAX_SORT_K, "fm_forecast_portfolio_sort: sort %d has K = %d, not 1..%d", j, K, FM_MAX_SORT_K);
+        FM_REQUIRE(a.coef_stride >= K + 1, "fm_forecast_portfolio_sort: coef_stride %d below K + 1 = %d", a.coef_stride, K + 1);
+        FM_REQUIRE(a.sel_level[j] >= 0 && a.sel_level[j] <= 255, "fm_forecast_portfolio_sort: sel_level must be 0..255");
+        for (int k = 0; k < K; ++k)
+            FM_REQUIRE(a.sel_cols[j][k] >= 0 && a.sel_cols[j][k] < a.ncols,
+                       "fm_forecast_portfolio_sort: sort %d column %d outside the panel's %d", j, a.sel_cols[j][k], a.ncols);
+    }
+    FM_REQUIRE(a.coef && a.seg_off && a.rec && a.cnt && a.status, "fm_forecast_portfolio_sort: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = port_lds_bytes(a.max_seg_len);
+    int rc;
+    if (a.max_seg_len <= 256 * 4) rc = pl ? launch_fport<256, 4, true>(a, lds, st) : launch_fport<256, 4, false>(a, lds, st);
+    else if (a.max_seg_len <= 512 * 10) rc = pl ? launch_fport<512, 10, true>(a, lds, st) : launch_fport<512, 10, false>(a, lds, st);
+    else rc = pl ? launch_fport<1024, 16, true>(a, lds, st) : launch_fport<1024, 16, false>(a, lds, st);
+    if (rc != FM_OK) return rc;
+    FM_CHECK_LAUNCH("fm_forecast_portfolio_sort");
     return FM_OK;
 }

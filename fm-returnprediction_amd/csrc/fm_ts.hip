@@ -564,8 +564,56 @@ __global__ __launch_bounds__(TT) void forecast_kernel(const double* cols, int64_
     }
 }
 
+// The lagged coefficient tables of fm_forecast_portfolio_sort: thread (j, t) looks month t up
+// in problem p_j's ascending fitted-month list (binary search) and copies the rolling row `lag`
+// fitted months before it, or writes NaN -- every output is written exactly once.
+__global__ __launch_bounds__(TT) void lagged_coef_kernel(const double* __restrict__ roll,
+                                                         const int32_t* __restrict__ idx,
+                                                         const int32_t* __restrict__ count, int nseg,
+                                                         int nprob, int pmax,
+                                                         const int32_t* __restrict__ problems, int lag,
+                                                         double* __restrict__ out) {
+    const int j = blockIdx.y, t = blockIdx.x * TT + threadIdx.x;
+    if (t >= nseg) return;
+    const int p = problems[j];
+    int i = -1;   // the fitted-month row of month t, -1: not fitted
+    if (p >= 0 && p < nprob) {
+        const int32_t* ix = idx + (int64_t)p * nseg;
+        int cnt = count[p];
+        cnt = cnt < 0 ? 0 : (cnt > nseg ? nseg : cnt);
+        int lo = 0, hi = cnt;   // first row with ix[row] >= t
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ix[mid] < t) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < cnt && ix[lo] == t) i = lo;
+    }
+    double* o = out + ((int64_t)j * nseg + t) * pmax;
+    if (i >= lag) {
+        const double* c = roll + ((int64_t)p * nseg + (i - lag)) * pmax;
+        for (int k = 0; k < pmax; ++k) o[k] = c[k];
+    } else {
+        for (int k = 0; k < pmax; ++k) o[k] = NAN;
+    }
+}
+
 }  // namespace
 }  // namespace fm
+
+extern "C" int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count, int32_t nseg,
+                              int32_t nprob, int32_t pmax, const int32_t* problems, int32_t nsel, int32_t lag,
+                              double* out, void* stream) {
+    using namespace fm;
+    FM_REQUIRE(nseg >= 0 && nprob >= 0 && nsel >= 0 && nsel <= 65535 && pmax >= 1 && lag >= 0,
+               "fm_lagged_coef: bad sizes");
+    if (nseg == 0 || nsel == 0) return FM_OK;
+    FM_REQUIRE(roll && idx && count && problems && out, "fm_lagged_coef: null pointer");
+    hipLaunchKernelGGL(lagged_coef_kernel, dim3((nseg + TT - 1) / TT, nsel), dim3(TT), 0, (hipStream_t)stream,
+                       roll, idx, count, nseg, nprob, pmax, problems, lag, out);
+    FM_CHECK_LAUNCH("fm_lagged_coef");
+    return FM_OK;
+}
 
 extern "C" int fm_forecast(const double* cols, int64_t col_stride, int32_t K,
                            const int64_t* seg_off, int32_t nseg, int64_t nrows, const double* coef,

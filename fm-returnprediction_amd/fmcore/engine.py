@@ -1154,6 +1154,8 @@ class Portfolios:
     rec: torch.Tensor      # [T, nport+1, 4] float64: ew ret, ew forecast, vw ret, vw forecast; last = H-L
     cnt: torch.Tensor      # [T, nport] int32 rows with a finite return
     status: torch.Tensor   # [T] int32: 1 = sorted month
+    forecast: Optional[torch.Tensor] = None   # [nsel, rows] float64 (forecast_portfolio_sort, on request)
+    # forecast_portfolio_sort returns every tensor with a leading [nsel] dimension
 
 
 def _row_vector(t, dtype, n, dev, what):
@@ -1209,10 +1211,123 @@ def portfolio_sort(seg_off, forecast, ret, weight=None, level=None, nyse=None, n
     return out
 
 
+def lagged_coefficients(roll, ix: TSIndex, problems, lag=1):
+    """The coefficient tables [nsel, T, pmax] of ``forecast_portfolio_sort`` from the time-series
+    stage's outputs (``roll`` [P, T, pmax], ``ix``), without a host sync on the fitted-month
+    counts (fm_lagged_coef): for problem p = problems[j], month ``ix.idx[p, i]`` of the fitted
+    rows i in [lag, count[p]) gets ``roll[p, i - lag]`` -- the row fm_predictive reads for that
+    month -- and every other month NaN."""
+    P, T, pmax = roll.shape
+    problems = tuple(int(p) for p in problems)
+    if any(p < 0 or p >= P for p in problems):
+        raise ValueError(f"lagged_coefficients: problems must lie in 0..{P - 1}")
+    if lag < 0:
+        raise ValueError("lagged_coefficients: lag must be >= 0")
+    roll = roll.contiguous()
+    dev = roll.device
+    out = torch.empty((len(problems), T, pmax), dtype=torch.float64, device=dev)
+    if not problems or T == 0:
+        return out
+    pj = _small_tensor(problems, torch.int32, dev)
+    idx, cnt = ix.idx.contiguous(), ix.count.contiguous()
+    _kcall("fm_lagged_coef", "fm_lagged_coef", roll.data_ptr(), idx.data_ptr(), cnt.data_ptr(), T, P, pmax,
+           pj.data_ptr(), len(problems), int(lag), out.data_ptr(), _stream())
+    return out
+
+
+def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, ret="retx", weight=None, level=None,
+                            nyse=None, nport=10, q=None, nyse_breakpoints=False, min_count=None,
+                            forecast_out=False, out: "Portfolios" = None):
+    """A12 fused with its forecast: for every sort j of ``sel`` = [(xs, min_level), ...] (``xs`` the
+    predictors' panel columns, names or indices, in coefficient order) and every month t, each row's
+    F = c0 + sum_k c_k clip(x_k) with c = ``coef[j, t]`` ([nsel, T, >= K+1], e.g. from
+    ``lagged_coefficients``) and the ``cuts`` (None: no clipping) is computed inside the sort
+    kernel's load phase, from whichever layout the panel holds (FP64 columns, else its planes; no
+    merged copy, no clipped panel, no forecast vector), then sorted as ``portfolio_sort`` sorts
+    with the panel column ``ret`` as the realised return (fm_forecast_portfolio_sort; the
+    definition is in fm_hip.h).  One launch per FM_MAX_SORTS sorts.  Returns ``Portfolios`` whose
+    tensors carry a leading [nsel] dimension; ``forecast_out``: also the forecasts [nsel, rows];
+    ``out``: a ``Portfolios`` of that shape to write into (else allocated)."""
+    src = _source(panel)
+    dev = src.device
+    n, T, C = panel.nrows, panel.nseg, src.ncols
+    nsel = len(sel)
+
+    def col(c):
+        return panel.col(c) if isinstance(c, str) else int(c)
+
+    sel = [([col(c) for c in xs], int(lv)) for xs, lv in sel]
+    coef = coef.contiguous()
+    if coef.dtype != torch.float64 or coef.dim() != 3 or coef.shape[0] != nsel or coef.shape[1] != T or \
+            coef.device != dev:
+        raise ValueError(f"forecast_portfolio_sort: coef must be a float64 [{nsel}, {T}, >= K+1] tensor on {dev}")
+    weight = _row_vector(weight, torch.float64, n, dev, "weight")
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    nyse = _row_vector(nyse, torch.uint8, n, dev, "nyse")
+    lo = hi = None
+    if cuts is not None:
+        lo, hi = cuts.lo.contiguous(), cuts.hi.contiguous()
+        if tuple(lo.shape) != (C, T) or tuple(hi.shape) != (C, T):
+            raise ValueError(f"forecast_portfolio_sort: the cuts must be [{C}, {T}] tables")
+    nport = int(nport)
+    qs = list(q) if q is not None else [k / nport for k in range(1, max(nport, 1))]
+    if q is not None and len(qs) != nport - 1:
+        raise ValueError(f"forecast_portfolio_sort: q must hold nport - 1 = {nport - 1} levels, got {len(qs)}")
+    np_ = min(max(nport, 2), L.FM_MAX_PORTS)   # output shapes of a call the library will refuse
+    shapes = dict(bp=((nsel, T, np_ - 1), torch.float64), port=((nsel, n), torch.uint8),
+                  rec=((nsel, T, np_ + 1, 4), torch.float64), cnt=((nsel, T, np_), torch.int32),
+                  status=((nsel, T), torch.int32))
+    if forecast_out:
+        shapes["forecast"] = ((nsel, n), torch.float64)
+    if out is None:
+        out = Portfolios(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    for k, (sh, dt) in shapes.items():
+        t = getattr(out, k)
+        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"forecast_portfolio_sort: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+    # FP64 columns if the panel has them, else its planes: exactly one layout goes to the kernel
+    f64 = src.f64 is not None
+    for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
+        part = sel[j0:j0 + L.FM_MAX_SORTS]
+        a = L.FPortArgs()
+        if f64:
+            a.cols, a.col_stride = src.ptr, src.stride
+        else:
+            a.hi_plane, a.lo_plane, a.plane_stride = src.hp, src.lp, src.pstride
+        a.ncols, a.ret_col = C, col(ret)
+        a.lo, a.hi = _ptr(lo), _ptr(hi)
+        a.weight, a.level, a.nyse = _ptr(weight), _ptr(level), _ptr(nyse)
+        a.seg_off, a.nrows, a.nseg, a.max_seg_len = panel.seg_off.data_ptr(), n, T, panel.max_seg_len
+        a.nport, a.nyse_breakpoints = nport, int(bool(nyse_breakpoints))
+        a.min_count = nport if min_count is None else int(min_count)
+        a.nsel = len(part)
+        for k, v in enumerate(qs[:L.FM_MAX_PORTS - 1]):
+            a.q[k] = float(v)
+        for j, (xs, lv) in enumerate(part):
+            a.sel_k[j], a.sel_level[j] = len(xs), lv
+            for k, c in enumerate(xs[:L.FM_MAX_SORT_K]):
+                a.sel_cols[j][k] = c
+        a.coef, a.coef_stride = coef[j0:].data_ptr() if nsel else None, coef.stride(1)
+        if nsel:
+            a.bp, a.port, a.rec = out.bp[j0:].data_ptr(), out.port[j0:].data_ptr(), out.rec[j0:].data_ptr()
+            a.cnt, a.status = out.cnt[j0:].data_ptr(), out.status[j0:].data_ptr()
+            a.forecast_out = out.forecast[j0:].data_ptr() if forecast_out else None
+        _kcall("fm_forecast_portfolio_sort", "fm_forecast_portfolio_sort", L.C.byref(a), _stream())
+        _remember("fm_forecast_portfolio_sort", "fm_forecast_portfolio_sort", a, src, panel.planes, panel.seg_off,
+                  coef, lo, hi, weight, level, nyse, out)
+    return out
+
+
 def portfolio_summary(p: Portfolios, nw_lags=4):
     """FM mean, Newey-West s.e., t and nobs of the (nport+1) * 4 monthly series of ``p.rec`` over
     the sorted months (status 1), NaN entries dropped per series -> ``Summary`` with
-    [nport+1, 4] tensors."""
+    [nport+1, 4] tensors; for the batched ``Portfolios`` of ``forecast_portfolio_sort`` every sort
+    is one problem of the same two launches, and the tensors are [nsel, nport+1, 4]."""
+    if p.rec.dim() == 4:
+        S, T, n1, k = p.rec.shape
+        ix = ts_compact(p.status, 1, T, T, S)
+        s = ts_summary(p.rec, n1 * k, T * n1 * k, ix, T, S, n1 * k, nw_lags)
+        return Summary(s.mean.view(S, n1, k), s.se.view(S, n1, k), s.tstat.view(S, n1, k), s.nobs.view(S, n1, k))
     T, n1, k = p.rec.shape
     ix = ts_compact(p.status.view(T, 1), 1, 1, T, 1)
     s = ts_summary(p.rec, n1 * k, n1 * k, ix, T, 1, n1 * k, nw_lags)

@@ -7,12 +7,14 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
  -> Fama-MacBeth means + Newey-West(4) t-stats (src/regressions.py:102-131)
  -> 120-month rolling coefficient means (:926)
  -> lagged-rolling forecasts and predictive-slope FM summaries (build-defined A7/A8)
+ -> optionally (``PipelineConfig.portfolios``) the forecast-sorted portfolios of every Table-2
+    problem (paper Table 5, build-defined A12) in one more launch that forecasts and sorts
 All stages are libfm_hip kernels; the panel is read from HBM twice (cuts, Gram).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -72,6 +74,17 @@ class PipelineConfig:
     lag: int = 1
     forecasts: bool = True
     fig1: bool = True
+    # A12 inside the pipeline (paper Table 5): the number of portfolios, None = off (the pipeline
+    # then issues exactly the launches it issues without these fields).  Every problem of the
+    # Table-2 models (not Figure 1) is sorted each month on F = a + b'clip(x) with that problem's
+    # lagged rolling coefficients -- the row its predictive record reads -- over its own universe.
+    # Needs forecasts=True (the rolling means and the lag come from that stage) and excludes
+    # standardize=True (coefficients on z-scores need the moment tables): ValueError otherwise.
+    # Keyword-only, so that the positional order of the fields above and of ``rank`` (pinned as
+    # the trailing field by tests/test_rank_host.py) stays what it was.
+    portfolios: Optional[int] = field(default=None, kw_only=True)
+    portfolio_q: Optional[Sequence[float]] = field(default=None, kw_only=True)   # nport - 1 levels (None: k / nport)
+    portfolio_nyse_breakpoints: bool = field(default=False, kw_only=True)        # breakpoints from the NYSE rows only
     rank: Optional[str] = None     # A13: predictors -> per-month ranks, a scale name ("raw", "pct", "uniform")
 
 
@@ -89,6 +102,9 @@ class PipelineResult:
     cuts: Optional[E.Cuts] = None
     level: Optional[torch.Tensor] = None
     breakpoints: Optional[tuple] = None
+    portfolios: Optional[E.Portfolios] = None        # cfg.portfolios: tensors with a leading [nsort] dimension
+    portfolio_summary: Optional[E.Summary] = None    # [nsort, nport+1, 4]
+    portfolio_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
 
 
 def build_models(panel: E.DevicePanel, model_cols: Dict[str, List[str]], y="retx", fig1=True,
@@ -122,6 +138,11 @@ def _standardize_params(panel: E.DevicePanel, cuts: E.Cuts, yi: int):
 
 def local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx"):
     """Panel-sized work for one shard of months: cuts, universes, batched Gram + solve."""
+    return _local_stage(panel, cfg, model_cols, y)[:5]
+
+
+def _local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx"):
+    """local_stage, plus the panel the Gram read (the ranked one under cfg.rank) and the models."""
     cuts = None
     shift = None
     inv_scale = None
@@ -172,7 +193,7 @@ def local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx")
                     moments=cfg.forecasts)
     if cfg.standardize:
         E.drop_degenerate_months(res, models, cuts.sd)
-    return res, names, cuts, level, bp
+    return res, names, cuts, level, bp, panel, models
 
 
 def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo=0, seg_hi=None,
@@ -191,14 +212,32 @@ def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo
 def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=None, y="retx"):
     cfg = cfg or PipelineConfig()
     model_cols = model_cols or table2_models()
-    res, names, cuts, level, bp = local_stage(panel, cfg, model_cols, y)
+    if cfg.portfolios is not None:
+        if cfg.standardize:
+            raise ValueError("PipelineConfig: portfolios excludes standardize (coefficients on z-scores "
+                             "need the moment tables)")
+        if not cfg.forecasts:
+            raise ValueError("PipelineConfig: portfolios needs forecasts=True (the lagged rolling coefficients)")
+    res, names, cuts, level, bp, gpanel, models = _local_stage(panel, cfg, model_cols, y)
     ix, summ, roll, pred, pst = time_series_stage(res, cfg)
     psumm = None
     if cfg.forecasts:
         psumm, _ = E.summarize_predictive(pred, pst, cfg.nw_lags)
+    ports = port_summ = port_probs = None
+    if cfg.portfolios is not None:
+        # Table 5: every Table-2 problem's sort, forecast and all, in one launch on the panel the
+        # Gram read, with the pipeline's cuts and the coefficient rows the predictive stage read
+        port_probs = [k for k, p in enumerate(res.problems) if names[p.model] != "Figure 1"]
+        coef = E.lagged_coefficients(roll, ix, port_probs, cfg.lag)
+        sel = [(models[res.problems[k].model].xs, res.problems[k].level) for k in port_probs]
+        ports = E.forecast_portfolio_sort(gpanel, coef, sel, cuts=cuts, ret=gpanel.col(y), weight=gpanel.me,
+                                          level=level, nyse=gpanel.nyse, nport=cfg.portfolios, q=cfg.portfolio_q,
+                                          nyse_breakpoints=cfg.portfolio_nyse_breakpoints)
+        port_summ = E.portfolio_summary(ports, cfg.nw_lags)
     return PipelineResult(model_names=names, model_cols=dict(model_cols, **({"Figure 1": FIG1_VARS} if cfg.fig1 else {})),
                           res=res, ix=ix, summary=summ, rolling=roll, pred=pred, pred_status=pst,
-                          pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp)
+                          pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
+                          portfolio_summary=port_summ, portfolio_problems=port_probs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

@@ -697,25 +697,28 @@ def forecast_sorted_portfolios(df: pd.DataFrame, forecast, return_col: str = "re
                           nport=nport, q=breakpoints, min_level=_UNIVERSE_LEVEL[universe],
                           nyse_breakpoints=nyse_breakpoints, max_seg_len=panel.max_seg_len)
     s = _E.portfolio_summary(p, nw_lags)
+    return _portfolio_frames(p.status.cpu().numpy(), p.rec.cpu().numpy(), p.cnt.cpu().numpy(), s.mean.cpu().numpy(),
+                             s.tstat.cpu().numpy(), s.nobs.cpu().numpy(), panel.months, nport, date_col)
+
+
+def _portfolio_frames(status, rec, cnt, mean, tstat, nobs, months, nport, date_col="mthcaldt"):
+    """forecast_sorted_portfolios' (monthly, summary) frames of one sort's host arrays."""
     labels = list(range(nport)) + ["H-L"]
-    srt = p.status.cpu().numpy() == 1
-    rec = p.rec.cpu().numpy()[srt]
-    cnt = p.cnt.cpu().numpy()[srt].astype(np.int64)
+    srt = status == 1
+    rec = rec[srt]
+    cnt = cnt[srt].astype(np.int64)
     n = np.concatenate([cnt, cnt[:, :1] + cnt[:, -1:]], axis=1)
-    index = pd.MultiIndex.from_product([np.asarray(panel.months)[srt], labels], names=[date_col, "portfolio"])
+    index = pd.MultiIndex.from_product([np.asarray(months)[srt], labels], names=[date_col, "portfolio"])
     monthly = pd.DataFrame(rec.reshape(-1, 4), index=index, columns=PORTFOLIO_COLUMNS)
     monthly["n"] = n.reshape(-1)
-    mean, tstat, nobs = s.mean.cpu().numpy(), s.tstat.cpu().numpy(), s.nobs.cpu().numpy()
     summary = pd.DataFrame({(c, stat): v[:, j] for j, c in enumerate(PORTFOLIO_COLUMNS)
                             for stat, v in (("mean", mean), ("tstat", tstat), ("nobs", nobs))},
                            index=pd.Index(labels, name="portfolio"))
     return monthly, summary
 
 
-def lewellen_pipeline(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):
-    """The whole Table-2 / Figure-1 / forecast pass device-resident from one frame
-    (winsorize -> universes -> 3 models x 3 universes + Figure 1 -> NW -> rolling ->
-    predictive slopes).  Returns fmcore.lewellen.PipelineResult (device tensors)."""
+def _pipeline_panel(crsp_comp: pd.DataFrame, variables_dict: dict = None):
+    """The device panel and the Table-2 models of a crsp_comp frame (rows by (month, permno))."""
     vd = variables_dict or _LW.VARIABLES_DICT
     model_cols = _LW.table2_models(vd)
     cols = list(dict.fromkeys(["retx"] + [c for xs in model_cols.values() for c in xs] + _LW.FIG1_VARS))
@@ -724,4 +727,36 @@ def lewellen_pipeline(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cf
     nyse = (df["primaryexch"] == "N").to_numpy().astype(np.uint8)
     panel = _E.panel_from_arrays([_api.as_f64(df[c]) for c in cols], cols, df["mthcaldt"].values,
                                  me=me, nyse=nyse)
+    return panel, model_cols
+
+
+def lewellen_pipeline(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):
+    """The whole Table-2 / Figure-1 / forecast pass device-resident from one frame
+    (winsorize -> universes -> 3 models x 3 universes + Figure 1 -> NW -> rolling ->
+    predictive slopes; with ``portfolios=nport`` also the forecast-sorted portfolios of every
+    Table-2 problem).  Returns fmcore.lewellen.PipelineResult (device tensors)."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
     return _LW.run_pipeline(panel, _LW.PipelineConfig(**cfg), model_cols=model_cols)
+
+
+def build_table_5(crsp_comp: pd.DataFrame, variables_dict: dict = None, nport: int = 10,
+                  nyse_breakpoints: bool = False, **cfg):
+    """Paper Table 5 from ONE device pipeline run (build-defined; no reference line): for every
+    Table-2 model and universe, the stocks sorted each month into ``nport`` portfolios on the
+    out-of-sample forecast from that problem's lagged rolling coefficients and the winsorized
+    characteristics, value weights from ``me`` -- what monthly_coefficients ->
+    rolling_coefficients -> expected_return_forecasts -> forecast_sorted_portfolios give per
+    (model, universe), without their uploads and refits.  ``cfg``: further PipelineConfig
+    fields (window, min_periods, lag, nw_lags, ...).  Returns {(model name, universe name):
+    (monthly, summary)} in forecast_sorted_portfolios' frame format."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    pcfg = _LW.PipelineConfig(**dict(cfg, portfolios=int(nport), portfolio_nyse_breakpoints=bool(nyse_breakpoints)))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    p, s = out.portfolios, out.portfolio_summary
+    host = [t.cpu().numpy() for t in (p.status, p.rec, p.cnt, s.mean, s.tstat, s.nobs)]
+    frames = {}
+    for j, k in enumerate(out.portfolio_problems):
+        prob = out.res.problems[k]
+        key = (out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level])
+        frames[key] = _portfolio_frames(*(h[j] for h in host), panel.months, int(nport))
+    return frames

@@ -44,6 +44,9 @@
  *   fm_forecast     <- build-defined extension A7: per-row F = a_{t-1} + b_{t-1}'x_t
  *   fm_portfolio_sort <- build-defined extension: forecast-sorted portfolios, paper Table 5;
  *                      no reference line
+ *   fm_forecast_portfolio_sort, fm_lagged_coef <- build-defined extension: the same sorts with
+ *                      the clipped lagged-rolling forecast computed in the sort kernel's load
+ *                      phase (Table 5 inside the device pipeline); no reference line
  *   fm_rank_transform <- build-defined extension A13: per-month cross-sectional ranks of the
  *                      characteristics (pandas groupby(month)[x].rank); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
@@ -191,7 +194,8 @@ const char* fm_version(void);
 const char* fm_last_error(void);
 int fm_abi_sizes(int32_t* gram_args, int32_t* solve_args);
 /* sizeof the named argument struct ("fm_gram_args", "fm_solve_args", "fm_select_args",
- * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args", "fm_rank_args"); -1 for an unknown name.  Bindings
+ * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args", "fm_rank_args",
+ * "fm_fport_args"); -1 for an unknown name.  Bindings
  * check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
 int fm_device_arch(char* buf, int32_t len);
@@ -451,6 +455,76 @@ typedef struct fm_port_args {
 } fm_port_args;
 
 int fm_portfolio_sort(const fm_port_args* args, void* stream);
+
+/* fm_forecast_portfolio_sort: nsel forecast sorts of one panel in one launch (grid (month,
+ * sort)), each row's forecast computed in the sort kernel's load phase from the panel's own
+ * layout instead of read from a vector (paper Table 5 inside the device pipeline; no reference
+ * line).  Exactly one predictor source: FP64 columns (cols, col_stride) or the split planes
+ * (hi_plane, lo_plane, plane_stride); both or neither: FM_EINVAL.  For sort j (K = sel_k[j] in
+ * 1..FM_MAX_SORT_K predictors, panel columns sel_cols[j][0..K) in coefficient order), month t
+ * with the coefficient row c = coef[(j * nseg + t) * coef_stride + 0..K] (coef_stride >= K + 1)
+ * and row i:
+ *   x'_k = clip(x_k) exactly as fm_clip clips with lo / hi [ncols][nseg] (x < lo -> lo, x > hi
+ *          -> hi; a NaN bound is ignored, a NaN x stays NaN; lo == hi == NULL: no clipping);
+ *   F    = c[0], then for k = 1..K in order F = F + c[k] * x'_k, every product and every sum
+ *          rounded on its own (fm_forecast's bits on the fm_clip-ped columns);
+ *   then fm_portfolio_sort's definition with forecast = F, ret = panel column ret_col (read
+ *   raw, never clipped, from the same layout) and min_level = sel_level[j].
+ * So a NaN in the coefficient row makes every F NaN and the month unsorted, and a NaN or +-inf
+ * predictor makes the row ineligible.  Outputs are fm_port_args' with a leading [nsel]
+ * dimension; forecast_out (optional) receives every row's F.  Months of more than 16,384 rows:
+ * FM_ETOOBIG before any launch, outputs untouched.  nsel == 0 or nseg == 0 is a valid empty
+ * call.  Zero-initialize the struct (it grows at the end). */
+#define FM_MAX_SORTS 16
+#define FM_MAX_SORT_K 30
+typedef struct fm_fport_args {
+    const double* cols;          /* [ncols][col_stride] or NULL (planes) */
+    int64_t col_stride;
+    const uint32_t* hi_plane;    /* [ncols][plane_stride] high / low words, or NULL (cols) */
+    const uint32_t* lo_plane;
+    int64_t plane_stride;
+    int32_t ncols;
+    int32_t ret_col;             /* panel column of the realised return */
+    const double* lo;            /* [ncols][nseg] clip bounds, or both NULL */
+    const double* hi;
+    const double* weight;        /* [rows] or NULL */
+    const uint8_t* level;        /* [rows] universe level or NULL */
+    const uint8_t* nyse;         /* [rows] nonzero = NYSE row, or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int64_t nrows;               /* seg_off[nseg]: the row stride of port / forecast_out */
+    int32_t nseg;
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t nport;               /* 2 .. FM_MAX_PORTS */
+    int32_t nyse_breakpoints;
+    int32_t min_count;           /* >= 1 */
+    int32_t nsel;                /* 0 .. FM_MAX_SORTS */
+    double q[FM_MAX_PORTS - 1];
+    int32_t sel_k[FM_MAX_SORTS];
+    int32_t sel_level[FM_MAX_SORTS];
+    int32_t sel_cols[FM_MAX_SORTS][FM_MAX_SORT_K];
+    const double* coef;          /* [nsel][nseg][coef_stride] */
+    int32_t coef_stride;
+    int32_t pad_fport;
+    double* bp;                  /* [nsel][nseg][nport-1] or NULL */
+    uint8_t* port;               /* [nsel][nrows] or NULL */
+    double* rec;                 /* [nsel][nseg][nport+1][4] */
+    int32_t* cnt;                /* [nsel][nseg][nport] */
+    uint32_t* status;            /* [nsel][nseg] */
+    double* forecast_out;        /* [nsel][nrows] or NULL */
+} fm_fport_args;
+
+int fm_forecast_portfolio_sort(const fm_fport_args* args, void* stream);
+
+/* fm_lagged_coef: the coefficient tables fm_forecast_portfolio_sort reads, from the time-series
+ * stage's outputs without a host sync on the fitted-month counts.  For j < nsel with
+ * p = problems[j] (device int32 [nsel], each in 0..nprob-1): every row out[j][t][0..pmax) is NaN
+ * except, for the fitted-month rows i in [lag, count[p]),
+ *   out[j][idx[p][i]][k] = roll[p][i - lag][k]
+ * -- the row fm_predictive reads for the same month (roll [nprob][nseg][pmax], idx
+ * [nprob][nseg] ascending, count [nprob]; lag >= 0). */
+int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count, int32_t nseg,
+                   int32_t nprob, int32_t pmax, const int32_t* problems, int32_t nsel, int32_t lag,
+                   double* out, void* stream);
 
 /* fm_rank_transform: every chosen column's cross-sectional rank within its month (build-defined
  * extension A13; no reference line).  It is pandas' groupby(month)[x].rank(method, pct) and is
