@@ -18,6 +18,14 @@
 //      whose successor differs has eq = 1), and writes its rank.
 // No (key, row) pairs are sorted: the three methods need the two counts only.  The unit's
 // values are read from HBM once and its ranks written once.
+//
+// Months of more than 16,384 rows (rank_long_kernel): the sorted keys of such a month do not fit
+// one workgroup's LDS, but both counts are sums over any partition of the month's rows, so the
+// month is cut into parts of 16,384 rows and a workgroup per (month, column, part) takes that
+// part's rows as its own slice, sorts one part after another into LDS by phases 1-2 and adds up
+// what phase 3 finds for its own rows' keys in each.  One launch, no workspace, no atomics, and
+// no workgroup reads what another one writes; the price is that every slice's workgroup sorts
+// every part: parts^2 part-sorts per unit, hence the 65,536-row limit.
 #include <math.h>
 
 #include "fm_common.h"
@@ -30,7 +38,8 @@ FM_PROBE_BUFFER(rank)
 namespace fm {
 namespace {
 
-constexpr int RANK_MAX_ROWS = 16384;   // 16 rows per thread of a 1024-thread workgroup
+constexpr int RANK_MAX_ROWS = FM_RANK_MAX_ROWS;   // 4 parts: the long path's cost is quadratic in the part count
+constexpr int RANK_PART = 16384;       // one workgroup's sort: 16 rows per thread of 1024 threads, 128 KB of keys
 constexpr int RANK_SHORT_MAX = 8192;   // months up to here: 8 rows per thread
 
 // ascending compare-exchange of buf[i], buf[l] (i < l)
@@ -187,6 +196,188 @@ __global__ __launch_bounds__(1024) void rank_kernel(fm_rank_args a) {
     FM_PROBE_AT(rank, 3);
 }
 
+// Months of more than RANK_PART rows.  Workgroup (s, c, z) of 1024 threads ranks the slice
+// [z * RANK_PART, (z + 1) * RANK_PART) of month s, column c (its own rows, laid out over the
+// threads as a part's): it visits the month's parts of RANK_PART rows in turn, sorts each into
+// LDS exactly as rank_kernel<16> does and adds its own keys' counts #{part keys < key} and
+// #{part keys <= key} to two per-row sums.  Only the sums stay in registers across a part's
+// sort: the own keys are made again from src for every part (the month's values come from
+// cache after the first read), 8 rows at a time, which is what keeps a 16-row slice within
+// 128 VGPRs.  A key need not occur in the visited part: the lower bound may then be the whole
+// part (the search starts from P2, not P2 / 2), and le = lt there.  L, the part count and every
+// barrier are block-uniform.
+__global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
+    constexpr int R = RANK_PART / 1024;    // rows per thread, of a visited part and of the own slice
+    constexpr int RUN = WAVE * R;
+    constexpr int SG = 8;
+    constexpr int NW = 1024 / WAVE;
+    extern __shared__ uint64_t rbuf[];     // RANK_PART keys
+    __shared__ int s_cnt[NW];
+    const int s = blockIdx.x, c = blockIdx.y;
+    const int own0 = blockIdx.z * RANK_PART;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int64_t r0 = a.seg_off[s];
+    int L = (int)(a.seg_off[s + 1] - r0);
+    L = L < a.max_seg_len ? L : a.max_seg_len;   // the grid's slices were counted from max_seg_len
+    if (own0 >= L) {   // block-uniform: an empty month (slice 0 reports it) or a slice past the month's end
+        if (own0 == 0 && tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = 0;
+        return;
+    }
+    const double* __restrict__ X = a.src + (int64_t)c * a.src_stride + r0;
+    const uint8_t* __restrict__ LV = a.level != nullptr ? a.level + r0 : nullptr;
+    const int last = L - 1;
+    const int min_level = a.min_level;
+    // row idx of the month as a key: SENT if past the end, NaN or outside the universe
+    auto key_of_row = [&](int idx, bool& elig) -> uint64_t {
+        const int ci = idx < L ? idx : last;   // unconditional (clamped) load, masked after
+        const double x = X[ci] + 0.0;          // -0.0 -> +0.0: the two zeros tie
+        const int lv = LV != nullptr ? (int)LV[ci] : 255;
+        elig = idx < L && !isnan(x) && lv >= min_level;
+        return elig ? dkey(x) : SENT;
+    };
+    const bool own_rows = own0 + w * RUN < L;   // wave-uniform: this wave holds rows of the slice
+
+    int lts[R], les[R];   // the own rows' counts over the parts visited so far
+#pragma unroll
+    for (int v = 0; v < R; ++v) lts[v] = les[v] = 0;
+    int n = 0;
+
+    for (int p0 = 0; p0 < L; p0 += RANK_PART) {   // block-uniform
+        const int Lp = L - p0 < RANK_PART ? L - p0 : RANK_PART;
+        const int nrun = (Lp + RUN - 1) / RUN;   // <= NW: waves nrun.. hold no row of this part
+        const int Pact = nrun * RUN;
+        int P2 = RUN;
+        while (P2 < Pact) P2 <<= 1;
+
+        // ---- 1. the part's keys, per-wave sorted runs ----------------------------------------
+        int cnt = 0;
+        if (w < nrun) {   // wave-uniform
+            uint64_t k[R];
+#pragma unroll
+            for (int v = 0; v < R; ++v) {
+                bool elig;
+                k[v] = key_of_row(p0 + (w * R + v) * WAVE + lane, elig);
+                cnt += elig ? 1 : 0;
+            }
+            wave_sort64<R>(k);
+#pragma unroll
+            for (int v = 0; v < R; ++v) rbuf[w * RUN + v * WAVE + lane] = k[v];
+        }
+        cnt = wave_sum(cnt);
+        if (lane == 0) s_cnt[w] = cnt;
+        __syncthreads();
+        for (int q = 0; q < NW; ++q) n += s_cnt[q];
+
+        // ---- 2. merge the runs: rank_kernel's phase 2, repeated here and not shared, since a
+        // common device function changes the register allocation of rank_kernel<8> / <16>,
+        // whose code this path leaves exactly as it was
+        for (int k = 2 * RUN; k <= P2; k <<= 1) {   // block-uniform
+            const int h = k >> 1;
+            for (int t = tid; t < (P2 >> 1); t += 1024) {
+                const int i = ((t & ~(h - 1)) << 1) | (t & (h - 1));
+                const int l = i ^ (k - 1);
+                if (l < Pact) cmpx(rbuf, i, l);
+            }
+            __syncthreads();
+            for (int j = h >> 1; j >= RUN; j >>= 1) {
+                for (int t = tid; t < (P2 >> 1); t += 1024) {
+                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                    const int l = i | j;
+                    if (l < Pact) cmpx(rbuf, i, l);
+                }
+                __syncthreads();
+            }
+            if (w < nrun) {
+                uint64_t m[R];
+#pragma unroll
+                for (int v = 0; v < R; ++v) m[v] = rbuf[w * RUN + v * WAVE + lane];
+                bitonic_u64_stages<R, 2 * RUN, RUN / 2>(m);
+#pragma unroll
+                for (int v = 0; v < R; ++v) rbuf[w * RUN + v * WAVE + lane] = m[v];
+            }
+            __syncthreads();
+        }
+
+        // ---- 3. the own keys' two counts in this part ----------------------------------------
+#pragma unroll
+        for (int v0 = 0; v0 < R; v0 += SG) {
+            if (!own_rows) break;   // wave-uniform; no barrier below
+            // the own keys are loop-invariant; an opaque base keeps the compiler from hoisting
+            // their loads out of the part loop, which would hold all 16 in registers again
+            int ob = own0;
+            asm volatile("" : "+s"(ob));
+            uint64_t key[SG];
+            int lt[SG], le[SG];
+#pragma unroll
+            for (int u = 0; u < SG; ++u) {
+                bool elig;
+                key[u] = key_of_row(ob + (w * R + v0 + u) * WAVE + lane, elig);
+                lt[u] = 0;
+            }
+            for (int step = P2; step > 0; step >>= 1) {   // from P2: every key of the part may be smaller
+#pragma unroll
+                for (int u = 0; u < SG; ++u) {
+                    const int pa = lt[u] + step - 1;
+                    const uint64_t xa = rbuf[pa < Pact ? pa : Pact - 1];
+                    lt[u] += (pa < Pact && xa < key[u]) ? step : 0;
+                }
+            }
+            // position lt holds the key if the part has it at all (else le = lt); its run of
+            // equals ends at lt + 1 unless the successor equals it too: only a wave that holds
+            // such a key among these rows runs the upper bound search (the same counts either way)
+            bool tied = false;
+#pragma unroll
+            for (int u = 0; u < SG; ++u) {
+                const int pc = lt[u], pn = lt[u] + 1;
+                const uint64_t xc = rbuf[pc < Pact ? pc : Pact - 1];
+                const uint64_t xn = rbuf[pn < Pact ? pn : Pact - 1];
+                tied |= pn < Pact && xn == key[u] && key[u] != SENT;
+                le[u] = lt[u] + ((pc < Pact && xc == key[u]) ? 1 : 0);
+            }
+            if (__ballot(tied) != 0ull) {   // wave-uniform
+#pragma unroll
+                for (int u = 0; u < SG; ++u) le[u] = 0;
+                for (int step = P2; step > 0; step >>= 1) {
+#pragma unroll
+                    for (int u = 0; u < SG; ++u) {
+                        const int pb = le[u] + step - 1;
+                        const uint64_t xb = rbuf[pb < Pact ? pb : Pact - 1];
+                        le[u] += (pb < Pact && xb <= key[u]) ? step : 0;
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SG; ++u) {
+                lts[v0 + u] += lt[u];
+                les[v0 + u] += le[u];
+            }
+        }
+        __syncthreads();   // the next part overwrites rbuf and s_cnt
+    }
+
+    // ---- ranks of the own slice ------------------------------------------------------------------
+    if (blockIdx.z == 0 && tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = n;
+    double* __restrict__ D = a.dst + (int64_t)c * a.dst_stride + r0;
+    const double dn = (double)n, dn1 = (double)(n + 1);
+    const int method = a.method, scale = a.scale;
+#pragma unroll
+    for (int v = 0; v < R; ++v) {
+        if (!own_rows) break;
+        const int idx = own0 + (w * R + v) * WAVE + lane;
+        bool elig;
+        key_of_row(idx, elig);
+        double r;   // a multiple of 0.5 below 2^17: exact
+        if (method == FM_RANK_MIN) r = (double)(lts[v] + 1);
+        else if (method == FM_RANK_MAX) r = (double)les[v];
+        else r = 0.5 * (double)(lts[v] + les[v] + 1);
+        double y = r;
+        if (scale == FM_RANK_PCT) y = r / dn;
+        else if (scale == FM_RANK_UNIFORM) y = r / dn1 - 0.5;
+        if (idx < L) D[idx] = elig ? y : NAN;
+    }
+}
+
 template <int R>
 int launch_rank(const fm_rank_args& a, hipStream_t st) {
     const int nw = (a.max_seg_len + WAVE * R - 1) / (WAVE * R);
@@ -203,6 +394,21 @@ int launch_rank(const fm_rank_args& a, hipStream_t st) {
         }
     }
     hipLaunchKernelGGL((rank_kernel<R>), dim3(a.nseg, a.ncols), dim3(nw * WAVE), lds, st, a);
+    return FM_OK;
+}
+
+int launch_rank_long(const fm_rank_args& a, hipStream_t st) {
+    static bool attr_set = false;
+    if (!attr_set) {   // 128 KB of dynamic LDS: opt in (once)
+        if (hipFuncSetAttribute((const void*)rank_long_kernel,hipFuncAttributeMaxDynamicSharedMemorySize,
+                                8 * RANK_PART) != hipSuccess) {
+            set_error("fm_rank_transform: cannot raise the dynamic LDS limit");
+            return FM_EHIP;
+        }
+        attr_set = true;
+    }
+    const int nslice = (a.max_seg_len + RANK_PART - 1) / RANK_PART;
+    hipLaunchKernelGGL(rank_long_kernel, dim3(a.nseg, a.ncols, nslice), dim3(1024), 8 * (size_t)RANK_PART, st, a);
     return FM_OK;
 }
 
@@ -233,7 +439,9 @@ extern "C" int fm_rank_transform(const fm_rank_args* args, void* stream) {
     FM_REQUIRE(a.src && a.dst && a.seg_off, "fm_rank_transform: null pointer");
     FM_REQUIRE(a.src_stride >= 0 && a.dst_stride >= 0, "fm_rank_transform: bad strides");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = a.max_seg_len <= RANK_SHORT_MAX ? launch_rank<8>(a, st) : launch_rank<16>(a, st);
+    const int rc = a.max_seg_len <= RANK_SHORT_MAX ? launch_rank<8>(a, st)
+                   : a.max_seg_len <= RANK_PART    ? launch_rank<16>(a, st)
+                                                   : launch_rank_long(a, st);
     if (rc != FM_OK) return rc;
     FM_CHECK_LAUNCH("fm_rank_transform");
     return FM_OK;

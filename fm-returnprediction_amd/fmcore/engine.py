@@ -1334,7 +1334,10 @@ def portfolio_summary(p: Portfolios, nw_lags=4):
     return Summary(s.mean.view(n1, k), s.se.view(n1, k), s.tstat.view(n1, k), s.nobs.view(n1, k))
 
 
-RANK_MAX_ROWS = 16384   # fm_rank_transform's month limit (one workgroup per (month, column), keys in LDS)
+# fm_rank_transform's month limit (FM_RANK_MAX_ROWS): up to 16,384 rows one workgroup per (month,
+# column) sorts the month's keys in LDS; a longer month is ranked in parts of 16,384 rows, at a cost
+# quadratic in the part count, so four parts are the limit
+RANK_MAX_ROWS = 65536
 RANK_METHODS = {"average": L.FM_RANK_AVERAGE, "min": L.FM_RANK_MIN, "max": L.FM_RANK_MAX}
 RANK_SCALES = {"raw": L.FM_RANK_RAW, "pct": L.FM_RANK_PCT, "uniform": L.FM_RANK_UNIFORM}
 

@@ -142,7 +142,9 @@ def rank_transform(crsp_comp: pd.DataFrame, varlist: list, date_col: str = "mthc
     "uniform", bit for bit, on the device (fm_rank_transform).  ``method`` in {"average", "min",
     "max"}.  ``universe`` in {None, "all_but_tiny", "large"} ranks within that get_subsets
     universe (from ``me`` and ``primaryexch``) and gives NaN outside it.  Returns a copy of the
-    frame in the caller's row order; rows with a missing month label get NaN."""
+    frame in the caller's row order; rows with a missing month label get NaN.  A month may
+    hold up to 65,536 rows (``FMError`` beyond that); a frame whose longest month has more than
+    16,384 rows is ranked by a slower kernel that visits such a month in 16,384-row parts."""
     if universe not in _UNIVERSE_LEVEL:
         raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
     df = crsp_comp.copy()

@@ -529,7 +529,8 @@ int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count,
 /* fm_rank_transform: every chosen column's cross-sectional rank within its month (build-defined
  * extension A13; no reference line).  It is pandas' groupby(month)[x].rank(method, pct) and is
  * pinned to it bit for bit.  Rows sorted by (month, permno), months seg_off[nseg+1] of at most
- * 16,384 rows (longer: FM_ETOOBIG before any launch).  Per column and month:
+ * FM_RANK_MAX_ROWS = 65,536 rows (longer: FM_ETOOBIG before any launch, outputs untouched).  Per
+ * column and month:
  *   eligible rows: the value is not NaN and, with level given, level >= min_level;
  *   order:         +-inf are ordinary values; -0.0 and +0.0 are equal;
  *   counts:        n = the month's eligible rows; for an eligible row, less = the eligible rows
@@ -543,7 +544,16 @@ int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count,
  * the same bits.  dst == src is refused (FM_EINVAL).  pandas' methods "first" and "dense" are
  * out of scope: the three methods above need only the two counts of a row's key, which a sort
  * of the keys alone gives; "first" needs a stable (key, row) sort and "dense" a distinct count.
+ * Cost and the limit: with max_seg_len <= 16,384 one workgroup sorts a month's keys in LDS.  A
+ * longer max_seg_len takes another kernel for every month of the call: less, less + eq and n
+ * are sums over any partition of the month's eligible rows, so the month is visited in parts
+ * of 16,384 rows and one workgroup per part sorts every part in turn and sums the counts of its
+ * own rows' keys over them (one launch, no workspace, no atomics; same bits).  That is parts^2
+ * part-sorts per (column, month): quadratic in the length, which is why the limit is 4 parts
+ * and not any length -- past that a global segmented sort is the right tool.  Keep months of up
+ * to 16,384 rows in calls of their own where that is possible.
  * Zero-initialize the struct (it grows at the end). */
+#define FM_RANK_MAX_ROWS 65536
 #define FM_RANK_AVERAGE 0
 #define FM_RANK_MIN 1
 #define FM_RANK_MAX 2
@@ -558,7 +568,7 @@ typedef struct fm_rank_args {
     int32_t ncols;
     int32_t nseg;
     const int64_t* seg_off;      /* [nseg+1] */
-    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t max_seg_len;         /* >= every month's rows, <= FM_RANK_MAX_ROWS; chooses the kernel */
     int32_t min_level;
     const uint8_t* level;        /* [rows] universe level or NULL (every row) */
     int32_t method;              /* FM_RANK_AVERAGE / MIN / MAX */
