@@ -520,12 +520,7 @@ extern "C" int fm_rolling_std(const int64_t* ids, const double* x, int64_t n, in
     FM_REQUIRE(lds <= 160 * 1024, "fm_rolling_std: window too large for LDS");
     const int64_t blocks = (n + ST_ROWS - 1) / ST_ROWS;
     FM_REQUIRE(blocks < (1ll << 31), "fm_rolling_std: too many rows");
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)rolling_std_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-        set_error("fm_rolling_std: cannot raise the dynamic LDS limit to %zu bytes", lds);
-        return FM_EHIP;
-    }
+    if (lds > 64 * 1024 && raise_dynamic_lds<rolling_std_kernel>(160 * 1024, "fm_rolling_std") != FM_OK) return FM_EHIP;
     hipLaunchKernelGGL(rolling_std_kernel, dim3((unsigned)blocks), dim3(ST_T), lds, (hipStream_t)stream, ids,
                        x, n, (int)window, (int)min_periods, scale, out);
     FM_CHECK_LAUNCH("fm_rolling_std");

@@ -27,6 +27,22 @@ int check_launch(const char* what);
         if (rc_ != FM_OK) return rc_;               \
     } while (0)
 
+// Lets Kernel take up to max_bytes of dynamic LDS (launches beyond the default 64 KB need the
+// opt-in): one hipFuncSetAttribute per kernel and process, nothing on later calls.
+template <auto Kernel>
+int raise_dynamic_lds(size_t max_bytes, const char* who) {
+    static bool done = false;
+    if (!done) {
+        if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes) !=
+            hipSuccess) {
+            set_error("%s: cannot raise the dynamic LDS limit to %zu bytes", who, max_bytes);
+            return FM_EHIP;
+        }
+        done = true;
+    }
+    return FM_OK;
+}
+
 constexpr uint64_t SENT = ~0ull;   // key of NaN / absent values: sorts after +inf
 constexpr int WAVE = 64;
 

@@ -497,40 +497,6 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(A a) {
     if (tid == 0) a.status[so] = 1u;
 }
 
-template <int NT, int VPT>
-int launch_port(const fm_port_args& a, size_t lds, hipStream_t st) {
-    if (lds >= 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in (once)
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)port_kernel<NT, VPT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    8 * pow2_ceil(NT * VPT)) != hipSuccess) {
-                set_error("fm_portfolio_sort: cannot raise the dynamic LDS limit");
-                return FM_EHIP;
-            }
-            attr_set = true;
-        }
-    }
-    hipLaunchKernelGGL((port_kernel<NT, VPT>), dim3(a.nseg), dim3(NT), lds, st, a);
-    return FM_OK;
-}
-
-template <int NT, int VPT, bool PL>
-int launch_fport(const fm_fport_args& a, size_t lds, hipStream_t st) {
-    if (lds >= 64 * 1024) {   // each instantiation opts in on its own (once)
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)port_kernel<NT, VPT, FusedSrc<PL>, fm_fport_args>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    8 * pow2_ceil(NT * VPT)) != hipSuccess) {
-                set_error("fm_forecast_portfolio_sort: cannot raise the dynamic LDS limit");
-                return FM_EHIP;
-            }
-            attr_set = true;
-        }
-    }
-    hipLaunchKernelGGL((port_kernel<NT, VPT, FusedSrc<PL>, fm_fport_args>), dim3(a.nseg, a.nsel), dim3(NT), lds, st, a);
-    return FM_OK;
-}
-
 // Dynamic LDS of a month of up to max_seg_len rows: the keys of the full sort; months that can
 // reach the sample select hold its tables instead.
 size_t port_lds_bytes(int max_seg_len) {
@@ -538,6 +504,40 @@ size_t port_lds_bytes(int max_seg_len) {
     const size_t fast = 13 * (size_t)(max_seg_len <= 512 * 10 ? 512 : 1024) + (size_t)PSLOTS * PCAP * 8;
     if (max_seg_len > PORT_FAST_MIN && lds < fast) lds = fast;
     return lds;
+}
+
+// The NT x VPT form of entry point `who` over `grid` (each instantiation opts in to its LDS on its own)
+template <int NT, int VPT, class Src, class A>
+int launch(const A& a, dim3 grid, size_t lds, const char* who, hipStream_t st) {
+    if (lds >= 64 * 1024 && raise_dynamic_lds<port_kernel<NT, VPT, Src, A>>(8 * pow2_ceil(NT * VPT), who) != FM_OK) return FM_EHIP;
+    hipLaunchKernelGGL((port_kernel<NT, VPT, Src, A>), grid, dim3(NT), lds, st, a);
+    return check_launch(who);
+}
+
+// The kernel's form by the longest month: f(threads, rows per thread) as compile-time constants
+template <class F>
+int with_form(int max_seg_len, F f) {
+    using std::integral_constant;
+    if (max_seg_len <= 256 * 4) return f(integral_constant<int, 256>{}, integral_constant<int, 4>{});
+    if (max_seg_len <= 512 * 10) return f(integral_constant<int, 512>{}, integral_constant<int, 10>{});
+    return f(integral_constant<int, 1024>{}, integral_constant<int, 16>{});
+}
+
+// What both entry points ask of the arguments they share
+template <class A>
+int check_sort_args(const A& a, const char* who) {
+    FM_REQUIRE(a.nport >= 2 && a.nport <= FM_MAX_PORTS, "%s: nport must be 2..%d", who, FM_MAX_PORTS);
+    for (int j = 0; j < a.nport - 1; ++j) {
+        const double lo = j == 0 ? 0.0 : a.q[j - 1];
+        FM_REQUIRE(a.q[j] > lo && a.q[j] < 1.0, "%s: q must be strictly ascending in (0, 1)", who);
+    }
+    FM_REQUIRE(a.nyse_breakpoints == 0 || a.nyse != nullptr, "%s: nyse_breakpoints needs nyse", who);
+    FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
+    if (a.max_seg_len > PORT_MAX_ROWS) {
+        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
+        return FM_ETOOBIG;
+    }
+    return FM_OK;
 }
 
 }  // namespace
@@ -548,29 +548,15 @@ extern "C" int fm_portfolio_sort(const fm_port_args* args, void* stream) {
     FM_REQUIRE(args != nullptr, "fm_portfolio_sort: null args");
     const fm_port_args& a = *args;
     FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0, "fm_portfolio_sort: bad sizes");
-    FM_REQUIRE(a.nport >= 2 && a.nport <= FM_MAX_PORTS, "fm_portfolio_sort: nport must be 2..%d", FM_MAX_PORTS);
-    for (int j = 0; j < a.nport - 1; ++j) {
-        const double lo = j == 0 ? 0.0 : a.q[j - 1];
-        FM_REQUIRE(a.q[j] > lo && a.q[j] < 1.0, "fm_portfolio_sort: q must be strictly ascending in (0, 1)");
-    }
-    FM_REQUIRE(a.nyse_breakpoints == 0 || a.nyse != nullptr, "fm_portfolio_sort: nyse_breakpoints needs nyse");
-    FM_REQUIRE(a.min_count >= 1, "fm_portfolio_sort: min_count must be >= 1");
     FM_REQUIRE(a.min_level >= 0 && a.min_level <= 255, "fm_portfolio_sort: min_level must be 0..255");
-    if (a.max_seg_len > PORT_MAX_ROWS) {
-        set_error("fm_portfolio_sort: %d-row months exceed %d", a.max_seg_len, PORT_MAX_ROWS);
-        return FM_ETOOBIG;
-    }
+    if (const int rc = check_sort_args(a, "fm_portfolio_sort")) return rc;
     if (a.nseg == 0) return FM_OK;
     FM_REQUIRE(a.forecast && a.ret && a.seg_off && a.rec && a.cnt && a.status, "fm_portfolio_sort: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+    const char* who = "fm_portfolio_sort";
     const size_t lds = port_lds_bytes(a.max_seg_len);
-    int rc;
-    if (a.max_seg_len <= 256 * 4) rc = launch_port<256, 4>(a, lds, st);
-    else if (a.max_seg_len <= 512 * 10) rc = launch_port<512, 10>(a, lds, st);
-    else rc = launch_port<1024, 16>(a, lds, st);
-    if (rc != FM_OK) return rc;
-    FM_CHECK_LAUNCH("fm_portfolio_sort");
-    return FM_OK;
+    return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
+        return launch<nt, vpt, PlainSrc>(a, dim3(a.nseg), lds, who, (hipStream_t)stream);
+    });
 }
 
 extern "C" int fm_forecast_portfolio_sort(const fm_fport_args* args, void* stream) {
@@ -579,17 +565,7 @@ extern "C" int fm_forecast_portfolio_sort(const fm_fport_args* args, void* strea
     const fm_fport_args& a = *args;
     FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0 && a.nrows >= 0, "fm_forecast_portfolio_sort: bad sizes");
     FM_REQUIRE(a.nsel >= 0 && a.nsel <= FM_MAX_SORTS, "fm_forecast_portfolio_sort: nsel must be 0..%d", FM_MAX_SORTS);
-    FM_REQUIRE(a.nport >= 2 && a.nport <= FM_MAX_PORTS, "fm_forecast_portfolio_sort: nport must be 2..%d", FM_MAX_PORTS);
-    for (int j = 0; j < a.nport - 1; ++j) {
-        const double lo = j == 0 ? 0.0 : a.q[j - 1];
-        FM_REQUIRE(a.q[j] > lo && a.q[j] < 1.0, "fm_forecast_portfolio_sort: q must be strictly ascending in (0, 1)");
-    }
-    FM_REQUIRE(a.nyse_breakpoints == 0 || a.nyse != nullptr, "fm_forecast_portfolio_sort: nyse_breakpoints needs nyse");
-    FM_REQUIRE(a.min_count >= 1, "fm_forecast_portfolio_sort: min_count must be >= 1");
-    if (a.max_seg_len > PORT_MAX_ROWS) {
-        set_error("fm_forecast_portfolio_sort: %d-row months exceed %d", a.max_seg_len, PORT_MAX_ROWS);
-        return FM_ETOOBIG;
-    }
+    if (const int rc = check_sort_args(a, "fm_forecast_portfolio_sort")) return rc;
     if (a.nseg == 0 || a.nsel == 0) return FM_OK;   // nothing is read: an empty panel has no pointers
     const bool f64 = a.cols != nullptr, pl = a.hi_plane != nullptr || a.lo_plane != nullptr;
     FM_REQUIRE(f64 != pl, "fm_forecast_portfolio_sort: exactly one of cols and the planes must be given");
@@ -607,13 +583,11 @@ extern "C" int fm_forecast_portfolio_sort(const fm_fport_args* args, void* strea
                        "fm_forecast_portfolio_sort: sort %d column %d outside the panel's %d", j, a.sel_cols[j][k], a.ncols);
     }
     FM_REQUIRE(a.coef && a.seg_off && a.rec && a.cnt && a.status, "fm_forecast_portfolio_sort: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+    const char* who = "fm_forecast_portfolio_sort";
+    const dim3 grid(a.nseg, a.nsel);
     const size_t lds = port_lds_bytes(a.max_seg_len);
-    int rc;
-    if (a.max_seg_len <= 256 * 4) rc = pl ? launch_fport<256, 4, true>(a, lds, st) : launch_fport<256, 4, false>(a, lds, st);
-    else if (a.max_seg_len <= 512 * 10) rc = pl ? launch_fport<512, 10, true>(a, lds, st) : launch_fport<512, 10, false>(a, lds, st);
-    else rc = pl ? launch_fport<1024, 16, true>(a, lds, st) : launch_fport<1024, 16, false>(a, lds, st);
-    if (rc != FM_OK) return rc;
-    FM_CHECK_LAUNCH("fm_forecast_portfolio_sort");
-    return FM_OK;
+    return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
+        return pl ? launch<nt, vpt, FusedSrc<true>>(a, grid, lds, who, (hipStream_t)stream)
+                  : launch<nt, vpt, FusedSrc<false>>(a, grid, lds, who, (hipStream_t)stream);
+    });
 }

@@ -26,6 +26,9 @@
 // what phase 3 finds for its own rows' keys in each.  One launch, no workspace, no atomics, and
 // no workgroup reads what another one writes; the price is that every slice's workgroup sorts
 // every part: parts^2 part-sorts per unit, hence the 65,536-row limit.
+//
+// Both kernels run the phases through the same device functions below (RankRows::key,
+// sort_runs, merge_runs, count_in_sorted, rank_value).
 #include <math.h>
 
 #include "fm_common.h"
@@ -51,44 +54,53 @@ __device__ __forceinline__ void cmpx(uint64_t* buf, int i, int l) {
     }
 }
 
-template <int R>
-__global__ __launch_bounds__(1024) void rank_kernel(fm_rank_args a) {
-    constexpr int RUN = WAVE * R;          // keys per wave = the sorted run length
-    constexpr int SG = R < 8 ? R : 8;      // rows searched in step (that many LDS reads in flight)
-    extern __shared__ uint64_t rbuf[];     // blockDim.x * R keys
-    __shared__ int s_cnt[1024 / WAVE];
-    const int s = blockIdx.x, c = blockIdx.y;
-    const int NT = blockDim.x, nw = NT / WAVE;
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
-    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
-    const int64_t r0 = a.seg_off[s];
-    int L = (int)(a.seg_off[s + 1] - r0);
-    L = L < a.max_seg_len ? L : a.max_seg_len;   // the workgroup and its LDS were sized from max_seg_len
-    FM_PROBE_AT(rank, 0);
-    if (L <= 0) {   // block-uniform
-        if (tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = 0;
-        return;
+// One column of one month, row by row as keys: SENT past the end, for a NaN and outside the
+// universe (no eligible value maps to SENT: key != SENT is "the row is ranked")
+struct RankRows {
+    const double* __restrict__ X;
+    const uint8_t* __restrict__ LV;
+    int L, min_level;
+    __device__ __forceinline__ uint64_t key(int idx) const {
+        bool elig;
+        return key(idx, elig);
     }
-    const int nrun = (L + RUN - 1) / RUN;   // <= nw: waves nrun.. hold no row
-    const int Pact = nrun * RUN;
-    int P2 = RUN;
-    while (P2 < Pact) P2 <<= 1;
+    __device__ __forceinline__ uint64_t key(int idx, bool& elig) const {
+        const int ci = idx < L ? idx : L - 1;   // unconditional (clamped) load, masked after
+        const double x = X[ci] + 0.0;           // -0.0 -> +0.0: the two zeros tie
+        const int lv = LV != nullptr ? (int)LV[ci] : 255;
+        elig = idx < L && !isnan(x) && lv >= min_level;
+        return elig ? dkey(x) : SENT;
+    }
+};
 
-    // ---- 1. load, keys, per-wave sorted runs -------------------------------------------------
-    const double* __restrict__ X = a.src + (int64_t)c * a.src_stride + r0;
-    const uint8_t* __restrict__ LV = a.level != nullptr ? a.level + r0 : nullptr;
-    uint64_t key[R];
+// The sorted array of up to 1024 R rows: nrun runs of RUN = 64 R keys (one per wave that holds
+// rows), Pact keys in all, P2 the power of two they would be padded to
+struct Sorted {
+    int nrun, Pact, P2;
+};
+template <int RUN>
+__device__ __forceinline__ Sorted sorted_dims(int rows) {
+    Sorted d;
+    d.nrun = (rows + RUN - 1) / RUN;
+    d.Pact = d.nrun * RUN;
+    d.P2 = RUN;
+    while (d.P2 < d.Pact) d.P2 <<= 1;
+    return d;
+}
+
+// Phase 1 for the wave's R * 64 rows from `base` on, in (v, lane) order: their keys (all SENT in
+// a wave w >= nrun, which holds none), a copy sorted in registers and stored as run w.  Returns
+// the ranked rows of the NT-thread workgroup (s_cnt: a slot per wave); ends with a barrier.
+template <int R>
+__device__ __forceinline__ int sort_runs(uint64_t* rbuf, int* s_cnt, int NT, const Sorted& d, const RankRows& rows,
+                                         int base, int w, int lane, uint64_t (&key)[R]) {
+    constexpr int RUN = WAVE * R;
     int cnt = 0;
-    if (w < nrun) {   // wave-uniform
-        const int last = L - 1;
+    if (w < d.nrun) {   // wave-uniform
 #pragma unroll
-        for (int v = 0; v < R; ++v) {   // unconditional (clamped) loads, masked after
-            const int idx = (w * R + v) * WAVE + lane;
-            const int ci = idx < L ? idx : last;
-            const double x = X[ci] + 0.0;   // -0.0 -> +0.0: the two zeros tie
-            const int lv = LV != nullptr ? (int)LV[ci] : 255;
-            const bool elig = idx < L && !isnan(x) && lv >= a.min_level;
-            key[v] = elig ? dkey(x) : SENT;
+        for (int v = 0; v < R; ++v) {
+            bool elig;
+            key[v] = rows.key(base + v * WAVE + lane, elig);
             cnt += elig ? 1 : 0;
         }
         uint64_t k[R];
@@ -105,27 +117,32 @@ __global__ __launch_bounds__(1024) void rank_kernel(fm_rank_args a) {
     if (lane == 0) s_cnt[w] = cnt;
     __syncthreads();
     int n = 0;
-    for (int q = 0; q < nw; ++q) n += s_cnt[q];
-    FM_PROBE_AT(rank, 1);
+    for (int q = 0; q < NT / WAVE; ++q) n += s_cnt[q];
+    return n;
+}
 
-    // ---- 2. merge the runs -------------------------------------------------------------------
-    for (int k = 2 * RUN; k <= P2; k <<= 1) {   // block-uniform
+// Phase 2: the runs in rbuf merged into one ascending array; every barrier is block-uniform
+template <int R>
+__device__ __forceinline__ void merge_runs(uint64_t* rbuf, int NT, const Sorted& d, int w, int lane) {
+    constexpr int RUN = WAVE * R;
+    const int tid = threadIdx.x;
+    for (int k = 2 * RUN; k <= d.P2; k <<= 1) {   // block-uniform
         const int h = k >> 1;
-        for (int t = tid; t < (P2 >> 1); t += NT) {
+        for (int t = tid; t < (d.P2 >> 1); t += NT) {
             const int i = ((t & ~(h - 1)) << 1) | (t & (h - 1));
             const int l = i ^ (k - 1);
-            if (l < Pact) cmpx(rbuf, i, l);
+            if (l < d.Pact) cmpx(rbuf, i, l);
         }
         __syncthreads();
         for (int j = h >> 1; j >= RUN; j >>= 1) {
-            for (int t = tid; t < (P2 >> 1); t += NT) {
+            for (int t = tid; t < (d.P2 >> 1); t += NT) {
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
                 const int l = i | j;
-                if (l < Pact) cmpx(rbuf, i, l);
+                if (l < d.Pact) cmpx(rbuf, i, l);
             }
             __syncthreads();
         }
-        if (w < nrun) {   // the stages inside the run: distances RUN / 2 .. 1, all ascending
+        if (w < d.nrun) {   // the stages inside the run: distances RUN / 2 .. 1, all ascending
             uint64_t m[R];
 #pragma unroll
             for (int v = 0; v < R; ++v) m[v] = rbuf[w * RUN + v * WAVE + lane];
@@ -135,60 +152,111 @@ __global__ __launch_bounds__(1024) void rank_kernel(fm_rank_args a) {
         }
         __syncthreads();
     }
+}
+
+// Phase 3's searches for SG keys in step (that many LDS reads in flight): lt = #{sorted keys <
+// key}, le = #{sorted keys <= key}; the keys past the eligible ones are SENT.  OWN: the keys are
+// among the sorted ones, so an eligible key has lt < n <= P2 (the lower bound starts from
+// P2 / 2) and its run of equals is not empty.  Otherwise every sorted key may be smaller (it
+// starts from P2) and le = lt unless position lt holds the key.
+template <int SG, bool OWN>
+__device__ __forceinline__ void count_in_sorted(const uint64_t* rbuf, const Sorted& d, const uint64_t* key,
+                                                int (&lt)[SG], int (&le)[SG]) {
+    const int Pact = d.Pact, P2 = d.P2;
+#pragma unroll
+    for (int u = 0; u < SG; ++u) lt[u] = 0;
+    for (int step = OWN ? P2 >> 1 : P2; step > 0; step >>= 1) {
+#pragma unroll
+        for (int u = 0; u < SG; ++u) {
+            const int pa = lt[u] + step - 1;
+            const uint64_t xa = rbuf[pa < Pact ? pa : Pact - 1];
+            lt[u] += (pa < Pact && xa < key[u]) ? step : 0;
+        }
+    }
+    // a key whose successor differs ends its run of equals at lt + 1 (at lt if it is absent):
+    // only a wave that holds a tied key among these rows runs the upper bound search (the same
+    // counts either way)
+    bool tied = false;
+#pragma unroll
+    for (int u = 0; u < SG; ++u) {
+        const int pc = lt[u], pn = lt[u] + 1;
+        const uint64_t xn = rbuf[pn < Pact ? pn : Pact - 1];
+        tied |= pn < Pact && xn == key[u] && key[u] != SENT;
+        if constexpr (OWN) {
+            le[u] = pn;
+        } else {
+            const uint64_t xc = rbuf[pc < Pact ? pc : Pact - 1];
+            le[u] = lt[u] + ((pc < Pact && xc == key[u]) ? 1 : 0);
+        }
+    }
+    if (__ballot(tied) != 0ull) {   // wave-uniform
+#pragma unroll
+        for (int u = 0; u < SG; ++u) le[u] = 0;
+        for (int step = P2; step > 0; step >>= 1) {   // from P2: le reaches P2 in a full month
+#pragma unroll
+            for (int u = 0; u < SG; ++u) {
+                const int pb = le[u] + step - 1;
+                const uint64_t xb = rbuf[pb < Pact ? pb : Pact - 1];
+                le[u] += (pb < Pact && xb <= key[u]) ? step : 0;
+            }
+        }
+    }
+}
+
+// The rank of a row with lt smaller and le smaller-or-equal keys among the month's n eligible
+// ones (dn = n, dn1 = n + 1): a multiple of 0.5 below 2^17, exact before the scaling
+__device__ __forceinline__ double rank_value(int method, int scale, int lt, int le, double dn, double dn1) {
+    double r;
+    if (method == FM_RANK_MIN) r = (double)(lt + 1);
+    else if (method == FM_RANK_MAX) r = (double)le;
+    else r = 0.5 * (double)(lt + le + 1);
+    double y = r;
+    if (scale == FM_RANK_PCT) y = r / dn;
+    else if (scale == FM_RANK_UNIFORM) y = r / dn1 - 0.5;
+    return y;
+}
+
+template <int R>
+__global__ __launch_bounds__(1024) void rank_kernel(fm_rank_args a) {
+    constexpr int RUN = WAVE * R;          // keys per wave = the sorted run length
+    constexpr int SG = R < 8 ? R : 8;      // rows searched in step
+    extern __shared__ uint64_t rbuf[];     // blockDim.x * R keys
+    __shared__ int s_cnt[1024 / WAVE];
+    const int s = blockIdx.x, c = blockIdx.y;
+    const int NT = blockDim.x;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int64_t r0 = a.seg_off[s];
+    int L = (int)(a.seg_off[s + 1] - r0);
+    L = L < a.max_seg_len ? L : a.max_seg_len;   // the workgroup and its LDS were sized from max_seg_len
+    FM_PROBE_AT(rank, 0);
+    if (L <= 0) {   // block-uniform
+        if (tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = 0;
+        return;
+    }
+    const Sorted d = sorted_dims<RUN>(L);   // nrun <= the waves: waves nrun.. hold no row
+    const RankRows rows{a.src + (int64_t)c * a.src_stride + r0, a.level != nullptr ? a.level + r0 : nullptr, L,
+                        a.min_level};
+
+    uint64_t key[R];
+    const int n = sort_runs<R>(rbuf, s_cnt, NT, d, rows, w * RUN, w, lane, key);
+    FM_PROBE_AT(rank, 1);
+    merge_runs<R>(rbuf, NT, d, w, lane);
     FM_PROBE_AT(rank, 2);
 
-    // ---- 3. less / less + eq by two bound searches, ranks ------------------------------------
     if (tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = n;
     double* __restrict__ D = a.dst + (int64_t)c * a.dst_stride + r0;
     const double dn = (double)n, dn1 = (double)(n + 1);
     const int method = a.method, scale = a.scale;
-    if (w < nrun) {
+    if (w < d.nrun) {
 #pragma unroll
         for (int v0 = 0; v0 < R; v0 += SG) {
-            int lt[SG], le[SG];   // #{sorted keys < key}, #{<= key}: the keys past n are SENT
-#pragma unroll
-            for (int u = 0; u < SG; ++u) lt[u] = 0;
-            for (int step = P2 >> 1; step > 0; step >>= 1) {   // an eligible key has lt < n <= P2
-#pragma unroll
-                for (int u = 0; u < SG; ++u) {
-                    const int pa = lt[u] + step - 1;
-                    const uint64_t xa = rbuf[pa < Pact ? pa : Pact - 1];
-                    lt[u] += (pa < Pact && xa < key[v0 + u]) ? step : 0;
-                }
-            }
-            // a key whose successor differs ends its run of equals at lt + 1: only a wave that
-            // holds a tied key among these rows runs the upper bound search (the same counts
-            // either way)
-            bool tied = false;
-#pragma unroll
-            for (int u = 0; u < SG; ++u) {
-                const int pn = lt[u] + 1;
-                const uint64_t xn = rbuf[pn < Pact ? pn : Pact - 1];
-                tied |= pn < Pact && xn == key[v0 + u] && key[v0 + u] != SENT;
-                le[u] = pn;
-            }
-            if (__ballot(tied) != 0ull) {   // wave-uniform
-#pragma unroll
-                for (int u = 0; u < SG; ++u) le[u] = 0;
-                for (int step = P2; step > 0; step >>= 1) {   // from P2: le reaches P2 in a full month
-#pragma unroll
-                    for (int u = 0; u < SG; ++u) {
-                        const int pb = le[u] + step - 1;
-                        const uint64_t xb = rbuf[pb < Pact ? pb : Pact - 1];
-                        le[u] += (pb < Pact && xb <= key[v0 + u]) ? step : 0;
-                    }
-                }
-            }
+            int lt[SG], le[SG];
+            count_in_sorted<SG, true>(rbuf, d, key + v0, lt, le);
 #pragma unroll
             for (int u = 0; u < SG; ++u) {
                 const int idx = (w * R + v0 + u) * WAVE + lane;
-                double r;   // a multiple of 0.5 below 2^15: exact
-                if (method == FM_RANK_MIN) r = (double)(lt[u] + 1);
-                else if (method == FM_RANK_MAX) r = (double)le[u];
-                else r = 0.5 * (double)(lt[u] + le[u] + 1);
-                double y = r;
-                if (scale == FM_RANK_PCT) y = r / dn;
-                else if (scale == FM_RANK_UNIFORM) y = r / dn1 - 0.5;
+                const double y = rank_value(method, scale, lt[u], le[u], dn, dn1);
                 if (idx < L) D[idx] = key[v0 + u] != SENT ? y : NAN;
             }
         }
@@ -203,16 +271,14 @@ __global__ __launch_bounds__(1024) void rank_kernel(fm_rank_args a) {
 // #{part keys <= key} to two per-row sums.  Only the sums stay in registers across a part's
 // sort: the own keys are made again from src for every part (the month's values come from
 // cache after the first read), 8 rows at a time, which is what keeps a 16-row slice within
-// 128 VGPRs.  A key need not occur in the visited part: the lower bound may then be the whole
-// part (the search starts from P2, not P2 / 2), and le = lt there.  L, the part count and every
-// barrier are block-uniform.
+// 128 VGPRs.  A key need not occur in the visited part (count_in_sorted<.., false>).  L, the
+// part count and every barrier are block-uniform.
 __global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
     constexpr int R = RANK_PART / 1024;    // rows per thread, of a visited part and of the own slice
     constexpr int RUN = WAVE * R;
     constexpr int SG = 8;
-    constexpr int NW = 1024 / WAVE;
     extern __shared__ uint64_t rbuf[];     // RANK_PART keys
-    __shared__ int s_cnt[NW];
+    __shared__ int s_cnt[1024 / WAVE];
     const int s = blockIdx.x, c = blockIdx.y;
     const int own0 = blockIdx.z * RANK_PART;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
@@ -224,18 +290,8 @@ __global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
         if (own0 == 0 && tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = 0;
         return;
     }
-    const double* __restrict__ X = a.src + (int64_t)c * a.src_stride + r0;
-    const uint8_t* __restrict__ LV = a.level != nullptr ? a.level + r0 : nullptr;
-    const int last = L - 1;
-    const int min_level = a.min_level;
-    // row idx of the month as a key: SENT if past the end, NaN or outside the universe
-    auto key_of_row = [&](int idx, bool& elig) -> uint64_t {
-        const int ci = idx < L ? idx : last;   // unconditional (clamped) load, masked after
-        const double x = X[ci] + 0.0;          // -0.0 -> +0.0: the two zeros tie
-        const int lv = LV != nullptr ? (int)LV[ci] : 255;
-        elig = idx < L && !isnan(x) && lv >= min_level;
-        return elig ? dkey(x) : SENT;
-    };
+    const RankRows rows{a.src + (int64_t)c * a.src_stride + r0, a.level != nullptr ? a.level + r0 : nullptr, L,
+                        a.min_level};
     const bool own_rows = own0 + w * RUN < L;   // wave-uniform: this wave holds rows of the slice
 
     int lts[R], les[R];   // the own rows' counts over the parts visited so far
@@ -244,62 +300,13 @@ __global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
     int n = 0;
 
     for (int p0 = 0; p0 < L; p0 += RANK_PART) {   // block-uniform
-        const int Lp = L - p0 < RANK_PART ? L - p0 : RANK_PART;
-        const int nrun = (Lp + RUN - 1) / RUN;   // <= NW: waves nrun.. hold no row of this part
-        const int Pact = nrun * RUN;
-        int P2 = RUN;
-        while (P2 < Pact) P2 <<= 1;
-
-        // ---- 1. the part's keys, per-wave sorted runs ----------------------------------------
-        int cnt = 0;
-        if (w < nrun) {   // wave-uniform
+        const Sorted d = sorted_dims<RUN>(L - p0 < RANK_PART ? L - p0 : RANK_PART);
+        {
             uint64_t k[R];
-#pragma unroll
-            for (int v = 0; v < R; ++v) {
-                bool elig;
-                k[v] = key_of_row(p0 + (w * R + v) * WAVE + lane, elig);
-                cnt += elig ? 1 : 0;
-            }
-            wave_sort64<R>(k);
-#pragma unroll
-            for (int v = 0; v < R; ++v) rbuf[w * RUN + v * WAVE + lane] = k[v];
+            n += sort_runs<R>(rbuf, s_cnt, 1024, d, rows, p0 + w * RUN, w, lane, k);
         }
-        cnt = wave_sum(cnt);
-        if (lane == 0) s_cnt[w] = cnt;
-        __syncthreads();
-        for (int q = 0; q < NW; ++q) n += s_cnt[q];
+        merge_runs<R>(rbuf, 1024, d, w, lane);
 
-        // ---- 2. merge the runs: rank_kernel's phase 2, repeated here and not shared, since a
-        // common device function changes the register allocation of rank_kernel<8> / <16>,
-        // whose code this path leaves exactly as it was
-        for (int k = 2 * RUN; k <= P2; k <<= 1) {   // block-uniform
-            const int h = k >> 1;
-            for (int t = tid; t < (P2 >> 1); t += 1024) {
-                const int i = ((t & ~(h - 1)) << 1) | (t & (h - 1));
-                const int l = i ^ (k - 1);
-                if (l < Pact) cmpx(rbuf, i, l);
-            }
-            __syncthreads();
-            for (int j = h >> 1; j >= RUN; j >>= 1) {
-                for (int t = tid; t < (P2 >> 1); t += 1024) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                    const int l = i | j;
-                    if (l < Pact) cmpx(rbuf, i, l);
-                }
-                __syncthreads();
-            }
-            if (w < nrun) {
-                uint64_t m[R];
-#pragma unroll
-                for (int v = 0; v < R; ++v) m[v] = rbuf[w * RUN + v * WAVE + lane];
-                bitonic_u64_stages<R, 2 * RUN, RUN / 2>(m);
-#pragma unroll
-                for (int v = 0; v < R; ++v) rbuf[w * RUN + v * WAVE + lane] = m[v];
-            }
-            __syncthreads();
-        }
-
-        // ---- 3. the own keys' two counts in this part ----------------------------------------
 #pragma unroll
         for (int v0 = 0; v0 < R; v0 += SG) {
             if (!own_rows) break;   // wave-uniform; no barrier below
@@ -310,43 +317,8 @@ __global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
             uint64_t key[SG];
             int lt[SG], le[SG];
 #pragma unroll
-            for (int u = 0; u < SG; ++u) {
-                bool elig;
-                key[u] = key_of_row(ob + (w * R + v0 + u) * WAVE + lane, elig);
-                lt[u] = 0;
-            }
-            for (int step = P2; step > 0; step >>= 1) {   // from P2: every key of the part may be smaller
-#pragma unroll
-                for (int u = 0; u < SG; ++u) {
-                    const int pa = lt[u] + step - 1;
-                    const uint64_t xa = rbuf[pa < Pact ? pa : Pact - 1];
-                    lt[u] += (pa < Pact && xa < key[u]) ? step : 0;
-                }
-            }
-            // position lt holds the key if the part has it at all (else le = lt); its run of
-            // equals ends at lt + 1 unless the successor equals it too: only a wave that holds
-            // such a key among these rows runs the upper bound search (the same counts either way)
-            bool tied = false;
-#pragma unroll
-            for (int u = 0; u < SG; ++u) {
-                const int pc = lt[u], pn = lt[u] + 1;
-                const uint64_t xc = rbuf[pc < Pact ? pc : Pact - 1];
-                const uint64_t xn = rbuf[pn < Pact ? pn : Pact - 1];
-                tied |= pn < Pact && xn == key[u] && key[u] != SENT;
-                le[u] = lt[u] + ((pc < Pact && xc == key[u]) ? 1 : 0);
-            }
-            if (__ballot(tied) != 0ull) {   // wave-uniform
-#pragma unroll
-                for (int u = 0; u < SG; ++u) le[u] = 0;
-                for (int step = P2; step > 0; step >>= 1) {
-#pragma unroll
-                    for (int u = 0; u < SG; ++u) {
-                        const int pb = le[u] + step - 1;
-                        const uint64_t xb = rbuf[pb < Pact ? pb : Pact - 1];
-                        le[u] += (pb < Pact && xb <= key[u]) ? step : 0;
-                    }
-                }
-            }
+            for (int u = 0; u < SG; ++u) key[u] = rows.key(ob + (w * R + v0 + u) * WAVE + lane);
+            count_in_sorted<SG, false>(rbuf, d, key, lt, le);
 #pragma unroll
             for (int u = 0; u < SG; ++u) {
                 lts[v0 + u] += lt[u];
@@ -356,7 +328,6 @@ __global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
         __syncthreads();   // the next part overwrites rbuf and s_cnt
     }
 
-    // ---- ranks of the own slice ------------------------------------------------------------------
     if (blockIdx.z == 0 && tid == 0 && a.nvalid != nullptr) a.nvalid[(int64_t)c * a.nseg + s] = n;
     double* __restrict__ D = a.dst + (int64_t)c * a.dst_stride + r0;
     const double dn = (double)n, dn1 = (double)(n + 1);
@@ -365,16 +336,8 @@ __global__ __launch_bounds__(1024) void rank_long_kernel(fm_rank_args a) {
     for (int v = 0; v < R; ++v) {
         if (!own_rows) break;
         const int idx = own0 + (w * R + v) * WAVE + lane;
-        bool elig;
-        key_of_row(idx, elig);
-        double r;   // a multiple of 0.5 below 2^17: exact
-        if (method == FM_RANK_MIN) r = (double)(lts[v] + 1);
-        else if (method == FM_RANK_MAX) r = (double)les[v];
-        else r = 0.5 * (double)(lts[v] + les[v] + 1);
-        double y = r;
-        if (scale == FM_RANK_PCT) y = r / dn;
-        else if (scale == FM_RANK_UNIFORM) y = r / dn1 - 0.5;
-        if (idx < L) D[idx] = elig ? y : NAN;
+        const double y = rank_value(method, scale, lts[v], les[v], dn, dn1);
+        if (idx < L) D[idx] = rows.key(idx) != SENT ? y : NAN;
     }
 }
 
@@ -382,31 +345,13 @@ template <int R>
 int launch_rank(const fm_rank_args& a, hipStream_t st) {
     const int nw = (a.max_seg_len + WAVE * R - 1) / (WAVE * R);
     const size_t lds = 8 * (size_t)nw * WAVE * R;
-    if (lds >= 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in (once)
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)rank_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    8 * 1024 * R) != hipSuccess) {
-                set_error("fm_rank_transform: cannot raise the dynamic LDS limit");
-                return FM_EHIP;
-            }
-            attr_set = true;
-        }
-    }
+    if (lds >= 64 * 1024 && raise_dynamic_lds<rank_kernel<R>>(8 * 1024 * R, "fm_rank_transform") != FM_OK) return FM_EHIP;
     hipLaunchKernelGGL((rank_kernel<R>), dim3(a.nseg, a.ncols), dim3(nw * WAVE), lds, st, a);
     return FM_OK;
 }
 
 int launch_rank_long(const fm_rank_args& a, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {   // 128 KB of dynamic LDS: opt in (once)
-        if (hipFuncSetAttribute((const void*)rank_long_kernel,hipFuncAttributeMaxDynamicSharedMemorySize,
-                                8 * RANK_PART) != hipSuccess) {
-            set_error("fm_rank_transform: cannot raise the dynamic LDS limit");
-            return FM_EHIP;
-        }
-        attr_set = true;
-    }
+    if (raise_dynamic_lds<rank_long_kernel>(8 * RANK_PART, "fm_rank_transform") != FM_OK) return FM_EHIP;
     const int nslice = (a.max_seg_len + RANK_PART - 1) / RANK_PART;
     hipLaunchKernelGGL(rank_long_kernel, dim3(a.nseg, a.ncols, nslice), dim3(1024), 8 * (size_t)RANK_PART, st, a);
     return FM_OK;

@@ -1269,14 +1269,9 @@ extern "C" int fm_solve(const fm_solve_args* args, void* stream) {
                "shift with inv_scale");
     if (a.nseg == 0 || a.nprob == 0) return FM_OK;
     const size_t dyn = (size_t)a.npatterns * a.nlevels * (a.zw * (a.zw + 1) / 2) * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)solve16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            MAXB_LDS * (int)sizeof(double));
-        (void)hipFuncSetAttribute((const void*)solve_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            MAXB_LDS * (int)sizeof(double));
-        attr_set = true;
-    }
+    const int rc = a.zw == 16 ? raise_dynamic_lds<solve16_kernel>(MAXB_LDS * sizeof(double), "fm_solve")
+                              : raise_dynamic_lds<solve_kernel<32>>(MAXB_LDS * sizeof(double), "fm_solve");
+    if (rc != FM_OK) return rc;
     if (a.zw == 16)
         hipLaunchKernelGGL(solve16_kernel, dim3(a.nseg), dim3(S16T), dyn, (hipStream_t)stream, a);
     else

@@ -1222,16 +1222,7 @@ extern "C" int fm_ts_fused(const fm_ts_args* args, void* stream) {
                                              a.pred != nullptr);
     FM_REQUIRE(lds <= FM_TS_FUSED_MAX_LDS,
                "fm_ts_fused: series too long for LDS staging (use the per-stage entry points)");
-    if (lds > 64 * 1024) {   // beyond the default dynamic-LDS limit: opt in (once)
-        static bool attr_set = false;
-        if (!attr_set) {
-            FM_REQUIRE(hipFuncSetAttribute((const void*)ts_fused_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           FM_TS_FUSED_MAX_LDS) == hipSuccess,
-                       "fm_ts_fused: cannot raise the dynamic LDS limit");
-            attr_set = true;
-        }
-    }
+    if (lds > 64 * 1024 && raise_dynamic_lds<ts_fused_kernel>(FM_TS_FUSED_MAX_LDS, "fm_ts_fused") != FM_OK) return FM_EHIP;
     const int nchunk = a.roll ? (a.nseg + RROWS - 1) / RROWS : 0;
     hipLaunchKernelGGL(ts_fused_kernel, dim3(a.kmax + nchunk, a.nprob), dim3(FT), lds, (hipStream_t)stream, a);
     FM_CHECK_LAUNCH("fm_ts_fused");

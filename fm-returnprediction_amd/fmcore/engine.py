@@ -1166,6 +1166,28 @@ def _row_vector(t, dtype, n, dev, what):
     return t.contiguous()
 
 
+def _sort_plan(who, lead, T, n, nport, q, nyse_breakpoints, min_count):
+    """What the two portfolio sorts share: ``fill(a)`` sets an argument struct's ``nport``, ``q`` (default
+    k / nport), ``nyse_breakpoints`` and ``min_count`` (default nport) and returns it; ``shapes``: the
+    ``Portfolios`` tensors' (shape, dtype) under the leading dimensions ``lead``."""
+    qs = list(q) if q is not None else [k / nport for k in range(1, max(nport, 1))]
+    if q is not None and len(qs) != nport - 1:
+        raise ValueError(f"{who}: q must hold nport - 1 = {nport - 1} levels, got {len(qs)}")
+
+    def fill(a):
+        a.nport, a.nyse_breakpoints = nport, int(bool(nyse_breakpoints))
+        a.min_count = nport if min_count is None else int(min_count)
+        for j, v in enumerate(qs[:L.FM_MAX_PORTS - 1]):
+            a.q[j] = float(v)
+        return a
+
+    np_ = min(max(nport, 2), L.FM_MAX_PORTS)   # output shapes of a call the library will refuse
+    shapes = dict(bp=(lead + (T, np_ - 1), torch.float64), port=(lead + (n,), torch.uint8),
+                  rec=(lead + (T, np_ + 1, 4), torch.float64), cnt=(lead + (T, np_), torch.int32),
+                  status=(lead + (T,), torch.int32))
+    return fill, shapes
+
+
 def portfolio_sort(seg_off, forecast, ret, weight=None, level=None, nyse=None, nport=10, q=None,
                    min_level=0, nyse_breakpoints=False, min_count=None, max_seg_len=None):
     """A12: per month (``seg_off`` int64 [T+1] device, rows sorted by month) sort the rows into
@@ -1185,27 +1207,15 @@ def portfolio_sort(seg_off, forecast, ret, weight=None, level=None, nyse=None, n
     weight = _row_vector(weight, torch.float64, n, dev, "weight")
     level = _row_vector(level, torch.uint8, n, dev, "level")
     nyse = _row_vector(nyse, torch.uint8, n, dev, "nyse")
-    nport = int(nport)
+    fill, shapes = _sort_plan("portfolio_sort", (), T, n, int(nport), q, nyse_breakpoints, min_count)
     if max_seg_len is None:
         max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
-    a = L.PortArgs()
+    a = fill(L.PortArgs())
     a.forecast, a.ret, a.weight, a.level, a.nyse = _ptr(forecast), _ptr(ret), _ptr(weight), _ptr(level), _ptr(nyse)
-    a.seg_off, a.nseg, a.max_seg_len = seg_off.data_ptr(), T, int(max_seg_len)
-    a.nport, a.min_level, a.nyse_breakpoints = nport, int(min_level), int(bool(nyse_breakpoints))
-    a.min_count = nport if min_count is None else int(min_count)
-    qs = list(q) if q is not None else [k / nport for k in range(1, max(nport, 1))]
-    if q is not None and len(qs) != nport - 1:
-        raise ValueError(f"portfolio_sort: q must hold nport - 1 = {nport - 1} levels, got {len(qs)}")
-    for j, v in enumerate(qs[:L.FM_MAX_PORTS - 1]):
-        a.q[j] = float(v)
-    np_ = min(max(nport, 2), L.FM_MAX_PORTS)   # output shapes of a call the library will refuse
-    out = Portfolios(bp=torch.empty((T, np_ - 1), dtype=torch.float64, device=dev),
-                     port=torch.empty(n, dtype=torch.uint8, device=dev),
-                     rec=torch.empty((T, np_ + 1, 4), dtype=torch.float64, device=dev),
-                     cnt=torch.empty((T, np_), dtype=torch.int32, device=dev),
-                     status=torch.empty(T, dtype=torch.int32, device=dev))
-    a.bp, a.port, a.rec, a.cnt, a.status = (out.bp.data_ptr(), out.port.data_ptr(), out.rec.data_ptr(),
-                                             out.cnt.data_ptr(), out.status.data_ptr())
+    a.seg_off, a.nseg, a.max_seg_len, a.min_level = seg_off.data_ptr(), T, int(max_seg_len), int(min_level)
+    out = Portfolios(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    for k in shapes:
+        setattr(a, k, getattr(out, k).data_ptr())
     _kcall("fm_portfolio_sort", "fm_portfolio_sort", L.C.byref(a), _stream())
     _remember("fm_portfolio_sort", "fm_portfolio_sort", a, seg_off, forecast, ret, weight, level, nyse, out)
     return out
@@ -1269,14 +1279,7 @@ def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, re
         lo, hi = cuts.lo.contiguous(), cuts.hi.contiguous()
         if tuple(lo.shape) != (C, T) or tuple(hi.shape) != (C, T):
             raise ValueError(f"forecast_portfolio_sort: the cuts must be [{C}, {T}] tables")
-    nport = int(nport)
-    qs = list(q) if q is not None else [k / nport for k in range(1, max(nport, 1))]
-    if q is not None and len(qs) != nport - 1:
-        raise ValueError(f"forecast_portfolio_sort: q must hold nport - 1 = {nport - 1} levels, got {len(qs)}")
-    np_ = min(max(nport, 2), L.FM_MAX_PORTS)   # output shapes of a call the library will refuse
-    shapes = dict(bp=((nsel, T, np_ - 1), torch.float64), port=((nsel, n), torch.uint8),
-                  rec=((nsel, T, np_ + 1, 4), torch.float64), cnt=((nsel, T, np_), torch.int32),
-                  status=((nsel, T), torch.int32))
+    fill, shapes = _sort_plan("forecast_portfolio_sort", (nsel,), T, n, int(nport), q, nyse_breakpoints, min_count)
     if forecast_out:
         shapes["forecast"] = ((nsel, n), torch.float64)
     if out is None:
@@ -1289,7 +1292,7 @@ def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, re
     f64 = src.f64 is not None
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
         part = sel[j0:j0 + L.FM_MAX_SORTS]
-        a = L.FPortArgs()
+        a = fill(L.FPortArgs())
         if f64:
             a.cols, a.col_stride = src.ptr, src.stride
         else:
@@ -1298,11 +1301,7 @@ def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, re
         a.lo, a.hi = _ptr(lo), _ptr(hi)
         a.weight, a.level, a.nyse = _ptr(weight), _ptr(level), _ptr(nyse)
         a.seg_off, a.nrows, a.nseg, a.max_seg_len = panel.seg_off.data_ptr(), n, T, panel.max_seg_len
-        a.nport, a.nyse_breakpoints = nport, int(bool(nyse_breakpoints))
-        a.min_count = nport if min_count is None else int(min_count)
         a.nsel = len(part)
-        for k, v in enumerate(qs[:L.FM_MAX_PORTS - 1]):
-            a.q[k] = float(v)
         for j, (xs, lv) in enumerate(part):
             a.sel_k[j], a.sel_level[j] = len(xs), lv
             for k, c in enumerate(xs[:L.FM_MAX_SORT_K]):
