@@ -49,6 +49,7 @@ extern "C" int64_t fm_struct_size(const char* name) {
     if (n == "fm_port_args") return (int64_t)sizeof(fm_port_args);
     if (n == "fm_rank_args") return (int64_t)sizeof(fm_rank_args);
     if (n == "fm_fport_args") return (int64_t)sizeof(fm_fport_args);
+    if (n == "fm_fdist_args") return (int64_t)sizeof(fm_fdist_args);
     return -1;
 }
 

@@ -27,6 +27,9 @@
 // VPT rows in the inner one (VPT independent loads in flight), accumulated in the fe registers
 // the sort keeps anyway; phase 4 reads the return column through the same layout.  No clipped
 // panel and no forecast vector ever reach HBM.
+//
+// fm_forecast_dist (A14; paper Table 3) is fdist_kernel below: the same phases 1-2 from the same
+// three sources, then two fixed-order reductions of the forecasts instead of phases 3-4.
 #include <math.h>
 
 #include "fm_common.h"
@@ -75,18 +78,18 @@ __device__ __forceinline__ void lds_bitonic(uint64_t* buf, int P) {
 
 // What a month's workgroup sorts by.  PlainSrc: the caller's forecast and return vectors
 // (fm_portfolio_sort).  FusedSrc<PL>: sort j of fm_forecast_portfolio_sort, panel values from the
-// FP64 columns or (PL) from the planes, two 4-byte loads joined in registers.
+// FP64 columns or (PL) from the planes, two 4-byte loads joined in registers (PanelSrc, over
+// the argument struct that holds the panel).
 struct PlainSrc {
     static constexpr bool FUSED = false;
     __device__ static PlainSrc make(const fm_port_args&) { return {}; }
 };
 
-template <bool PL>
-struct FusedSrc {
+template <bool PL, class A>
+struct PanelSrc {
     static constexpr bool FUSED = true;
-    const fm_fport_args& a;
+    const A& a;
     int j;   // blockIdx.y
-    __device__ static FusedSrc make(const fm_fport_args& a) { return {a, (int)blockIdx.y}; }
     __device__ __forceinline__ double value(int col, int64_t row) const {
         if constexpr (PL) {
             const int64_t o = (int64_t)col * a.plane_stride + row;
@@ -97,10 +100,62 @@ struct FusedSrc {
         }
     }
 };
+template <bool PL>
+struct FusedSrc : PanelSrc<PL, fm_fport_args> {
+    __device__ static FusedSrc make(const fm_fport_args& a) { return {{a, (int)blockIdx.y}}; }
+};
+template <bool PL>   // the same view of fm_forecast_dist's panel
+struct DistSrc : PanelSrc<PL, fm_fdist_args> {
+    __device__ static DistSrc make(const fm_fdist_args& a) { return {{a, (int)blockIdx.y}}; }
+};
+
+// The fused load of month s (L > 0 rows from r0) of sort src.j: fe[v] = the forecast of the
+// thread's row (w * VPT + v) * 64 + lane (clamped to the month's last row), written to
+// forecast_out at ro on request.  Predictor k outside (c_k and the month's cuts are
+// wave-uniform), the thread's rows inside (VPT independent loads in flight); every product and
+// every sum rounds on its own (-ffp-contract=off), in fm_forecast's order.
+template <int VPT, class Src, class A>
+__device__ __forceinline__ void fused_forecast(const Src& src, const A& a, int s, int64_t so, int64_t ro,
+                                               int64_t r0, int L, int w, int lane, double (&fe)[VPT]) {
+    const int last = L - 1;
+    const int K = a.sel_k[src.j];
+    const double* __restrict__ c = a.coef + so * a.coef_stride;
+    const double c0 = c[0];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) fe[v] = c0;
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        const int col = a.sel_cols[src.j][k];
+        const double ck = c[1 + k];
+        const double lo = a.lo != nullptr ? a.lo[(int64_t)col * a.nseg + s] : NAN;
+        const double hi = a.hi != nullptr ? a.hi[(int64_t)col * a.nseg + s] : NAN;
+        double x[VPT];
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = (w * VPT + v) * WAVE + lane;
+            x[v] = src.value(col, r0 + (idx < L ? idx : last));
+        }
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            double y = x[v];   // fm_clip: a NaN value stays NaN, a NaN bound is ignored
+            if (y < lo) y = lo;
+            if (y > hi) y = hi;
+            fe[v] = fe[v] + ck * y;
+        }
+    }
+    if (a.forecast_out != nullptr) {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = (w * VPT + v) * WAVE + lane;
+            if (idx < L) a.forecast_out[ro + idx] = fe[v];
+        }
+    }
+}
 
 // One month (of one sort) by the NT-thread workgroup: A is fm_port_args with PlainSrc,
 // fm_fport_args with FusedSrc (the fields both share have the same names).  The body stays in
-// the kernel itself: behind an inlined device function the 1024 x 16 form allocates 18 more VGPRs.
+// the kernel itself: behind an inlined device function the 1024 x 16 form allocates 18 more VGPRs
+// (the fused load alone, fused_forecast above, leaves every form's allocation as it was).
 template <int NT, int VPT, class Src = PlainSrc, class A = fm_port_args>
 __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(A a) {
     constexpr int NW = NT / WAVE;
@@ -144,41 +199,7 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(A a) {
     if (L > 0) {        // block-uniform
         const int last = L - 1;
         if constexpr (FUSED) {
-            // the forecast: predictor k outside (c_k and the month's cuts are wave-uniform), the
-            // thread's rows inside (VPT independent loads in flight); every product and every sum
-            // rounds on its own (-ffp-contract=off), in fm_forecast's order
-            const int K = a.sel_k[src.j];
-            const double* __restrict__ c = a.coef + so * a.coef_stride;
-            const double c0 = c[0];
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) fe[v] = c0;
-#pragma unroll 1
-            for (int k = 0; k < K; ++k) {
-                const int col = a.sel_cols[src.j][k];
-                const double ck = c[1 + k];
-                const double lo = a.lo != nullptr ? a.lo[(int64_t)col * a.nseg + s] : NAN;
-                const double hi = a.hi != nullptr ? a.hi[(int64_t)col * a.nseg + s] : NAN;
-                double x[VPT];
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int idx = (w * VPT + v) * WAVE + lane;
-                    x[v] = src.value(col, r0 + (idx < L ? idx : last));
-                }
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    double y = x[v];   // fm_clip: a NaN value stays NaN, a NaN bound is ignored
-                    if (y < lo) y = lo;
-                    if (y > hi) y = hi;
-                    fe[v] = fe[v] + ck * y;
-                }
-            }
-            if (a.forecast_out != nullptr) {
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int idx = (w * VPT + v) * WAVE + lane;
-                    if (idx < L) a.forecast_out[ro + idx] = fe[v];
-                }
-            }
+            fused_forecast<VPT>(src, a, s, so, ro, r0, L, w, lane, fe);
         }
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
@@ -540,6 +561,260 @@ int check_sort_args(const A& a, const char* who) {
     return FM_OK;
 }
 
+// ---- fm_forecast_dist (extension A14; paper Table 3) -----------------------------------------
+// Per (month, sort): the count, mean, ddof-1 standard deviation and nq quantiles of the eligible
+// forecasts.  Phases 1-2 are port_kernel's (the same loads, fused_forecast, the same sample select
+// and full sort, here as the device function order_stat_keys: port_kernel keeps its own text for
+// the register count noted above it, and tests/test_gpu_fdist.py holds the two to the same keys);
+// phase 3 reduces the fe registers twice instead of partitioning rows.  No list is staged and
+// neither return nor weight is read.
+
+// Shared scratch of order_stat_keys for NW-wave workgroups: trank in, okey out
+template <int NW>
+struct OrderSh {
+    uint64_t okey[PSLOTS];
+    int trank[PSLOTS], tslot[PSLOTS], tbase[PSLOTS], ccnt[PSLOTS];
+    int iscr[NW];
+    int n, over;
+};
+
+// sh.okey[t] = the key at ascending rank sh.trank[t] (t < nt <= PSLOTS) among the n > 0 rows of
+// this month marked in bpm (the thread's rows v with bit v set; fe[v] is then not NaN).  The caller
+// has stored sh.trank and zeroed sh.n and sh.over (no barrier needed in between); ends with a
+// barrier.  port_kernel's phase 2, statement for statement.
+template <int NT, int VPT>
+__device__ __forceinline__ void order_stat_keys(const double (&fe)[VPT], uint32_t bpm, int n, int nt,
+                                                uint64_t* pbuf, OrderSh<NT / WAVE>& sh) {
+    constexpr int NW = NT / WAVE;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    bool have = false;   // block-uniform: sh.okey holds the keys at the target ranks
+    if constexpr (NT >= 512) {
+        if (n > PORT_FAST_MIN) {
+            uint64_t* samp = pbuf;
+            uint32_t* hist = reinterpret_cast<uint32_t*>(samp + NT);
+            uint8_t* slot = reinterpret_cast<uint8_t*>(hist + NT);
+            uint64_t* cand = reinterpret_cast<uint64_t*>(slot + NT);
+            {
+                const int first = bpm != 0u ? __ffs((int)bpm) - 1 : -1;
+                uint64_t key = SENT;
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) key = v == first ? dkey(fe[v]) : key;
+                samp[tid] = key;
+                hist[tid] = 0u;
+                if (tid < PSLOTS) sh.ccnt[tid] = 0;
+            }
+            __syncthreads();
+            lds_bitonic<NT>(samp, NT);
+            int bk[VPT];   // min(#{samples <= key}, NT - 1): monotone in the key
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) bk[v] = 0;
+            constexpr int SG = VPT <= 10 ? VPT : 1;
+#pragma unroll
+            for (int v0 = 0; v0 < VPT; v0 += SG) {
+                if (SG == 1 && !((bpm >> v0) & 1u)) continue;
+#pragma unroll
+                for (int step = NT / 2; step > 0; step >>= 1) {
+#pragma unroll
+                    for (int v = v0; v < v0 + SG; ++v) {
+                        const uint64_t key = ((bpm >> v) & 1u) ? dkey(fe[v]) : SENT;
+                        bk[v] += samp[bk[v] + step - 1] <= key ? step : 0;
+                    }
+                }
+                if (SG == 1) atomicAdd(&hist[bk[v0]], 1u);
+            }
+            if (SG > 1) {
+#pragma unroll
+                for (int v = 0; v < VPT; ++v)
+                    if ((bpm >> v) & 1u) atomicAdd(&hist[bk[v]], 1u);
+            }
+            __syncthreads();
+            const int x = (int)hist[tid];
+            int tot;
+            const int excl = block_excl_scan<NW>(x, sh.iscr, &tot);
+            const int trv = lane < nt ? sh.trank[lane] : -1;   // lane t: target rank t
+            int flag = 0;
+            for (int t = 0; t < nt; ++t) {
+                const int r = __builtin_amdgcn_readlane(trv, t);
+                flag |= (r >= excl && r < excl + x) ? 1 : 0;
+            }
+            int nslots;
+            const int sid = block_excl_scan<NW>(flag, sh.iscr, &nslots);
+            slot[tid] = flag ? (uint8_t)sid : (uint8_t)255;
+            if (flag) {
+                if (x > PCAP) sh.over = 1;
+                for (int t = 0; t < nt; ++t) {
+                    const int r = sh.trank[t];   // (divergent here: no readlane)
+                    if (r >= excl && r < excl + x) {
+                        sh.tslot[t] = sid;
+                        sh.tbase[t] = excl;
+                    }
+                }
+            }
+            __syncthreads();
+            if (sh.over == 0) {   // block-uniform
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    if ((bpm >> v) & 1u) {
+                        const int sl = slot[bk[v]];
+                        if (sl != 255) cand[sl * PCAP + atomicAdd(&sh.ccnt[sl], 1)] = dkey(fe[v]);
+                    }
+                }
+                __syncthreads();
+                for (int sl = w; sl < nslots; sl += NW) wave_sort_lds<PCAP / WAVE>(cand + sl * PCAP, sh.ccnt[sl]);
+                __syncthreads();
+                if (tid < nt) sh.okey[tid] = cand[sh.tslot[tid] * PCAP + sh.trank[tid] - sh.tbase[tid]];
+                have = true;
+            }
+        }
+    }
+    if (!have) {
+        __syncthreads();
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const bool isbp = (bpm >> v) & 1u;
+            const uint64_t m = __ballot(isbp);
+            const int c = (int)__popcll(m);
+            int base = 0;
+            if (lane == 0 && c > 0) base = atomicAdd(&sh.n, c);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (isbp) pbuf[base + mask_rank(m)] = dkey(fe[v]);
+        }
+        const int P = pow2_ceil(n);
+        for (int i = n + tid; i < P; i += NT) pbuf[i] = SENT;
+        __syncthreads();
+        lds_bitonic<NT>(pbuf, P);
+        if (tid < nt) sh.okey[tid] = pbuf[sh.trank[tid]];
+    }
+    __syncthreads();
+}
+
+// The plain source of fm_forecast_dist: sort j's forecasts are the caller's vector j
+struct VecSrc {
+    static constexpr bool FUSED = false;
+    int j;   // blockIdx.y
+    __device__ static VecSrc make(const fm_fdist_args&) { return {(int)blockIdx.y}; }
+};
+
+// The fixed-order sum of one term per row of the month (x[v] for the thread's row v; +0.0 for
+// rows that do not count): each 64-row tile in row order by the wave butterfly (tile w * VPT + v
+// is wave w's register v), then lane l of wave 0 adds the tile sums l, l + 64, ... in order and
+// the butterfly runs again.  A tile past the month's end sums to +0.0 and adding it changes
+// nothing (the lane's sum starts at +0.0, so it is never -0.0): the result does not depend on
+// how many tiles the workgroup's form has.  Block-uniform result; two barriers.
+template <int NW, int VPT>
+__device__ __forceinline__ double tile_sum(const double (&x)[VPT], double* s_tile, int w, int lane) {
+    constexpr int NTILE = NW * VPT;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const double t = wave_sum(x[v]);
+        if (lane == 0) s_tile[w * VPT + v] = t;
+    }
+    __syncthreads();
+    if (w == 0) {
+        double acc = 0.0;
+        for (int i = lane; i < NTILE; i += WAVE) acc += s_tile[i];
+        acc = wave_sum(acc);
+        if (lane == 0) s_tile[NTILE] = acc;
+    }
+    __syncthreads();
+    return s_tile[NTILE];
+}
+
+template <int NT, int VPT, class Src>
+__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fdist_kernel(fm_fdist_args a) {
+    constexpr int NW = NT / WAVE;
+    constexpr bool FUSED = Src::FUSED;
+    const Src src = Src::make(a);
+    extern __shared__ uint64_t pbuf[];   // the keys of the order statistics
+    __shared__ OrderSh<NW> sh;
+    __shared__ double s_g[FM_MAX_DIST_Q];
+    __shared__ double s_tile[NW * VPT + 1];
+    const int s = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int nq = a.nq, nrec = 2 + nq;
+    const int64_t r0 = a.seg_off[s];
+    int L = (int)(a.seg_off[s + 1] - r0);
+    L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
+    const int64_t so = s + (int64_t)src.j * a.nseg, ro = r0 + (int64_t)src.j * a.nrows;
+    const int min_level = a.sel_level[src.j];
+
+    // ---- 1. load, eligibility ---------------------------------------------------------------
+    double fe[VPT];     // the eligible rows' forecasts, NaN otherwise
+    uint32_t bpm = 0;   // bit v: row v of this thread is eligible
+    if (L > 0) {        // block-uniform
+        const int last = L - 1;
+        if constexpr (FUSED) fused_forecast<VPT>(src, a, s, so, ro, r0, L, w, lane, fe);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
+            const int idx = (w * VPT + v) * WAVE + lane;
+            const int ci = idx < L ? idx : last;
+            double f;
+            if constexpr (FUSED) f = fe[v];
+            else f = a.forecast[ro + ci];
+            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
+            const bool elig = idx < L && isfinite(f) && lv >= min_level;
+            fe[v] = elig ? f : NAN;
+            bpm |= elig ? 1u << v : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) fe[v] = NAN;
+    }
+    const int n = block_sum<NW>((int)__popc(bpm), sh.iscr);
+    double* rec = a.rec + so * nrec;
+    if (tid == 0) a.cnt[so] = n;
+    if (n < a.min_count) {   // block-uniform
+        if (tid == 0) a.status[so] = 0u;
+        if (tid < nrec) rec[tid] = NAN;
+        return;
+    }
+
+    // ---- 2. the 2 nq order statistics, quantiles ---------------------------------------------
+    if (nq > 0) {   // block-uniform
+        if (tid < nq) {
+            int i, j;
+            double g;
+            qranks(n, a.q[tid], 0, i, j, g);
+            sh.trank[2 * tid] = i;
+            sh.trank[2 * tid + 1] = j;
+            s_g[tid] = g;
+        }
+        if (tid == 0) {
+            sh.n = 0;
+            sh.over = 0;
+        }
+        order_stat_keys<NT, VPT>(fe, bpm, n, 2 * nq, pbuf, sh);
+        if (tid < nq) rec[2 + tid] = qlerp(kval(sh.okey[2 * tid]), kval(sh.okey[2 * tid + 1]), s_g[tid], 0);
+    }
+
+    // ---- 3. mean, then the squared deviations from it, each in tile_sum's fixed order --------
+    double x[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((bpm >> v) & 1u) ? fe[v] : 0.0;
+    const double mean = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)n;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const double d = fe[v] - mean;
+        x[v] = ((bpm >> v) & 1u) ? d * d : 0.0;
+    }
+    const double ss = tile_sum<NW, VPT>(x, s_tile, w, lane);
+    if (tid == 0) {
+        rec[0] = mean;
+        rec[1] = n > 1 ? sqrt(ss / (double)(n - 1)) : NAN;
+        a.status[so] = 1u;
+    }
+}
+
+template <int NT, int VPT, class Src>
+int launch_fdist(const fm_fdist_args& a, size_t lds, hipStream_t st) {
+    const char* who = "fm_forecast_dist";
+    if (lds >= 64 * 1024 && raise_dynamic_lds<fdist_kernel<NT, VPT, Src>>(8 * pow2_ceil(NT * VPT), who) != FM_OK) return FM_EHIP;
+    hipLaunchKernelGGL((fdist_kernel<NT, VPT, Src>), dim3(a.nseg, a.nsel), dim3(NT), lds, st, a);
+    return check_launch(who);
+}
+
 }  // namespace
 }  // namespace fm
 
@@ -589,5 +864,53 @@ extern "C" int fm_forecast_portfolio_sort(const fm_fport_args* args, void* strea
     return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
         return pl ? launch<nt, vpt, FusedSrc<true>>(a, grid, lds, who, (hipStream_t)stream)
                   : launch<nt, vpt, FusedSrc<false>>(a, grid, lds, who, (hipStream_t)stream);
+    });
+}
+
+extern "C" int fm_forecast_dist(const fm_fdist_args* args, void* stream) {
+    using namespace fm;
+    const char* who = "fm_forecast_dist";
+    FM_REQUIRE(args != nullptr, "%s: null args", who);
+    const fm_fdist_args& a = *args;
+    FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0 && a.nrows >= 0, "%s: bad sizes", who);
+    FM_REQUIRE(a.nsel >= 0 && a.nsel <= FM_MAX_SORTS, "%s: nsel must be 0..%d", who, FM_MAX_SORTS);
+    FM_REQUIRE(a.nq >= 0 && a.nq <= FM_MAX_DIST_Q, "%s: nq must be 0..%d", who, FM_MAX_DIST_Q);
+    for (int i = 0; i < a.nq; ++i) {
+        const double lo = i == 0 ? 0.0 : a.q[i - 1];
+        FM_REQUIRE(a.q[i] > lo && a.q[i] < 1.0, "%s: q must be strictly ascending in (0, 1)", who);
+    }
+    FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
+    if (a.max_seg_len > PORT_MAX_ROWS) {
+        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
+        return FM_ETOOBIG;
+    }
+    if (a.nseg == 0 || a.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
+    const bool vec = a.forecast != nullptr, f64 = a.cols != nullptr, pl = a.hi_plane != nullptr || a.lo_plane != nullptr;
+    FM_REQUIRE((int)vec + (int)f64 + (int)pl == 1, "%s: exactly one of forecast, cols and the planes must be given", who);
+    FM_REQUIRE(!pl || (a.hi_plane != nullptr && a.lo_plane != nullptr), "%s: both planes are needed", who);
+    for (int j = 0; j < a.nsel; ++j)
+        FM_REQUIRE(a.sel_level[j] >= 0 && a.sel_level[j] <= 255, "%s: sel_level must be 0..255", who);
+    if (vec) {
+        FM_REQUIRE(a.forecast_out == nullptr, "%s: forecast_out goes with a panel source", who);
+    } else {
+        FM_REQUIRE((f64 ? a.col_stride : a.plane_stride) >= a.nrows, "%s: stride below the row count", who);
+        FM_REQUIRE(a.ncols >= 1, "%s: ncols must be >= 1", who);
+        FM_REQUIRE((a.lo == nullptr) == (a.hi == nullptr), "%s: lo and hi go together", who);
+        for (int j = 0; j < a.nsel; ++j) {
+            const int K = a.sel_k[j];
+            FM_REQUIRE(K >= 1 && K <= FM_MAX_SORT_K, "%s: sort %d has K = %d, not 1..%d", who, j, K, FM_MAX_SORT_K);
+            FM_REQUIRE(a.coef_stride >= K + 1, "%s: coef_stride %d below K + 1 = %d", who, a.coef_stride, K + 1);
+            for (int k = 0; k < K; ++k)
+                FM_REQUIRE(a.sel_cols[j][k] >= 0 && a.sel_cols[j][k] < a.ncols,
+                           "%s: sort %d column %d outside the panel's %d", who, j, a.sel_cols[j][k], a.ncols);
+        }
+        FM_REQUIRE(a.coef != nullptr, "%s: null pointer", who);
+    }
+    FM_REQUIRE(a.seg_off && a.rec && a.cnt && a.status, "%s: null pointer", who);
+    const size_t lds = port_lds_bytes(a.max_seg_len);
+    const hipStream_t st = (hipStream_t)stream;
+    return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
+        if (vec) return launch_fdist<nt, vpt, VecSrc>(a, lds, st);
+        return pl ? launch_fdist<nt, vpt, DistSrc<true>>(a, lds, st) : launch_fdist<nt, vpt, DistSrc<false>>(a, lds, st);
     });
 }

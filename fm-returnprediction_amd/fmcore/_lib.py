@@ -28,6 +28,7 @@ FM_MAX_LEVELS = 3
 FM_MAX_PORTS = 20
 FM_MAX_SORTS = 16
 FM_MAX_SORT_K = 30
+FM_MAX_DIST_Q = 8
 FM_TS_FUSED_MAX_LDS = 128 * 1024
 FM_RANK_AVERAGE, FM_RANK_MIN, FM_RANK_MAX = 0, 1, 2
 FM_RANK_RAW, FM_RANK_PCT, FM_RANK_UNIFORM = 0, 1, 2
@@ -129,6 +130,18 @@ class FPortArgs(C.Structure):
     ]
 
 
+class FDistArgs(C.Structure):
+    _fields_ = [
+        ("forecast", _p), ("cols", _p), ("col_stride", _i64), ("hi_plane", _p), ("lo_plane", _p),
+        ("plane_stride", _i64), ("lo", _p), ("hi", _p), ("coef", _p), ("level", _p), ("seg_off", _p),
+        ("nrows", _i64), ("ncols", _i32), ("coef_stride", _i32), ("nseg", _i32), ("max_seg_len", _i32),
+        ("min_count", _i32), ("nsel", _i32), ("nq", _i32), ("pad_fdist", _i32), ("q", _f64 * FM_MAX_DIST_Q),
+        ("sel_k", _i32 * FM_MAX_SORTS), ("sel_level", _i32 * FM_MAX_SORTS),
+        ("sel_cols", (_i32 * FM_MAX_SORT_K) * FM_MAX_SORTS), ("rec", _p), ("cnt", _p), ("status", _p),
+        ("forecast_out", _p),
+    ]
+
+
 class RankArgs(C.Structure):
     _fields_ = [
         ("src", _p), ("src_stride", _i64), ("dst", _p), ("dst_stride", _i64), ("ncols", _i32),
@@ -177,6 +190,7 @@ _SIGS = {
     "fm_portfolio_sort": (_i32, [C.POINTER(PortArgs), _p]),
     "fm_forecast_portfolio_sort": (_i32, [C.POINTER(FPortArgs), _p]),
     "fm_lagged_coef": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p, _p]),
+    "fm_forecast_dist": (_i32, [C.POINTER(FDistArgs), _p]),
     "fm_rank_transform": (_i32, [C.POINTER(RankArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
@@ -194,7 +208,7 @@ EXPORTED = tuple(_SIGS)
 _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_args": SelectArgs,
             "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs,
             "fm_port_args": PortArgs, "fm_rank_args": RankArgs,
-            "fm_fport_args": FPortArgs}
+            "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs}
 
 _lib = None
 

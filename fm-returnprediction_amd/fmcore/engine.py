@@ -1333,6 +1333,132 @@ def portfolio_summary(p: Portfolios, nw_lags=4):
     return Summary(s.mean.view(n1, k), s.se.view(n1, k), s.tstat.view(n1, k), s.nobs.view(n1, k))
 
 
+@dataclass
+class ForecastDist:
+    rec: torch.Tensor      # [nsel, T, 2+nq] float64: mean, sd (ddof 1), the nq quantiles (NaN: status 0)
+    cnt: torch.Tensor      # [nsel, T] int32 eligible rows
+    status: torch.Tensor   # [nsel, T] int32: 1 = the month has at least min_count eligible rows
+    forecast: Optional[torch.Tensor] = None   # [nsel, rows] float64 (forecast_dist, on request)
+
+
+def _dist_plan(who, nsel, T, n, q, min_count, forecast_out, out, dev):
+    """What the two forecast-distribution entry points share: the levels, the ``ForecastDist`` to fill
+    (``out`` checked, else allocated) and ``fill(a, j0, m)``, which sets the shared fields of an
+    argument struct for the sorts j0 .. j0 + m."""
+    qs = [float(v) for v in q]
+    nq = min(len(qs), L.FM_MAX_DIST_Q)   # output shapes of a call the library will refuse
+    shapes = dict(rec=((nsel, T, 2 + nq), torch.float64), cnt=((nsel, T), torch.int32),
+                  status=((nsel, T), torch.int32))
+    if forecast_out:
+        shapes["forecast"] = ((nsel, n), torch.float64)
+    if out is None:
+        out = ForecastDist(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    for k, (sh, dt) in shapes.items():
+        t = getattr(out, k)
+        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+
+    def fill(a, j0, m):
+        a.nq, a.min_count, a.nsel, a.nseg, a.nrows = len(qs), int(min_count), m, T, n
+        for i, v in enumerate(qs[:L.FM_MAX_DIST_Q]):
+            a.q[i] = v
+        if nsel:
+            a.rec, a.cnt, a.status = out.rec[j0:].data_ptr(), out.cnt[j0:].data_ptr(), out.status[j0:].data_ptr()
+            a.forecast_out = out.forecast[j0:].data_ptr() if forecast_out else None
+        return a
+
+    return out, fill
+
+
+def forecast_dist(panel: DevicePanel, coef, sel, cuts: Cuts = None, level=None, q=(0.1, 0.9), min_count=1,
+                  forecast_out=False, out: "ForecastDist" = None):
+    """A14: for every sort j of ``sel`` = [(xs, min_level), ...] and every month, the count, mean,
+    ddof-1 standard deviation and ``q`` quantiles of the eligible rows' forecasts -- the forecast
+    of ``forecast_portfolio_sort`` (``coef`` [nsel, T, >= K+1], ``cuts``, ``level`` as there), bit
+    for bit, computed in the kernel's load phase from whichever layout the panel holds
+    (fm_forecast_dist; the definition is in fm_hip.h).  One launch per FM_MAX_SORTS sorts.  Returns
+    ``ForecastDist``; ``forecast_out``: also the forecasts [nsel, rows]; ``out``: a
+    ``ForecastDist`` of that shape to write into (else allocated)."""
+    src = _source(panel)
+    dev = src.device
+    n, T, C = panel.nrows, panel.nseg, src.ncols
+    nsel = len(sel)
+    sel = [([panel.col(c) if isinstance(c, str) else int(c) for c in xs], int(lv)) for xs, lv in sel]
+    coef = coef.contiguous()
+    if coef.dtype != torch.float64 or coef.dim() != 3 or coef.shape[0] != nsel or coef.shape[1] != T or \
+            coef.device != dev:
+        raise ValueError(f"forecast_dist: coef must be a float64 [{nsel}, {T}, >= K+1] tensor on {dev}")
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    lo = hi = None
+    if cuts is not None:
+        lo, hi = cuts.lo.contiguous(), cuts.hi.contiguous()
+        if tuple(lo.shape) != (C, T) or tuple(hi.shape) != (C, T):
+            raise ValueError(f"forecast_dist: the cuts must be [{C}, {T}] tables")
+    out, fill = _dist_plan("forecast_dist", nsel, T, n, q, min_count, forecast_out, out, dev)
+    for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
+        part = sel[j0:j0 + L.FM_MAX_SORTS]
+        a = fill(L.FDistArgs(), j0, len(part))
+        if src.f64 is not None:
+            a.cols, a.col_stride = src.ptr, src.stride
+        else:
+            a.hi_plane, a.lo_plane, a.plane_stride = src.hp, src.lp, src.pstride
+        a.ncols, a.lo, a.hi, a.level = C, _ptr(lo), _ptr(hi), _ptr(level)
+        a.seg_off, a.max_seg_len = panel.seg_off.data_ptr(), panel.max_seg_len
+        for j, (xs, lv) in enumerate(part):
+            a.sel_k[j], a.sel_level[j] = len(xs), lv
+            for k, c in enumerate(xs[:L.FM_MAX_SORT_K]):
+                a.sel_cols[j][k] = c
+        a.coef, a.coef_stride = coef[j0:].data_ptr() if nsel else None, coef.stride(1)
+        _kcall("fm_forecast_dist", "fm_forecast_dist", L.C.byref(a), _stream())
+        _remember("fm_forecast_dist", "fm_forecast_dist", a, src, panel.planes, panel.seg_off, coef, lo, hi, level, out)
+    return out
+
+
+def forecast_dist_vector(seg_off, forecast, level=None, min_level=0, q=(0.1, 0.9), min_count=1, max_seg_len=None):
+    """A14 on forecast vectors the caller holds: ``forecast`` float64 [rows] or [nsel, rows] on the
+    device, months ``seg_off`` int64 [T+1]; eligible rows are the finite forecasts with ``level`` >=
+    ``min_level`` (one value, or one per vector).  Returns ``ForecastDist`` with a leading [nsel]
+    dimension (1 for a 1-D forecast).  ``max_seg_len``: the longest month if the caller knows it
+    (otherwise read from ``seg_off``, one host sync)."""
+    dev = forecast.device
+    if forecast.dtype != torch.float64 or forecast.dim() not in (1, 2):
+        raise ValueError("forecast_dist_vector: forecast must be a float64 [rows] or [nsel, rows] tensor")
+    forecast = forecast.view(1, -1) if forecast.dim() == 1 else forecast
+    forecast = forecast.contiguous()
+    nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("forecast_dist_vector: seg_off must be an int64 [T+1] tensor on the forecast's device")
+    seg_off = seg_off.contiguous()
+    T = int(seg_off.shape[0]) - 1
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    levels = [int(min_level)] * nsel if np.ndim(min_level) == 0 else [int(v) for v in min_level]
+    if len(levels) != nsel:
+        raise ValueError(f"forecast_dist_vector: min_level must be one value or {nsel}")
+    if max_seg_len is None:
+        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    out, fill = _dist_plan("forecast_dist_vector", nsel, T, n, q, min_count, False, None, dev)
+    for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
+        m = min(nsel - j0, L.FM_MAX_SORTS)
+        a = fill(L.FDistArgs(), j0, m)
+        a.forecast = forecast[j0:].data_ptr() if nsel else None
+        a.level, a.seg_off, a.max_seg_len = _ptr(level), seg_off.data_ptr(), int(max_seg_len)
+        for j in range(m):
+            a.sel_level[j] = levels[j0 + j]
+        _kcall("fm_forecast_dist", "fm_forecast_dist", L.C.byref(a), _stream())
+        _remember("fm_forecast_dist", "fm_forecast_dist", a, seg_off, forecast, level, out)
+    return out
+
+
+def forecast_dist_summary(d: ForecastDist, nw_lags=4):
+    """FM mean, Newey-West s.e., t and nobs of the 2 + nq monthly series of ``d.rec`` over the
+    months with status 1, NaN entries dropped per series (the sd of a one-row month) ->
+    ``Summary`` with [nsel, 2+nq] tensors: every sort is one problem of the two launches
+    ``portfolio_summary`` issues."""
+    S, T, k = d.rec.shape
+    ix = ts_compact(d.status, 1, T, T, S)
+    return ts_summary(d.rec, k, T * k, ix, T, S, k, nw_lags)
+
+
 # fm_rank_transform's month limit (FM_RANK_MAX_ROWS): up to 16,384 rows one workgroup per (month,
 # column) sorts the month's keys in LDS; a longer month is ranked in parts of 16,384 rows, at a cost
 # quadratic in the part count, so four parts are the limit

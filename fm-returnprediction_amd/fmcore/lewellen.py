@@ -9,6 +9,8 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
  -> lagged-rolling forecasts and predictive-slope FM summaries (build-defined A7/A8)
  -> optionally (``PipelineConfig.portfolios``) the forecast-sorted portfolios of every Table-2
     problem (paper Table 5, build-defined A12) in one more launch that forecasts and sorts
+ -> optionally (``PipelineConfig.forecast_dist``) each month's mean, standard deviation and
+    quantiles of those forecasts (paper Table 3, build-defined A14), likewise in one launch
 All stages are libfm_hip kernels; the panel is read from HBM twice (cuts, Gram).
 """
 from __future__ import annotations
@@ -85,6 +87,11 @@ class PipelineConfig:
     portfolios: Optional[int] = field(default=None, kw_only=True)
     portfolio_q: Optional[Sequence[float]] = field(default=None, kw_only=True)   # nport - 1 levels (None: k / nport)
     portfolio_nyse_breakpoints: bool = field(default=False, kw_only=True)        # breakpoints from the NYSE rows only
+    # A14 inside the pipeline (paper Table 3's univariate properties): each month's cross-sectional
+    # mean, standard deviation and ``forecast_dist_q`` quantiles of the same forecasts, over the same
+    # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
+    forecast_dist: bool = field(default=False, kw_only=True)
+    forecast_dist_q: Sequence[float] = field(default=(0.1, 0.9), kw_only=True)
     rank: Optional[str] = None     # A13: predictors -> per-month ranks, a scale name ("raw", "pct", "uniform")
 
 
@@ -105,6 +112,9 @@ class PipelineResult:
     portfolios: Optional[E.Portfolios] = None        # cfg.portfolios: tensors with a leading [nsort] dimension
     portfolio_summary: Optional[E.Summary] = None    # [nsort, nport+1, 4]
     portfolio_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
+    forecast_dist: Optional[E.ForecastDist] = None       # cfg.forecast_dist: [nsort, T, 2+nq] and [nsort, T]
+    forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
+    forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
 
 
 def build_models(panel: E.DevicePanel, model_cols: Dict[str, List[str]], y="retx", fig1=True,
@@ -212,24 +222,32 @@ def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo
 def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=None, y="retx"):
     cfg = cfg or PipelineConfig()
     model_cols = model_cols or table2_models()
-    if cfg.portfolios is not None:
-        if cfg.standardize:
-            raise ValueError("PipelineConfig: portfolios excludes standardize (coefficients on z-scores "
+    for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist")):
+        if on and cfg.standardize:
+            raise ValueError(f"PipelineConfig: {what} excludes standardize (coefficients on z-scores "
                              "need the moment tables)")
-        if not cfg.forecasts:
-            raise ValueError("PipelineConfig: portfolios needs forecasts=True (the lagged rolling coefficients)")
+        if on and not cfg.forecasts:
+            raise ValueError(f"PipelineConfig: {what} needs forecasts=True (the lagged rolling coefficients)")
     res, names, cuts, level, bp, gpanel, models = _local_stage(panel, cfg, model_cols, y)
     ix, summ, roll, pred, pst = time_series_stage(res, cfg)
     psumm = None
     if cfg.forecasts:
         psumm, _ = E.summarize_predictive(pred, pst, cfg.nw_lags)
     ports = port_summ = port_probs = None
+    dist = dist_summ = dist_probs = None
+    if cfg.portfolios is not None or cfg.forecast_dist:
+        # Tables 5 and 3: every Table-2 problem's forecast, sorted or summarized in one launch each
+        # on the panel the Gram read, with the pipeline's cuts and the coefficient rows the
+        # predictive stage read
+        probs = [k for k, p in enumerate(res.problems) if names[p.model] != "Figure 1"]
+        coef = E.lagged_coefficients(roll, ix, probs, cfg.lag)
+        sel = [(models[res.problems[k].model].xs, res.problems[k].level) for k in probs]
+    if cfg.forecast_dist:
+        dist_probs = probs
+        dist = E.forecast_dist(gpanel, coef, sel, cuts=cuts, level=level, q=cfg.forecast_dist_q)
+        dist_summ = E.forecast_dist_summary(dist, cfg.nw_lags)
     if cfg.portfolios is not None:
-        # Table 5: every Table-2 problem's sort, forecast and all, in one launch on the panel the
-        # Gram read, with the pipeline's cuts and the coefficient rows the predictive stage read
-        port_probs = [k for k, p in enumerate(res.problems) if names[p.model] != "Figure 1"]
-        coef = E.lagged_coefficients(roll, ix, port_probs, cfg.lag)
-        sel = [(models[res.problems[k].model].xs, res.problems[k].level) for k in port_probs]
+        port_probs = probs
         ports = E.forecast_portfolio_sort(gpanel, coef, sel, cuts=cuts, ret=gpanel.col(y), weight=gpanel.me,
                                           level=level, nyse=gpanel.nyse, nport=cfg.portfolios, q=cfg.portfolio_q,
                                           nyse_breakpoints=cfg.portfolio_nyse_breakpoints)
@@ -237,7 +255,8 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     return PipelineResult(model_names=names, model_cols=dict(model_cols, **({"Figure 1": FIG1_VARS} if cfg.fig1 else {})),
                           res=res, ix=ix, summary=summ, rolling=roll, pred=pred, pred_status=pst,
                           pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
-                          portfolio_summary=port_summ, portfolio_problems=port_probs)
+                          portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
+                          forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

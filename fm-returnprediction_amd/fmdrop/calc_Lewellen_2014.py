@@ -9,7 +9,8 @@ Mirrored (same names, signatures, return types and row/column/index order):
   create_figure_1  reference :871-957   F1 OLS + 120-month rolling means on device
 Extensions the north star names (not in the reference; parity unpinned):
   standardize, rank_transform, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
-  predictive_slope_regressions, forecast_sorted_portfolios, lewellen_pipeline.
+  predictive_slope_regressions, forecast_sorted_portfolios, forecast_distribution,
+  lewellen_pipeline, build_table_5, build_table_3.
 Firm-axis characteristic builders (§8(f) row 2; one fused device pass, fm_firm_chars):
   calc_log_size, calc_log_bm, calc_return_12_2, calc_accruals, calc_roa,
   calc_log_assets_growth, calc_dy, calc_log_return_13_36, calc_log_issues_12,
@@ -719,6 +720,50 @@ def _portfolio_frames(status, rec, cnt, mean, tstat, nobs, months, nport, date_c
     return monthly, summary
 
 
+def _dist_columns(q):
+    """Table 3's column names of the quantile levels ``q``: p10, p90, p2.5, ..."""
+    return ["p%g" % (100.0 * float(v)) for v in q]
+
+
+def forecast_distribution(df: pd.DataFrame, forecast, universe: str = None, q=(0.1, 0.9),
+                          date_col: str = "mthcaldt", nw_lags: int = 4):
+    """A14 (paper Table 3, univariate properties): each month's cross-sectional mean, standard
+    deviation (ddof 1) and np.quantile levels ``q`` of ``forecast`` over the rows with a finite
+    forecast, on the device (fm_forecast_dist).  ``universe`` in {None, "all_but_tiny", "large"}
+    keeps the rows of that get_subsets universe (from ``me`` and ``primaryexch``).
+    Returns (monthly, summary): ``monthly`` is indexed by month with columns mean, std, one per
+    level (p10, p90) and n, months without an eligible row absent; ``summary`` is indexed by those
+    columns (not n) with columns mean / tstat / nobs: the time-series average and its
+    Newey-West(nw_lags) t-statistic."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    f = np.asarray(forecast, dtype=np.float64)
+    if f.shape != (len(df),):
+        raise ValueError("forecast must hold one value per row of df")
+    order = np.lexsort((df["permno"].to_numpy(), df[date_col].to_numpy()))
+    d = df.iloc[order]
+    me = _api.as_f64(d["me"]) if universe is not None else None
+    nyse = (d["primaryexch"] == "N").to_numpy().astype(np.uint8) if universe is not None else None
+    panel = _E.panel_from_arrays([f[order]], ["forecast"], d[date_col].values, me=me, nyse=nyse)
+    level = _E.universe(panel)[2] if universe is not None else None
+    dist = _E.forecast_dist_vector(panel.seg_off, panel.cols[0], level=level, min_level=_UNIVERSE_LEVEL[universe],
+                                   q=q, max_seg_len=panel.max_seg_len)
+    s = _E.forecast_dist_summary(dist, nw_lags)
+    return _dist_frames(dist.status[0].cpu().numpy(), dist.rec[0].cpu().numpy(), dist.cnt[0].cpu().numpy(),
+                        s.mean[0].cpu().numpy(), s.tstat[0].cpu().numpy(), s.nobs[0].cpu().numpy(), panel.months, q,
+                        date_col)
+
+
+def _dist_frames(status, rec, cnt, mean, tstat, nobs, months, q, date_col="mthcaldt"):
+    """forecast_distribution's (monthly, summary) frames of one forecast's host arrays."""
+    cols = ["mean", "std"] + _dist_columns(q)
+    ok = status == 1
+    monthly = pd.DataFrame(rec[ok], index=pd.Index(np.asarray(months)[ok], name=date_col), columns=cols)
+    monthly["n"] = cnt[ok].astype(np.int64)
+    summary = pd.DataFrame({"mean": mean, "tstat": tstat, "nobs": nobs}, index=pd.Index(cols, name="statistic"))
+    return monthly, summary
+
+
 def _pipeline_panel(crsp_comp: pd.DataFrame, variables_dict: dict = None):
     """The device panel and the Table-2 models of a crsp_comp frame (rows by (month, permno))."""
     vd = variables_dict or _LW.VARIABLES_DICT
@@ -762,3 +807,27 @@ def build_table_5(crsp_comp: pd.DataFrame, variables_dict: dict = None, nport: i
         key = (out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level])
         frames[key] = _portfolio_frames(*(h[j] for h in host), panel.months, int(nport))
     return frames
+
+
+def build_table_3(crsp_comp: pd.DataFrame, variables_dict: dict = None, q=(0.1, 0.9), **cfg):
+    """Paper Table 3 from ONE device pipeline run (build-defined; no reference line): for every
+    Table-2 model and universe, the univariate properties of the out-of-sample forecast from that
+    problem's lagged rolling coefficients and the winsorized characteristics -- the time-series
+    averages of each month's cross-sectional mean (``Avg``), standard deviation (``Std``) and
+    ``q`` quantiles (``p10``, ``p90``) -- beside its predictive ability: the Fama-MacBeth slope of
+    returns on the forecast, its Newey-West standard error and t-statistic and the average R2
+    (``PipelineResult.pred_summary`` as it stands).  ``cfg``: further PipelineConfig fields
+    (window, min_periods, lag, nw_lags, ...).  Returns a DataFrame indexed by (model, universe)."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    pcfg = _LW.PipelineConfig(**dict(cfg, forecast_dist=True, forecast_dist_q=tuple(q)))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    dmean = out.forecast_dist_summary.mean.cpu().numpy()
+    ps = out.pred_summary
+    pmean, pse, pt = ps.mean.cpu().numpy(), ps.se.cpu().numpy(), ps.tstat.cpu().numpy()
+    keys, rows = [], []
+    for j, k in enumerate(out.forecast_dist_problems):
+        prob = out.res.problems[k]
+        keys.append((out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level]))
+        rows.append(list(dmean[j]) + [pmean[k, 0], pse[k, 0], pt[k, 0], pmean[k, 1]])
+    return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(keys, names=["model", "universe"]),
+                        columns=["Avg", "Std"] + _dist_columns(q) + ["Slope", "S.E.", "t-stat", "R2"])

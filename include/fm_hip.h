@@ -47,6 +47,9 @@
  *   fm_forecast_portfolio_sort, fm_lagged_coef <- build-defined extension: the same sorts with
  *                      the clipped lagged-rolling forecast computed in the sort kernel's load
  *                      phase (Table 5 inside the device pipeline); no reference line
+ *   fm_forecast_dist <- build-defined extension A14: per-month mean, standard deviation and
+ *                      quantiles of the forecasts (paper Table 3's univariate properties); no
+ *                      reference line
  *   fm_rank_transform <- build-defined extension A13: per-month cross-sectional ranks of the
  *                      characteristics (pandas groupby(month)[x].rank); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
@@ -195,7 +198,7 @@ const char* fm_last_error(void);
 int fm_abi_sizes(int32_t* gram_args, int32_t* solve_args);
 /* sizeof the named argument struct ("fm_gram_args", "fm_solve_args", "fm_select_args",
  * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args", "fm_rank_args",
- * "fm_fport_args"); -1 for an unknown name.  Bindings
+ * "fm_fport_args", "fm_fdist_args"); -1 for an unknown name.  Bindings
  * check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
 int fm_device_arch(char* buf, int32_t len);
@@ -525,6 +528,70 @@ int fm_forecast_portfolio_sort(const fm_fport_args* args, void* stream);
 int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count, int32_t nseg,
                    int32_t nprob, int32_t pmax, const int32_t* problems, int32_t nsel, int32_t lag,
                    double* out, void* stream);
+
+/* fm_forecast_dist: per month, the cross-sectional mean, standard deviation and quantiles of
+ * nsel expected-return forecasts in one launch, grid (month, sort) (build-defined extension A14;
+ * no reference line; paper Table 3, "univariate properties").  Rows sorted by (month, permno),
+ * months seg_off[nseg+1] of at most 16,384 rows (it shares fm_portfolio_sort's selection; longer:
+ * FM_ETOOBIG before any launch, outputs untouched).  Exactly one forecast source, anything else
+ * FM_EINVAL:
+ *   forecast [nsel][nrows]: the caller's vectors (forecast_out must then be NULL), or
+ *   cols / col_stride, or hi_plane / lo_plane / plane_stride: the panel, and sort j's forecast
+ *   is fm_forecast_portfolio_sort's, bit for bit: with K = sel_k[j], columns sel_cols[j][0..K),
+ *   c = coef[(j * nseg + t) * coef_stride + 0..K] and lo / hi [ncols][nseg] (a NaN bound is
+ *   ignored; both NULL: no clipping), F = c[0], then for k = 1..K in order
+ *   F = F + c[k] * clip(x_k), every operation rounded on its own; forecast_out (optional)
+ *   receives every row's F.
+ * Per (sort j, month t), all outputs with a leading [nsel] dimension:
+ *   eligible rows: isfinite(F) and level >= sel_level[j] (level NULL: every row);
+ *   cnt    = the number of eligible rows;
+ *   cnt < min_count: status = 0 and rec[0..2+nq) NaN; otherwise status = 1 and
+ *   rec[0] = the mean of F over the eligible rows: sum / cnt;
+ *   rec[1] = the ddof-1 standard deviation, two passes: sqrt(sum((F - rec[0])^2) / (cnt - 1)),
+ *            NaN when cnt == 1;
+ *   rec[2+i] = numpy 'linear' quantile q[i] of the eligible forecasts (exact order statistics;
+ *            the sign of an exactly-zero quantile is not specified).
+ * Both sums run in one fixed order: the month's rows in row order are cut into tiles of 64 (rows
+ * that are not eligible, and rows past the month's end, count as +0.0); a tile is summed by the
+ * wave butterfly (lane l adds the value of lane l ^ 32, then ^ 16, 8, 4, 2, 1); lane l then adds
+ * the tile sums l, l + 64, l + 128, ... in that order, starting from +0.0, and the 64 lane sums go
+ * through the same butterfly.  So a month's bits depend on that month's rows alone: not on the
+ * source, the panel's layout, the grid, the other months or max_seg_len (which picks the
+ * workgroup's shape); two calls, or a month-sharded call, give the same bits.  nsel == 0 or
+ * nseg == 0 is a valid empty call.  Zero-initialize the struct (it grows at the end). */
+#define FM_MAX_DIST_Q 8
+typedef struct fm_fdist_args {
+    const double* forecast;      /* [nsel][nrows] forecast vectors, or NULL (a panel source) */
+    const double* cols;          /* [ncols][col_stride], or NULL */
+    int64_t col_stride;
+    const uint32_t* hi_plane;    /* [ncols][plane_stride] high / low words, or NULL */
+    const uint32_t* lo_plane;
+    int64_t plane_stride;
+    const double* lo;            /* [ncols][nseg] clip bounds, or both NULL */
+    const double* hi;
+    const double* coef;          /* [nsel][nseg][coef_stride] (panel sources) */
+    const uint8_t* level;        /* [rows] universe level or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int64_t nrows;               /* seg_off[nseg]: the row stride of forecast / forecast_out */
+    int32_t ncols;
+    int32_t coef_stride;
+    int32_t nseg;
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t min_count;           /* >= 1 */
+    int32_t nsel;                /* 0 .. FM_MAX_SORTS */
+    int32_t nq;                  /* 0 .. FM_MAX_DIST_Q */
+    int32_t pad_fdist;
+    double q[FM_MAX_DIST_Q];     /* [nq] levels, strictly ascending in (0, 1) */
+    int32_t sel_k[FM_MAX_SORTS];
+    int32_t sel_level[FM_MAX_SORTS];
+    int32_t sel_cols[FM_MAX_SORTS][FM_MAX_SORT_K];
+    double* rec;                 /* [nsel][nseg][2+nq] */
+    int32_t* cnt;                /* [nsel][nseg] */
+    uint32_t* status;            /* [nsel][nseg] */
+    double* forecast_out;        /* [nsel][nrows] or NULL */
+} fm_fdist_args;
+
+int fm_forecast_dist(const fm_fdist_args* args, void* stream);
 
 /* fm_rank_transform: every chosen column's cross-sectional rank within its month (build-defined
  * extension A13; no reference line).  It is pandas' groupby(month)[x].rank(method, pct) and is
