@@ -93,6 +93,7 @@ extern "C" int fm_segment_moments(const double* cols, int64_t col_stride, int32_
     using namespace fm;
     FM_REQUIRE(cols && seg_off && count && mean && sd, "fm_segment_moments: null pointer");
     FM_REQUIRE(ncols > 0 && ncols <= 65535, "fm_segment_moments: bad ncols");
+    FM_REQUIRE(nseg >= 0, "fm_segment_moments: bad nseg");
     if (nseg == 0) return FM_OK;
     hipLaunchKernelGGL(moments_kernel, dim3(nseg, ncols), dim3(MT), 0, (hipStream_t)stream, cols,
                        col_stride, seg_off, nseg, level, min_level, finite_only, count, mean, sd);
@@ -106,6 +107,7 @@ extern "C" int fm_distinct_count(const int64_t* ids, int64_t nrows, const double
                                  int64_t id_range, uint32_t* bitmap, int32_t* out, void* stream) {
     using namespace fm;
     FM_REQUIRE(ids && cols && bitmap && out, "fm_distinct_count: null pointer");
+    FM_REQUIRE(nrows >= 0 && ncols > 0, "fm_distinct_count: bad sizes");
     FM_REQUIRE(id_range > 0 && id_range <= (1ll << 34), "fm_distinct_count: id range out of bounds");
     const int64_t words = (id_range + 31) / 32;
     hipStream_t st = (hipStream_t)stream;

@@ -645,6 +645,14 @@ typedef struct fm_rank_args {
 
 int fm_rank_transform(const fm_rank_args* args, void* stream);
 
+/* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
+ * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
+ * count[c * nseg + s], mean (NaN for count 0) and ddof=1 standard deviation (NaN for count
+ * < 2), two passes; with finite_only == 0 an inf among the rows gives IEEE results (mean
+ * +-inf or NaN, sd NaN).  fm_distinct_count: out[c] = the number of distinct ids among column
+ * c's rows; every id lies in [id_lo, id_lo + id_range), 1 <= id_range <= 2^34; bitmap is a
+ * workspace of ncols * ceil(id_range / 32) words.  Sizes below zero, ncols < 1 and an id
+ * range out of bounds return FM_EINVAL before any HIP call. */
 int fm_segment_moments(const double* cols, int64_t col_stride, int32_t ncols,
                        const int64_t* seg_off, int32_t nseg, const uint8_t* level,
                        int32_t min_level, int32_t finite_only, int32_t* count, double* mean,
