@@ -3,8 +3,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <string>
-
 #include "fm_common.h"
 
 namespace fm {
@@ -31,25 +29,11 @@ extern "C" const char* fm_version(void) { return "libfm_hip 0.1.0 (gfx950)"; }
 
 extern "C" const char* fm_last_error(void) { return fm::g_err; }
 
-extern "C" int fm_abi_sizes(int32_t* gram_args, int32_t* solve_args) {
-    *gram_args = (int32_t)sizeof(fm_gram_args);
-    *solve_args = (int32_t)sizeof(fm_solve_args);
-    return FM_OK;
-}
-
 extern "C" int64_t fm_struct_size(const char* name) {
     if (name == nullptr) return -1;
-    const std::string n(name);
-    if (n == "fm_gram_args") return (int64_t)sizeof(fm_gram_args);
-    if (n == "fm_solve_args") return (int64_t)sizeof(fm_solve_args);
-    if (n == "fm_select_args") return (int64_t)sizeof(fm_select_args);
-    if (n == "fm_universe_args") return (int64_t)sizeof(fm_universe_args);
-    if (n == "fm_ts_args") return (int64_t)sizeof(fm_ts_args);
-    if (n == "fm_chars_args") return (int64_t)sizeof(fm_chars_args);
-    if (n == "fm_port_args") return (int64_t)sizeof(fm_port_args);
-    if (n == "fm_rank_args") return (int64_t)sizeof(fm_rank_args);
-    if (n == "fm_fport_args") return (int64_t)sizeof(fm_fport_args);
-    if (n == "fm_fdist_args") return (int64_t)sizeof(fm_fdist_args);
+#define FM_SIZE_OF(s) if (strcmp(name, #s) == 0) return (int64_t)sizeof(s);
+    FM_ARG_STRUCTS(FM_SIZE_OF)
+#undef FM_SIZE_OF
     return -1;
 }
 

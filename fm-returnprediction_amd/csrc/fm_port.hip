@@ -21,7 +21,7 @@
 // than 5,120 rows re-read return and weight per term, from the cache).
 //
 // fm_forecast_portfolio_sort runs the same four phases (the same kernel template, instantiated
-// with FusedSrc) over a grid of (month, sort), with phase 1's load replaced by the forecast itself:
+// with PanelSrc) over a grid of (month, sort), with phase 1's load replaced by the forecast itself:
 // F = c0 + sum_k c_k clip(x_k) from the panel's own layout (FP64 columns or the split planes),
 // predictor k in the outer loop (the month's c_k and cuts are wave-uniform) and the thread's
 // VPT rows in the inner one (VPT independent loads in flight), accumulated in the fe registers
@@ -77,19 +77,21 @@ __device__ __forceinline__ void lds_bitonic(uint64_t* buf, int P) {
 }
 
 // What a month's workgroup sorts by.  PlainSrc: the caller's forecast and return vectors
-// (fm_portfolio_sort).  FusedSrc<PL>: sort j of fm_forecast_portfolio_sort, panel values from the
-// FP64 columns or (PL) from the planes, two 4-byte loads joined in registers (PanelSrc, over
-// the argument struct that holds the panel).
+// (fm_portfolio_sort).  PanelSrc<PL>: sort j of the fm_forecast_src that fm_fport_args and
+// fm_fdist_args embed as `src`, panel values from the FP64 columns or (PL) from the planes, two
+// 4-byte loads joined in registers.
 struct PlainSrc {
     static constexpr bool FUSED = false;
     __device__ static PlainSrc make(const fm_port_args&) { return {}; }
 };
 
-template <bool PL, class A>
+template <bool PL>
 struct PanelSrc {
     static constexpr bool FUSED = true;
-    const A& a;
+    const fm_forecast_src& a;
     int j;   // blockIdx.y
+    template <class A>
+    __device__ static PanelSrc make(const A& args) { return {args.src, (int)blockIdx.y}; }
     __device__ __forceinline__ double value(int col, int64_t row) const {
         if constexpr (PL) {
             const int64_t o = (int64_t)col * a.plane_stride + row;
@@ -100,23 +102,16 @@ struct PanelSrc {
         }
     }
 };
-template <bool PL>
-struct FusedSrc : PanelSrc<PL, fm_fport_args> {
-    __device__ static FusedSrc make(const fm_fport_args& a) { return {{a, (int)blockIdx.y}}; }
-};
-template <bool PL>   // the same view of fm_forecast_dist's panel
-struct DistSrc : PanelSrc<PL, fm_fdist_args> {
-    __device__ static DistSrc make(const fm_fdist_args& a) { return {{a, (int)blockIdx.y}}; }
-};
 
-// The fused load of month s (L > 0 rows from r0) of sort src.j: fe[v] = the forecast of the
-// thread's row (w * VPT + v) * 64 + lane (clamped to the month's last row), written to
+// The fused load of month s of nseg (L > 0 rows from r0) of sort src.j: fe[v] = the forecast of
+// the thread's row (w * VPT + v) * 64 + lane (clamped to the month's last row), written to
 // forecast_out at ro on request.  Predictor k outside (c_k and the month's cuts are
 // wave-uniform), the thread's rows inside (VPT independent loads in flight); every product and
 // every sum rounds on its own (-ffp-contract=off), in fm_forecast's order.
-template <int VPT, class Src, class A>
-__device__ __forceinline__ void fused_forecast(const Src& src, const A& a, int s, int64_t so, int64_t ro,
+template <int VPT, class Src>
+__device__ __forceinline__ void fused_forecast(const Src& src, int nseg, int s, int64_t so, int64_t ro,
                                                int64_t r0, int L, int w, int lane, double (&fe)[VPT]) {
+    const fm_forecast_src& a = src.a;
     const int last = L - 1;
     const int K = a.sel_k[src.j];
     const double* __restrict__ c = a.coef + so * a.coef_stride;
@@ -127,8 +122,8 @@ __device__ __forceinline__ void fused_forecast(const Src& src, const A& a, int s
     for (int k = 0; k < K; ++k) {
         const int col = a.sel_cols[src.j][k];
         const double ck = c[1 + k];
-        const double lo = a.lo != nullptr ? a.lo[(int64_t)col * a.nseg + s] : NAN;
-        const double hi = a.hi != nullptr ? a.hi[(int64_t)col * a.nseg + s] : NAN;
+        const double lo = a.lo != nullptr ? a.lo[(int64_t)col * nseg + s] : NAN;
+        const double hi = a.hi != nullptr ? a.hi[(int64_t)col * nseg + s] : NAN;
         double x[VPT];
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {
@@ -153,7 +148,8 @@ __device__ __forceinline__ void fused_forecast(const Src& src, const A& a, int s
 }
 
 // One month (of one sort) by the NT-thread workgroup: A is fm_port_args with PlainSrc,
-// fm_fport_args with FusedSrc (the fields both share have the same names).  The body stays in
+// fm_fport_args with PanelSrc (the fields both share have the same names; the forecast's own
+// are those of the embedded fm_forecast_src, a.src).  The body stays in
 // the kernel itself: behind an inlined device function the 1024 x 16 form allocates 18 more VGPRs
 // (the fused load alone, fused_forecast above, leaves every form's allocation as it was).
 template <int NT, int VPT, class Src = PlainSrc, class A = fm_port_args>
@@ -184,8 +180,8 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(A a) {
     int min_level;
     if constexpr (FUSED) {
         so += (int64_t)src.j * a.nseg;
-        ro += (int64_t)src.j * a.nrows;
-        min_level = a.sel_level[src.j];
+        ro += (int64_t)src.j * a.src.nrows;
+        min_level = a.src.sel_level[src.j];
     } else {
         min_level = a.min_level;
     }
@@ -199,7 +195,7 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void port_kernel(A a) {
     if (L > 0) {        // block-uniform
         const int last = L - 1;
         if constexpr (FUSED) {
-            fused_forecast<VPT>(src, a, s, so, ro, r0, L, w, lane, fe);
+            fused_forecast<VPT>(src, a.nseg, s, so, ro, r0, L, w, lane, fe);
         }
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
@@ -561,6 +557,37 @@ int check_sort_args(const A& a, const char* who) {
     return FM_OK;
 }
 
+// What both fused entry points ask of their fm_forecast_src over nseg months; vec: the caller's
+// own forecast vectors are the source (fm_forecast_dist), so f holds no panel
+int check_forecast_src(const fm_forecast_src& f, int nseg, const char* who, bool vec = false) {
+    FM_REQUIRE(nseg >= 0 && f.nrows >= 0, "%s: bad sizes", who);
+    FM_REQUIRE(f.nsel >= 0 && f.nsel <= FM_MAX_SORTS, "%s: nsel must be 0..%d", who, FM_MAX_SORTS);
+    if (nseg == 0 || f.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
+    for (int j = 0; j < f.nsel; ++j)
+        FM_REQUIRE(f.sel_level[j] >= 0 && f.sel_level[j] <= 255, "%s: sel_level must be 0..255", who);
+    const bool f64 = f.cols != nullptr, pl = f.hi_plane != nullptr || f.lo_plane != nullptr;
+    if (vec) {
+        FM_REQUIRE(!f64 && !pl, "%s: exactly one of forecast, cols and the planes must be given", who);
+        FM_REQUIRE(f.forecast_out == nullptr, "%s: forecast_out goes with a panel source", who);
+        return FM_OK;
+    }
+    FM_REQUIRE(f64 != pl, "%s: exactly one of cols and the planes must be given", who);
+    FM_REQUIRE(!pl || (f.hi_plane != nullptr && f.lo_plane != nullptr), "%s: both planes are needed", who);
+    FM_REQUIRE((f64 ? f.col_stride : f.plane_stride) >= f.nrows, "%s: stride below the row count", who);
+    FM_REQUIRE(f.ncols >= 1, "%s: ncols must be >= 1", who);
+    FM_REQUIRE((f.lo == nullptr) == (f.hi == nullptr), "%s: lo and hi go together", who);
+    for (int j = 0; j < f.nsel; ++j) {
+        const int K = f.sel_k[j];
+        FM_REQUIRE(K >= 1 && K <= FM_MAX_SORT_K, "%s: sort %d has K = %d, not 1..%d", who, j, K, FM_MAX_SORT_K);
+        FM_REQUIRE(f.coef_stride >= K + 1, "%s: coef_stride %d below K + 1 = %d", who, f.coef_stride, K + 1);
+        for (int k = 0; k < K; ++k)
+            FM_REQUIRE(f.sel_cols[j][k] >= 0 && f.sel_cols[j][k] < f.ncols,
+                       "%s: sort %d column %d outside the panel's %d", who, j, f.sel_cols[j][k], f.ncols);
+    }
+    FM_REQUIRE(f.coef != nullptr, "%s: null pointer", who);
+    return FM_OK;
+}
+
 // ---- fm_forecast_dist (extension A14; paper Table 3) -----------------------------------------
 // Per (month, sort): the count, mean, ddof-1 standard deviation and nq quantiles of the eligible
 // forecasts.  Phases 1-2 are port_kernel's (the same loads, fused_forecast, the same sample select
@@ -737,15 +764,15 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fdist_kernel(fm_fdist_a
     const int64_t r0 = a.seg_off[s];
     int L = (int)(a.seg_off[s + 1] - r0);
     L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
-    const int64_t so = s + (int64_t)src.j * a.nseg, ro = r0 + (int64_t)src.j * a.nrows;
-    const int min_level = a.sel_level[src.j];
+    const int64_t so = s + (int64_t)src.j * a.nseg, ro = r0 + (int64_t)src.j * a.src.nrows;
+    const int min_level = a.src.sel_level[src.j];
 
     // ---- 1. load, eligibility ---------------------------------------------------------------
     double fe[VPT];     // the eligible rows' forecasts, NaN otherwise
     uint32_t bpm = 0;   // bit v: row v of this thread is eligible
     if (L > 0) {        // block-uniform
         const int last = L - 1;
-        if constexpr (FUSED) fused_forecast<VPT>(src, a, s, so, ro, r0, L, w, lane, fe);
+        if constexpr (FUSED) fused_forecast<VPT>(src, a.nseg, s, so, ro, r0, L, w, lane, fe);
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
             const int idx = (w * VPT + v) * WAVE + lane;
@@ -811,7 +838,7 @@ template <int NT, int VPT, class Src>
 int launch_fdist(const fm_fdist_args& a, size_t lds, hipStream_t st) {
     const char* who = "fm_forecast_dist";
     if (lds >= 64 * 1024 && raise_dynamic_lds<fdist_kernel<NT, VPT, Src>>(8 * pow2_ceil(NT * VPT), who) != FM_OK) return FM_EHIP;
-    hipLaunchKernelGGL((fdist_kernel<NT, VPT, Src>), dim3(a.nseg, a.nsel), dim3(NT), lds, st, a);
+    hipLaunchKernelGGL((fdist_kernel<NT, VPT, Src>), dim3(a.nseg, a.src.nsel), dim3(NT), lds, st, a);
     return check_launch(who);
 }
 
@@ -836,34 +863,21 @@ extern "C" int fm_portfolio_sort(const fm_port_args* args, void* stream) {
 
 extern "C" int fm_forecast_portfolio_sort(const fm_fport_args* args, void* stream) {
     using namespace fm;
-    FM_REQUIRE(args != nullptr, "fm_forecast_portfolio_sort: null args");
-    const fm_fport_args& a = *args;
-    FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0 && a.nrows >= 0, "fm_forecast_portfolio_sort: bad sizes");
-    FM_REQUIRE(a.nsel >= 0 && a.nsel <= FM_MAX_SORTS, "fm_forecast_portfolio_sort: nsel must be 0..%d", FM_MAX_SORTS);
-    if (const int rc = check_sort_args(a, "fm_forecast_portfolio_sort")) return rc;
-    if (a.nseg == 0 || a.nsel == 0) return FM_OK;   // nothing is read: an empty panel has no pointers
-    const bool f64 = a.cols != nullptr, pl = a.hi_plane != nullptr || a.lo_plane != nullptr;
-    FM_REQUIRE(f64 != pl, "fm_forecast_portfolio_sort: exactly one of cols and the planes must be given");
-    FM_REQUIRE(!pl || (a.hi_plane != nullptr && a.lo_plane != nullptr), "fm_forecast_portfolio_sort: both planes are needed");
-    FM_REQUIRE((f64 ? a.col_stride : a.plane_stride) >= a.nrows, "fm_forecast_portfolio_sort: stride below the row count");
-    FM_REQUIRE(a.ncols >= 1 && a.ret_col >= 0 && a.ret_col < a.ncols, "fm_forecast_portfolio_sort: ret_col outside the panel");
-    FM_REQUIRE((a.lo == nullptr) == (a.hi == nullptr), "fm_forecast_portfolio_sort: lo and hi go together");
-    for (int j = 0; j < a.nsel; ++j) {
-        const int K = a.sel_k[j];
-        FM_REQUIRE(K >= 1 && K <= FM_MAX_SORT_K, "fm_forecast_portfolio_sort: sort %d has K = %d, not 1..%d", j, K, FM_MAX_SORT_K);
-        FM_REQUIRE(a.coef_stride >= K + 1, "fm_forecast_portfolio_sort: coef_stride %d below K + 1 = %d", a.coef_stride, K + 1);
-        FM_REQUIRE(a.sel_level[j] >= 0 && a.sel_level[j] <= 255, "fm_forecast_portfolio_sort: sel_level must be 0..255");
-        for (int k = 0; k < K; ++k)
-            FM_REQUIRE(a.sel_cols[j][k] >= 0 && a.sel_cols[j][k] < a.ncols,
-                       "fm_forecast_portfolio_sort: sort %d column %d outside the panel's %d", j, a.sel_cols[j][k], a.ncols);
-    }
-    FM_REQUIRE(a.coef && a.seg_off && a.rec && a.cnt && a.status, "fm_forecast_portfolio_sort: null pointer");
     const char* who = "fm_forecast_portfolio_sort";
-    const dim3 grid(a.nseg, a.nsel);
+    FM_REQUIRE(args != nullptr, "%s: null args", who);
+    const fm_fport_args& a = *args;
+    FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
+    if (const int rc = check_sort_args(a, who)) return rc;
+    if (const int rc = check_forecast_src(a.src, a.nseg, who)) return rc;
+    if (a.nseg == 0 || a.src.nsel == 0) return FM_OK;   // nothing is read: an empty panel has no pointers
+    FM_REQUIRE(a.ret_col >= 0 && a.ret_col < a.src.ncols, "%s: ret_col outside the panel", who);
+    FM_REQUIRE(a.seg_off && a.rec && a.cnt && a.status, "%s: null pointer", who);
+    const bool pl = a.src.hi_plane != nullptr;
+    const dim3 grid(a.nseg, a.src.nsel);
     const size_t lds = port_lds_bytes(a.max_seg_len);
     return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
-        return pl ? launch<nt, vpt, FusedSrc<true>>(a, grid, lds, who, (hipStream_t)stream)
-                  : launch<nt, vpt, FusedSrc<false>>(a, grid, lds, who, (hipStream_t)stream);
+        return pl ? launch<nt, vpt, PanelSrc<true>>(a, grid, lds, who, (hipStream_t)stream)
+                  : launch<nt, vpt, PanelSrc<false>>(a, grid, lds, who, (hipStream_t)stream);
     });
 }
 
@@ -872,8 +886,7 @@ extern "C" int fm_forecast_dist(const fm_fdist_args* args, void* stream) {
     const char* who = "fm_forecast_dist";
     FM_REQUIRE(args != nullptr, "%s: null args", who);
     const fm_fdist_args& a = *args;
-    FM_REQUIRE(a.nseg >= 0 && a.max_seg_len >= 0 && a.nrows >= 0, "%s: bad sizes", who);
-    FM_REQUIRE(a.nsel >= 0 && a.nsel <= FM_MAX_SORTS, "%s: nsel must be 0..%d", who, FM_MAX_SORTS);
+    FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
     FM_REQUIRE(a.nq >= 0 && a.nq <= FM_MAX_DIST_Q, "%s: nq must be 0..%d", who, FM_MAX_DIST_Q);
     for (int i = 0; i < a.nq; ++i) {
         const double lo = i == 0 ? 0.0 : a.q[i - 1];
@@ -884,33 +897,15 @@ extern "C" int fm_forecast_dist(const fm_fdist_args* args, void* stream) {
         set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
         return FM_ETOOBIG;
     }
-    if (a.nseg == 0 || a.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
-    const bool vec = a.forecast != nullptr, f64 = a.cols != nullptr, pl = a.hi_plane != nullptr || a.lo_plane != nullptr;
-    FM_REQUIRE((int)vec + (int)f64 + (int)pl == 1, "%s: exactly one of forecast, cols and the planes must be given", who);
-    FM_REQUIRE(!pl || (a.hi_plane != nullptr && a.lo_plane != nullptr), "%s: both planes are needed", who);
-    for (int j = 0; j < a.nsel; ++j)
-        FM_REQUIRE(a.sel_level[j] >= 0 && a.sel_level[j] <= 255, "%s: sel_level must be 0..255", who);
-    if (vec) {
-        FM_REQUIRE(a.forecast_out == nullptr, "%s: forecast_out goes with a panel source", who);
-    } else {
-        FM_REQUIRE((f64 ? a.col_stride : a.plane_stride) >= a.nrows, "%s: stride below the row count", who);
-        FM_REQUIRE(a.ncols >= 1, "%s: ncols must be >= 1", who);
-        FM_REQUIRE((a.lo == nullptr) == (a.hi == nullptr), "%s: lo and hi go together", who);
-        for (int j = 0; j < a.nsel; ++j) {
-            const int K = a.sel_k[j];
-            FM_REQUIRE(K >= 1 && K <= FM_MAX_SORT_K, "%s: sort %d has K = %d, not 1..%d", who, j, K, FM_MAX_SORT_K);
-            FM_REQUIRE(a.coef_stride >= K + 1, "%s: coef_stride %d below K + 1 = %d", who, a.coef_stride, K + 1);
-            for (int k = 0; k < K; ++k)
-                FM_REQUIRE(a.sel_cols[j][k] >= 0 && a.sel_cols[j][k] < a.ncols,
-                           "%s: sort %d column %d outside the panel's %d", who, j, a.sel_cols[j][k], a.ncols);
-        }
-        FM_REQUIRE(a.coef != nullptr, "%s: null pointer", who);
-    }
+    const bool vec = a.forecast != nullptr;
+    if (const int rc = check_forecast_src(a.src, a.nseg, who, vec)) return rc;
+    if (a.nseg == 0 || a.src.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
     FM_REQUIRE(a.seg_off && a.rec && a.cnt && a.status, "%s: null pointer", who);
+    const bool pl = a.src.hi_plane != nullptr;
     const size_t lds = port_lds_bytes(a.max_seg_len);
     const hipStream_t st = (hipStream_t)stream;
     return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
         if (vec) return launch_fdist<nt, vpt, VecSrc>(a, lds, st);
-        return pl ? launch_fdist<nt, vpt, DistSrc<true>>(a, lds, st) : launch_fdist<nt, vpt, DistSrc<false>>(a, lds, st);
+        return pl ? launch_fdist<nt, vpt, PanelSrc<true>>(a, lds, st) : launch_fdist<nt, vpt, PanelSrc<false>>(a, lds, st);
     });
 }

@@ -359,7 +359,7 @@ __global__ __launch_bounds__(VT) void solve_kernel(fm_solve_args a) {
 
 // ---------------------------------------------------------------------------------------
 // The statsmodels fix-ups of flagged (month, problem) pairs.  They run inside solve16_kernel
-// (zw == 16) or as the separate fm_solve_fixup / fm_const_check launches, and all read the
+// (zw == 16) or as the separate fm_solve_fixup launch, and all read the
 // same things, held in one context: the panel rows (CA: FP64 columns or the two planes), the
 // per-(column, month) transforms, the problem tables and the solve's outputs.
 template <class CA>
@@ -373,6 +373,21 @@ struct FixCtx {
     int pmax; double* rec; uint32_t* status;
     int check_const;
 };
+
+// The context of the fix-ups of solve `a`, its rows read through `cols` (both launches build it here)
+template <class CA>
+__host__ __device__ __forceinline__ FixCtx<CA> fix_ctx(const fm_solve_args& a, CA cols) {
+    FixCtx<CA> fx{};
+    fx.check_const = a.fix_check_const;
+    fx.cols = cols, fx.stride = a.fix_stride, fx.seg_off = a.fix_seg_off, fx.nseg = a.nseg;
+    fx.lo = a.fix_lo, fx.hi = a.fix_hi;
+    fx.shift = a.fix_shift, fx.inv_scale = a.fix_inv_scale, fx.add_back = a.add_back;
+    fx.level = a.fix_level;
+    fx.nprob = a.nprob, fx.prob_level = a.prob_level, fx.prob_z = a.prob_z, fx.prob_nz = a.prob_nz;
+    fx.moments = a.moments, fx.mom_stride = a.mom_stride;
+    fx.pmax = a.pmax, fx.rec = a.rec, fx.status = a.status;
+    return fx;
+}
 
 // Exact nonzero-constant test for problems flagged CONST_SUSPECT (statsmodels
 // add_constant(has_constant='skip'): np.ptp(x)==0 & all(x != 0), src/regressions.py:50).
@@ -1163,15 +1178,7 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
     // instantiation per layout (a per-access branch raised the kernel to 231 VGPRs)
     auto fix_all = [&](auto cols) {
         __syncthreads();
-        FixCtx<decltype(cols)> fx{};
-        fx.check_const = a.fix_check_const;
-        fx.cols = cols, fx.stride = a.fix_stride, fx.seg_off = a.fix_seg_off, fx.nseg = a.nseg;
-        fx.lo = a.fix_lo, fx.hi = a.fix_hi;
-        fx.shift = a.fix_shift, fx.inv_scale = a.fix_inv_scale, fx.add_back = a.add_back;
-        fx.level = a.fix_level;
-        fx.nprob = a.nprob, fx.prob_level = a.prob_level, fx.prob_z = a.prob_z, fx.prob_nz = a.prob_nz;
-        fx.moments = a.moments, fx.mom_stride = a.mom_stride;
-        fx.pmax = a.pmax, fx.rec = a.rec, fx.status = a.status;
+        const FixCtx<decltype(cols)> fx = fix_ctx(a, cols);
         for (int q = 0; q < a.nprob; ++q) {
             const uint32_t st = t_st[q];
             if (!fix_wanted(st, fx.check_const)) continue;   // block-uniform
@@ -1182,34 +1189,15 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
     else if (a.fix_hi_plane != nullptr) fix_all(PlaneCols{a.fix_hi_plane, (int64_t)(a.fix_lo_plane - a.fix_hi_plane)});
 }
 
-__global__ __launch_bounds__(VT) void const_kernel(FixCtx<F64Cols> fx, const int32_t* pairs, int npairs) {
-    __shared__ uint64_t red[VNW];
-    // npairs < 0: scan every (month, problem) and take those the solve flagged, so the
-    // check needs no host round trip; else the listed pairs.
-    const int total = npairs < 0 ? fx.nseg * fx.nprob : npairs;
-    for (int e = blockIdx.x; e < total; e += gridDim.x) {
-        int s, p;
-        if (npairs < 0) {
-            s = e / fx.nprob;
-            p = e - s * fx.nprob;
-            if (!(fx.status[e] & FM_ST_CONST_SUSPECT)) continue;
-        } else {
-            s = pairs[2 * e];
-            p = pairs[2 * e + 1];
-        }
-        const_pair(s, p, red, fx);
-    }
-}
-
 template <int NC>
-__global__ __launch_bounds__(VT) void fixup_kernel(FixCtx<F64Cols> fx, const int32_t* pairs, int npairs) {
+__global__ __launch_bounds__(VT) void fixup_kernel(FixCtx<F64Cols> fx) {
     __shared__ FixSmem<NC, VT> sm;
-    // npairs < 0: scan every (month, problem) for the flags (no host round trip).  Each
-    // workgroup reads VT status words at once and lists the flagged pairs in LDS (a
-    // pair-by-pair scan would wait out one memory round trip per pair), then fixes them.
+    // Every (month, problem) is scanned for the flags (no host round trip).  Each workgroup
+    // reads VT status words at once and lists the flagged pairs in LDS (a pair-by-pair scan
+    // would wait out one memory round trip per pair), then fixes them.
     __shared__ int flagged[VT];
     __shared__ int nflag;
-    const int total = npairs < 0 ? fx.nseg * fx.nprob : npairs;
+    const int total = fx.nseg * fx.nprob;
     const int tid = threadIdx.x;
     FM_PROBE_AT(solve, 4);
     for (int base = blockIdx.x * VT; base < total; base += gridDim.x * VT) {
@@ -1217,29 +1205,28 @@ __global__ __launch_bounds__(VT) void fixup_kernel(FixCtx<F64Cols> fx, const int
         __syncthreads();
         {
             const int e = base + tid;
-            if (e < total) {
-                int s, p;
-                if (npairs < 0) {
-                    s = e / fx.nprob;
-                    p = e - s * fx.nprob;
-                } else {
-                    s = pairs[2 * e];
-                    p = pairs[2 * e + 1];
-                }
-                if (fix_wanted(fx.status[(int64_t)s * fx.nprob + p], fx.check_const))
-                    flagged[atomicAdd(&nflag, 1)] = s * fx.nprob + p;
-            }
+            if (e < total && fix_wanted(fx.status[e], fx.check_const)) flagged[atomicAdd(&nflag, 1)] = e;
         }
         __syncthreads();
         const int nf = nflag;
         for (int f = 0; f < nf; ++f) {
             const int sp = flagged[f];
             const int s = sp / fx.nprob, p = sp - s * fx.nprob;
-            fix_one<NC, VT>(s, p, fx.status[(int64_t)s * fx.nprob + p], sm, fx);
+            fix_one<NC, VT>(s, p, fx.status[sp], sm, fx);
         }
         __syncthreads();   // the list is rebuilt for the next range
     }
     FM_PROBE_AT(solve, 5);
+}
+
+// What the inline fix-ups of fm_solve and fm_solve_fixup both ask of the fix_* arguments
+int check_fix_args(const fm_solve_args& a, const char* who) {
+    FM_REQUIRE(a.fix_seg_off != nullptr, "%s: fix_seg_off is NULL", who);
+    FM_REQUIRE(a.moments != nullptr, "%s: the fix-ups need moments", who);
+    FM_REQUIRE((a.fix_lo == nullptr) == (a.fix_hi == nullptr), "%s: fix_lo and fix_hi go together", who);
+    FM_REQUIRE(a.fix_inv_scale == nullptr || a.fix_shift != nullptr, "%s: fix_inv_scale needs fix_shift", who);
+    FM_REQUIRE(a.pmax >= 2 && a.pmax <= 32, "%s: pmax must be 2..32", who);
+    return FM_OK;
 }
 
 }  // namespace
@@ -1262,11 +1249,10 @@ extern "C" int fm_solve(const fm_solve_args* args, void* stream) {
     FM_REQUIRE(a.zw == 32 || a.nprob <= S16_MAXP, "fm_solve: at most %d problems per group", S16_MAXP);
     FM_REQUIRE((a.fix_hi_plane == nullptr) == (a.fix_lo_plane == nullptr),
                "fm_solve: fix_hi_plane and fix_lo_plane go together");
-    FM_REQUIRE((a.fix_cols == nullptr && a.fix_hi_plane == nullptr) || (a.zw == 16 && a.fix_seg_off && a.moments && a.pmax + 1 <= 16 &&
-                                         (a.fix_lo == nullptr) == (a.fix_hi == nullptr) &&
-                                         (a.fix_inv_scale == nullptr || a.fix_shift != nullptr)),
-               "fm_solve: inline fix-ups need zw 16, fix_seg_off, moments, pmax <= 15, lo with hi, "
-               "shift with inv_scale");
+    if (a.fix_cols != nullptr || a.fix_hi_plane != nullptr) {
+        FM_REQUIRE(a.zw == 16 && a.pmax + 1 <= 16, "fm_solve: inline fix-ups need zw 16 and pmax <= 15");
+        if (const int rc = check_fix_args(a, "fm_solve")) return rc;
+    }
     if (a.nseg == 0 || a.nprob == 0) return FM_OK;
     const size_t dyn = (size_t)a.npatterns * a.nlevels * (a.zw * (a.zw + 1) / 2) * sizeof(double);
     const int rc = a.zw == 16 ? raise_dynamic_lds<solve16_kernel>(MAXB_LDS * sizeof(double), "fm_solve")
@@ -1280,58 +1266,22 @@ extern "C" int fm_solve(const fm_solve_args* args, void* stream) {
     return FM_OK;
 }
 
-extern "C" int fm_const_check(const double* cols, int64_t col_stride, int32_t ncols,
-                              const int64_t* seg_off, int32_t nseg, const double* lo,
-                              const double* hi, const uint8_t* level, int32_t nprob,
-                              const int32_t* prob_level, const int32_t* prob_z,
-                              const int32_t* prob_nz, const int32_t* pairs, int32_t npairs,
-                              uint32_t* status, void* stream) {
+extern "C" int fm_solve_fixup(const fm_solve_args* args, void* stream) {
     using namespace fm;
-    FM_REQUIRE(cols && seg_off && prob_level && prob_z && prob_nz && status &&
-                   (pairs || npairs < 0), "fm_const_check: null pointer");
-    FM_REQUIRE((lo == nullptr) == (hi == nullptr), "fm_const_check: lo/hi must both be set or NULL");
-    const int64_t work = npairs < 0 ? (int64_t)nseg * nprob : npairs;
-    if (work == 0) return FM_OK;
-    const int grid = (int)(npairs < 0 ? (work < SCAN_GRID ? work : SCAN_GRID) : work);
-    (void)ncols;            // the problems' z indices name the columns
-    FixCtx<F64Cols> fx{};   // what const_pair does not read stays zero
-    fx.cols = F64Cols{cols}, fx.stride = col_stride, fx.seg_off = seg_off, fx.nseg = nseg;
-    fx.lo = lo, fx.hi = hi, fx.level = level;
-    fx.nprob = nprob, fx.prob_level = prob_level, fx.prob_z = prob_z, fx.prob_nz = prob_nz;
-    fx.status = status;
-    hipLaunchKernelGGL(const_kernel, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx, pairs, npairs);
-    FM_CHECK_LAUNCH("fm_const_check");
-    return FM_OK;
-}
-
-extern "C" int fm_solve_fixup(const double* cols, int64_t col_stride, const int64_t* seg_off,
-                              int32_t nseg, const double* lo, const double* hi, const double* shift,
-                              const double* inv_scale, const double* add_back, const uint8_t* level,
-                              int32_t nprob, const int32_t* prob_level, const int32_t* prob_z,
-                              const int32_t* prob_nz, const int32_t* pairs, int32_t npairs,
-                              const double* moments, int32_t mom_stride, int32_t pmax, double* rec,
-                              uint32_t* status, int32_t check_const, void* stream) {
-    using namespace fm;
-    FM_REQUIRE(cols && seg_off && prob_level && prob_z && prob_nz && moments && rec && status &&
-                   (pairs || npairs < 0), "fm_solve_fixup: null pointer");
-    FM_REQUIRE((lo == nullptr) == (hi == nullptr), "fm_solve_fixup: lo/hi must both be set or NULL");
-    FM_REQUIRE(inv_scale == nullptr || shift != nullptr, "fm_solve_fixup: inv_scale needs shift");
-    FM_REQUIRE(pmax >= 2 && pmax <= 32, "fm_solve_fixup: pmax must be 2..32");
-    const int64_t work = npairs < 0 ? (int64_t)nseg * nprob : npairs;
+    FM_REQUIRE(args != nullptr, "fm_solve_fixup: null args");
+    const fm_solve_args& a = *args;
+    FM_REQUIRE(a.fix_hi_plane == nullptr && a.fix_lo_plane == nullptr, "fm_solve_fixup: FP64 columns only (a plane is set)");
+    FM_REQUIRE(a.fix_cols && a.prob_level && a.prob_z && a.prob_nz && a.rec && a.status, "fm_solve_fixup: null pointer");
+    if (const int rc = check_fix_args(a, "fm_solve_fixup")) return rc;
+    const int64_t work = (int64_t)a.nseg * a.nprob;
     if (work == 0) return FM_OK;
     const int64_t ranges = (work + VT - 1) / VT;   // VT pairs per workgroup pass
     const int grid = (int)(ranges < SCAN_GRID ? ranges : SCAN_GRID);
-    FixCtx<F64Cols> fx{};
-    fx.cols = F64Cols{cols}, fx.stride = col_stride, fx.seg_off = seg_off, fx.nseg = nseg;
-    fx.lo = lo, fx.hi = hi, fx.level = level;
-    fx.shift = shift, fx.inv_scale = inv_scale, fx.add_back = add_back;
-    fx.nprob = nprob, fx.prob_level = prob_level, fx.prob_z = prob_z, fx.prob_nz = prob_nz;
-    fx.moments = moments, fx.mom_stride = mom_stride;
-    fx.pmax = pmax, fx.rec = rec, fx.status = status, fx.check_const = check_const;
-    if (pmax + 1 <= 16)
-        hipLaunchKernelGGL(fixup_kernel<16>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx, pairs, npairs);
+    const FixCtx<F64Cols> fx = fix_ctx(a, F64Cols{a.fix_cols});
+    if (a.pmax + 1 <= 16)
+        hipLaunchKernelGGL(fixup_kernel<16>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx);
     else
-        hipLaunchKernelGGL(fixup_kernel<32>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx, pairs, npairs);
+        hipLaunchKernelGGL(fixup_kernel<32>, dim3(grid), dim3(VT), 0, (hipStream_t)stream, fx);
     FM_CHECK_LAUNCH("fm_solve_fixup");
     return FM_OK;
 }

@@ -91,7 +91,7 @@ class SolveArgs(C.Structure):
         ("prob_nz", _p), ("prob_flags", _p), ("add_back", _p), ("gram_flags", _p),
         ("nmodels", _i32), ("pmax", _i32), ("rec", _p), ("status", _p),
         ("moments", _p), ("mom_stride", _i32), ("ab_ncols", _i32),
-        # inline statsmodels fix-ups (fix_cols None: a separate fm_solve_fixup call)
+        # what the statsmodels fix-ups read: set for fm_solve (inline) or, after it, for fm_solve_fixup
         ("fix_cols", _p), ("fix_stride", _i64), ("fix_seg_off", _p), ("fix_lo", _p), ("fix_hi", _p),
         ("fix_shift", _p), ("fix_inv_scale", _p), ("fix_level", _p), ("fix_check_const", _i32),
         ("fix_pad", _i32),
@@ -117,28 +117,31 @@ class PortArgs(C.Structure):
     ]
 
 
-class FPortArgs(C.Structure):
+class ForecastSrc(C.Structure):
+    """fm_forecast_src: the fused forecast both FPortArgs and FDistArgs embed as ``src``."""
     _fields_ = [
         ("cols", _p), ("col_stride", _i64), ("hi_plane", _p), ("lo_plane", _p), ("plane_stride", _i64),
-        ("ncols", _i32), ("ret_col", _i32), ("lo", _p), ("hi", _p), ("weight", _p), ("level", _p),
-        ("nyse", _p), ("seg_off", _p), ("nrows", _i64), ("nseg", _i32), ("max_seg_len", _i32),
-        ("nport", _i32), ("nyse_breakpoints", _i32), ("min_count", _i32), ("nsel", _i32),
-        ("q", _f64 * (FM_MAX_PORTS - 1)), ("sel_k", _i32 * FM_MAX_SORTS), ("sel_level", _i32 * FM_MAX_SORTS),
-        ("sel_cols", (_i32 * FM_MAX_SORT_K) * FM_MAX_SORTS), ("coef", _p), ("coef_stride", _i32),
-        ("pad_fport", _i32), ("bp", _p), ("port", _p), ("rec", _p), ("cnt", _p), ("status", _p),
-        ("forecast_out", _p),
+        ("lo", _p), ("hi", _p), ("coef", _p), ("forecast_out", _p), ("nrows", _i64),
+        ("ncols", _i32), ("coef_stride", _i32), ("nsel", _i32), ("pad_src", _i32),
+        ("sel_k", _i32 * FM_MAX_SORTS), ("sel_level", _i32 * FM_MAX_SORTS),
+        ("sel_cols", (_i32 * FM_MAX_SORT_K) * FM_MAX_SORTS),
+    ]
+
+
+class FPortArgs(C.Structure):
+    _fields_ = [
+        ("src", ForecastSrc), ("ret_col", _i32), ("nseg", _i32), ("max_seg_len", _i32), ("nport", _i32),
+        ("nyse_breakpoints", _i32), ("min_count", _i32), ("weight", _p), ("level", _p), ("nyse", _p),
+        ("seg_off", _p), ("q", _f64 * (FM_MAX_PORTS - 1)), ("bp", _p), ("port", _p), ("rec", _p),
+        ("cnt", _p), ("status", _p),
     ]
 
 
 class FDistArgs(C.Structure):
     _fields_ = [
-        ("forecast", _p), ("cols", _p), ("col_stride", _i64), ("hi_plane", _p), ("lo_plane", _p),
-        ("plane_stride", _i64), ("lo", _p), ("hi", _p), ("coef", _p), ("level", _p), ("seg_off", _p),
-        ("nrows", _i64), ("ncols", _i32), ("coef_stride", _i32), ("nseg", _i32), ("max_seg_len", _i32),
-        ("min_count", _i32), ("nsel", _i32), ("nq", _i32), ("pad_fdist", _i32), ("q", _f64 * FM_MAX_DIST_Q),
-        ("sel_k", _i32 * FM_MAX_SORTS), ("sel_level", _i32 * FM_MAX_SORTS),
-        ("sel_cols", (_i32 * FM_MAX_SORT_K) * FM_MAX_SORTS), ("rec", _p), ("cnt", _p), ("status", _p),
-        ("forecast_out", _p),
+        ("src", ForecastSrc), ("forecast", _p), ("level", _p), ("seg_off", _p), ("nseg", _i32),
+        ("max_seg_len", _i32), ("min_count", _i32), ("nq", _i32), ("q", _f64 * FM_MAX_DIST_Q),
+        ("rec", _p), ("cnt", _p), ("status", _p),
     ]
 
 
@@ -155,7 +158,6 @@ _SIGS = {
     "fm_version": (C.c_char_p, []),
     "fm_last_error": (C.c_char_p, []),
     "fm_device_arch": (_i32, [C.c_char_p, _i32]),
-    "fm_abi_sizes": (_i32, [C.POINTER(_i32), C.POINTER(_i32)]),
     "fm_struct_size": (_i64, [C.c_char_p]),
     "fm_select_cuts": (_i32, [_p, _i64, _i32, _p, _i32, _i32, _p, _f64, _f64, _i32, _i32,
                               _p, _p, _p, _p, _p, _p, _p]),
@@ -172,10 +174,7 @@ _SIGS = {
     "fm_pilot_shift": (_i32, [_p, _i64, _i32, _p, _i32, _p, _p]),
     "fm_gram": (_i32, [C.POINTER(GramArgs), _p]),
     "fm_solve": (_i32, [C.POINTER(SolveArgs), _p]),
-    "fm_const_check": (_i32, [_p, _i64, _i32, _p, _i32, _p, _p, _p, _i32, _p, _p, _p, _p,
-                              _i32, _p, _p]),
-    "fm_solve_fixup": (_i32, [_p, _i64, _p, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _i32,
-                            _p, _i32, _i32, _p, _p, _i32, _p]),
+    "fm_solve_fixup": (_i32, [C.POINTER(SolveArgs), _p]),
     "fm_ts_compact": (_i32, [_p, _i64, _i64, _i32, _i32, _p, _p, _p]),
     "fm_ts_summary": (_i32, [_p, _i64, _i64, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p,
                              _p, _p]),
@@ -207,7 +206,7 @@ _SIGS = {
 EXPORTED = tuple(_SIGS)
 _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_args": SelectArgs,
             "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs,
-            "fm_port_args": PortArgs, "fm_rank_args": RankArgs,
+            "fm_port_args": PortArgs, "fm_rank_args": RankArgs, "fm_forecast_src": ForecastSrc,
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs}
 
 _lib = None

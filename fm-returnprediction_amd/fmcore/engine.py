@@ -793,6 +793,12 @@ def _group_plans(panel, models, problems, nlevels, cap, const_check, dev):
     return plans
 
 
+def solve_fix_inline(zw, pmax):
+    """True where fm_solve does the statsmodels fix-ups inside its own launch (the 16-wide solve of
+    at most 15 columns); elsewhere fm_solve_fixup follows it."""
+    return zw == 16 and pmax + 1 <= 16
+
+
 def _solve_group(panel, src, gpl, partial, seg_chunk_off, zw, nlevels, T, pmax, mom_stride, lo, hi,
                  shift, inv_scale, add_back, level, const_check, keep):
     """fm_solve + the statsmodels fix-ups (inf in y, nonzero constant columns) for one
@@ -815,28 +821,29 @@ def _solve_group(panel, src, gpl, partial, seg_chunk_off, zw, nlevels, T, pmax, 
     # variance (CONST_SUSPECT), inf in y (pinv(X) @ y gives +-inf / NaN coefficients) and the
     # QR + SVD refit of ill-conditioned / rank-deficient problems (FM_ST_REFIT).  The 16-wide
     # solve does them inside its own launch (each month's workgroup, right after its solve);
-    # the 32-wide one is followed by fm_solve_fixup, which scans the status on the device
-    # (npairs = -1): no host round trip either way.
-    inline_fix = zw == 16 and pmax + 1 <= 16
+    # the 32-wide one is followed by fm_solve_fixup, which scans the status on the device: no
+    # host round trip either way.  Both read the fix_* fields of the one struct.
+    inline_fix = solve_fix_inline(zw, pmax)
     if not inline_fix and src.f64 is None:   # fm_solve_fixup reads FP64 columns
         src = _source(panel, panel.values())
-    if inline_fix:
+
+    def set_fix():
         # the fix-ups' rows: the FP64 columns, else the planes of a planes-only panel
         sa.fix_cols, sa.fix_stride, sa.fix_seg_off = src.ptr, src.stride, panel.seg_off.data_ptr()
         if src.f64 is None:
             sa.fix_hi_plane, sa.fix_lo_plane = src.hp, src.lp
         sa.fix_lo, sa.fix_hi, sa.fix_shift, sa.fix_inv_scale = _ptr(lo), _ptr(hi), _ptr(shift), _ptr(inv_scale)
         sa.fix_level, sa.fix_check_const = _ptr(level), int(bool(const_check))
-    _kcall("fm_solve", "fm_solve", L.C.byref(sa), _stream())
-    _remember("fm_solve", "fm_solve", sa, partial, seg_chunk_off, gpl, add_back, grec, gst, gmom, src.f64,
-              panel.planes, lo, hi, shift, inv_scale, level, *keep)
+
     if inline_fix:
-        return grec, gst, gmom
-    _kcall("fm_solve_fixup", "fm_solve_fixup", src.ptr, src.stride, panel.seg_off.data_ptr(), T,
-           _ptr(lo), _ptr(hi), _ptr(shift), _ptr(inv_scale), _ptr(add_back), _ptr(level), ng,
-           gpl.pl.data_ptr(), gpl.pz.data_ptr(), gpl.pnz.data_ptr(), None, -1,
-           gmom.data_ptr(), mom_stride, pmax, grec.data_ptr(), gst.data_ptr(), int(bool(const_check)),
-           _stream())
+        set_fix()
+    _kcall("fm_solve", "fm_solve", L.C.byref(sa), _stream())
+    # (a copy: the struct as this launch saw it, whatever fm_solve_fixup gets set below)
+    _remember("fm_solve", "fm_solve", L.SolveArgs.from_buffer_copy(sa), partial, seg_chunk_off, gpl, add_back,
+              grec, gst, gmom, src.f64, panel.planes, lo, hi, shift, inv_scale, level, *keep)
+    if not inline_fix:
+        set_fix()
+        _kcall("fm_solve_fixup", "fm_solve_fixup", L.C.byref(sa), _stream())
     return grec, gst, gmom
 
 
@@ -1245,6 +1252,46 @@ def lagged_coefficients(roll, ix: TSIndex, problems, lag=1):
     return out
 
 
+def _forecast_plan(who, panel, coef, sel, cuts):
+    """What the fused-forecast functions do before their loop: the panel's source, ``sel`` with its
+    columns resolved to indices, ``coef`` and the cuts' tables checked -> (src, sel, coef, lo, hi)."""
+    src = _source(panel)
+    T, C, nsel = panel.nseg, src.ncols, len(sel)
+    sel = [([panel.col(c) if isinstance(c, str) else int(c) for c in xs], int(lv)) for xs, lv in sel]
+    coef = coef.contiguous()
+    if coef.dtype != torch.float64 or coef.dim() != 3 or coef.shape[0] != nsel or coef.shape[1] != T or \
+            coef.device != src.device:
+        raise ValueError(f"{who}: coef must be a float64 [{nsel}, {T}, >= K+1] tensor on {src.device}")
+    lo = hi = None
+    if cuts is not None:
+        lo, hi = cuts.lo.contiguous(), cuts.hi.contiguous()
+        if tuple(lo.shape) != (C, T) or tuple(hi.shape) != (C, T):
+            raise ValueError(f"{who}: the cuts must be [{C}, {T}] tables")
+    return src, sel, coef, lo, hi
+
+
+def _fill_forecast_src(f, n, part, j0=0, src=None, coef=None, lo=None, hi=None, forecast_out=None):
+    """Fill the fm_forecast_src ``f`` for the sorts ``part`` = sel[j0:j0 + m] of an ``n``-row panel:
+    the sorts' columns and levels, then from ``src`` the one layout the kernel reads (FP64 columns if
+    the panel has them, else its planes), the cuts, ``coef[j0:]`` and ``forecast_out[j0:]``.
+    ``src`` None (the caller's own forecast vectors): the sorts' count and levels only."""
+    f.nrows, f.nsel = n, len(part)
+    for j, (xs, lv) in enumerate(part):
+        f.sel_k[j], f.sel_level[j] = len(xs), lv
+        for k, c in enumerate(xs[:L.FM_MAX_SORT_K]):
+            f.sel_cols[j][k] = c
+    if src is None:
+        return
+    if src.f64 is not None:
+        f.cols, f.col_stride = src.ptr, src.stride
+    else:
+        f.hi_plane, f.lo_plane, f.plane_stride = src.hp, src.lp, src.pstride
+    f.ncols, f.lo, f.hi = src.ncols, _ptr(lo), _ptr(hi)
+    nsel = coef.shape[0]
+    f.coef, f.coef_stride = coef[j0:].data_ptr() if nsel else None, coef.stride(1)
+    f.forecast_out = forecast_out[j0:].data_ptr() if forecast_out is not None and nsel else None
+
+
 def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, ret="retx", weight=None, level=None,
                             nyse=None, nport=10, q=None, nyse_breakpoints=False, min_count=None,
                             forecast_out=False, out: "Portfolios" = None):
@@ -1258,27 +1305,12 @@ def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, re
     definition is in fm_hip.h).  One launch per FM_MAX_SORTS sorts.  Returns ``Portfolios`` whose
     tensors carry a leading [nsel] dimension; ``forecast_out``: also the forecasts [nsel, rows];
     ``out``: a ``Portfolios`` of that shape to write into (else allocated)."""
-    src = _source(panel)
+    src, sel, coef, lo, hi = _forecast_plan("forecast_portfolio_sort", panel, coef, sel, cuts)
     dev = src.device
-    n, T, C = panel.nrows, panel.nseg, src.ncols
-    nsel = len(sel)
-
-    def col(c):
-        return panel.col(c) if isinstance(c, str) else int(c)
-
-    sel = [([col(c) for c in xs], int(lv)) for xs, lv in sel]
-    coef = coef.contiguous()
-    if coef.dtype != torch.float64 or coef.dim() != 3 or coef.shape[0] != nsel or coef.shape[1] != T or \
-            coef.device != dev:
-        raise ValueError(f"forecast_portfolio_sort: coef must be a float64 [{nsel}, {T}, >= K+1] tensor on {dev}")
+    n, T, nsel = panel.nrows, panel.nseg, len(sel)
     weight = _row_vector(weight, torch.float64, n, dev, "weight")
     level = _row_vector(level, torch.uint8, n, dev, "level")
     nyse = _row_vector(nyse, torch.uint8, n, dev, "nyse")
-    lo = hi = None
-    if cuts is not None:
-        lo, hi = cuts.lo.contiguous(), cuts.hi.contiguous()
-        if tuple(lo.shape) != (C, T) or tuple(hi.shape) != (C, T):
-            raise ValueError(f"forecast_portfolio_sort: the cuts must be [{C}, {T}] tables")
     fill, shapes = _sort_plan("forecast_portfolio_sort", (nsel,), T, n, int(nport), q, nyse_breakpoints, min_count)
     if forecast_out:
         shapes["forecast"] = ((nsel, n), torch.float64)
@@ -1288,29 +1320,16 @@ def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, re
         t = getattr(out, k)
         if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
             raise ValueError(f"forecast_portfolio_sort: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
-    # FP64 columns if the panel has them, else its planes: exactly one layout goes to the kernel
-    f64 = src.f64 is not None
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
-        part = sel[j0:j0 + L.FM_MAX_SORTS]
         a = fill(L.FPortArgs())
-        if f64:
-            a.cols, a.col_stride = src.ptr, src.stride
-        else:
-            a.hi_plane, a.lo_plane, a.plane_stride = src.hp, src.lp, src.pstride
-        a.ncols, a.ret_col = C, col(ret)
-        a.lo, a.hi = _ptr(lo), _ptr(hi)
+        _fill_forecast_src(a.src, n, sel[j0:j0 + L.FM_MAX_SORTS], j0, src, coef, lo, hi,
+                           out.forecast if forecast_out else None)
+        a.ret_col = panel.col(ret) if isinstance(ret, str) else int(ret)
         a.weight, a.level, a.nyse = _ptr(weight), _ptr(level), _ptr(nyse)
-        a.seg_off, a.nrows, a.nseg, a.max_seg_len = panel.seg_off.data_ptr(), n, T, panel.max_seg_len
-        a.nsel = len(part)
-        for j, (xs, lv) in enumerate(part):
-            a.sel_k[j], a.sel_level[j] = len(xs), lv
-            for k, c in enumerate(xs[:L.FM_MAX_SORT_K]):
-                a.sel_cols[j][k] = c
-        a.coef, a.coef_stride = coef[j0:].data_ptr() if nsel else None, coef.stride(1)
+        a.seg_off, a.nseg, a.max_seg_len = panel.seg_off.data_ptr(), T, panel.max_seg_len
         if nsel:
             a.bp, a.port, a.rec = out.bp[j0:].data_ptr(), out.port[j0:].data_ptr(), out.rec[j0:].data_ptr()
             a.cnt, a.status = out.cnt[j0:].data_ptr(), out.status[j0:].data_ptr()
-            a.forecast_out = out.forecast[j0:].data_ptr() if forecast_out else None
         _kcall("fm_forecast_portfolio_sort", "fm_forecast_portfolio_sort", L.C.byref(a), _stream())
         _remember("fm_forecast_portfolio_sort", "fm_forecast_portfolio_sort", a, src, panel.planes, panel.seg_off,
                   coef, lo, hi, weight, level, nyse, out)
@@ -1343,8 +1362,8 @@ class ForecastDist:
 
 def _dist_plan(who, nsel, T, n, q, min_count, forecast_out, out, dev):
     """What the two forecast-distribution entry points share: the levels, the ``ForecastDist`` to fill
-    (``out`` checked, else allocated) and ``fill(a, j0, m)``, which sets the shared fields of an
-    argument struct for the sorts j0 .. j0 + m."""
+    (``out`` checked, else allocated) and ``fill(a, j0)``, which sets the fields of an argument
+    struct outside its ``src`` for the sorts from j0."""
     qs = [float(v) for v in q]
     nq = min(len(qs), L.FM_MAX_DIST_Q)   # output shapes of a call the library will refuse
     shapes = dict(rec=((nsel, T, 2 + nq), torch.float64), cnt=((nsel, T), torch.int32),
@@ -1358,13 +1377,12 @@ def _dist_plan(who, nsel, T, n, q, min_count, forecast_out, out, dev):
         if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
             raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
 
-    def fill(a, j0, m):
-        a.nq, a.min_count, a.nsel, a.nseg, a.nrows = len(qs), int(min_count), m, T, n
+    def fill(a, j0):
+        a.nq, a.min_count, a.nseg = len(qs), int(min_count), T
         for i, v in enumerate(qs[:L.FM_MAX_DIST_Q]):
             a.q[i] = v
         if nsel:
             a.rec, a.cnt, a.status = out.rec[j0:].data_ptr(), out.cnt[j0:].data_ptr(), out.status[j0:].data_ptr()
-            a.forecast_out = out.forecast[j0:].data_ptr() if forecast_out else None
         return a
 
     return out, fill
@@ -1379,36 +1397,16 @@ def forecast_dist(panel: DevicePanel, coef, sel, cuts: Cuts = None, level=None, 
     (fm_forecast_dist; the definition is in fm_hip.h).  One launch per FM_MAX_SORTS sorts.  Returns
     ``ForecastDist``; ``forecast_out``: also the forecasts [nsel, rows]; ``out``: a
     ``ForecastDist`` of that shape to write into (else allocated)."""
-    src = _source(panel)
+    src, sel, coef, lo, hi = _forecast_plan("forecast_dist", panel, coef, sel, cuts)
     dev = src.device
-    n, T, C = panel.nrows, panel.nseg, src.ncols
-    nsel = len(sel)
-    sel = [([panel.col(c) if isinstance(c, str) else int(c) for c in xs], int(lv)) for xs, lv in sel]
-    coef = coef.contiguous()
-    if coef.dtype != torch.float64 or coef.dim() != 3 or coef.shape[0] != nsel or coef.shape[1] != T or \
-            coef.device != dev:
-        raise ValueError(f"forecast_dist: coef must be a float64 [{nsel}, {T}, >= K+1] tensor on {dev}")
+    n, T, nsel = panel.nrows, panel.nseg, len(sel)
     level = _row_vector(level, torch.uint8, n, dev, "level")
-    lo = hi = None
-    if cuts is not None:
-        lo, hi = cuts.lo.contiguous(), cuts.hi.contiguous()
-        if tuple(lo.shape) != (C, T) or tuple(hi.shape) != (C, T):
-            raise ValueError(f"forecast_dist: the cuts must be [{C}, {T}] tables")
     out, fill = _dist_plan("forecast_dist", nsel, T, n, q, min_count, forecast_out, out, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
-        part = sel[j0:j0 + L.FM_MAX_SORTS]
-        a = fill(L.FDistArgs(), j0, len(part))
-        if src.f64 is not None:
-            a.cols, a.col_stride = src.ptr, src.stride
-        else:
-            a.hi_plane, a.lo_plane, a.plane_stride = src.hp, src.lp, src.pstride
-        a.ncols, a.lo, a.hi, a.level = C, _ptr(lo), _ptr(hi), _ptr(level)
-        a.seg_off, a.max_seg_len = panel.seg_off.data_ptr(), panel.max_seg_len
-        for j, (xs, lv) in enumerate(part):
-            a.sel_k[j], a.sel_level[j] = len(xs), lv
-            for k, c in enumerate(xs[:L.FM_MAX_SORT_K]):
-                a.sel_cols[j][k] = c
-        a.coef, a.coef_stride = coef[j0:].data_ptr() if nsel else None, coef.stride(1)
+        a = fill(L.FDistArgs(), j0)
+        _fill_forecast_src(a.src, n, sel[j0:j0 + L.FM_MAX_SORTS], j0, src, coef, lo, hi,
+                           out.forecast if forecast_out else None)
+        a.level, a.seg_off, a.max_seg_len = _ptr(level), panel.seg_off.data_ptr(), panel.max_seg_len
         _kcall("fm_forecast_dist", "fm_forecast_dist", L.C.byref(a), _stream())
         _remember("fm_forecast_dist", "fm_forecast_dist", a, src, panel.planes, panel.seg_off, coef, lo, hi, level, out)
     return out
@@ -1438,12 +1436,10 @@ def forecast_dist_vector(seg_off, forecast, level=None, min_level=0, q=(0.1, 0.9
         max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
     out, fill = _dist_plan("forecast_dist_vector", nsel, T, n, q, min_count, False, None, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
-        m = min(nsel - j0, L.FM_MAX_SORTS)
-        a = fill(L.FDistArgs(), j0, m)
+        a = fill(L.FDistArgs(), j0)
+        _fill_forecast_src(a.src, n, [((), lv) for lv in levels[j0:j0 + L.FM_MAX_SORTS]])
         a.forecast = forecast[j0:].data_ptr() if nsel else None
         a.level, a.seg_off, a.max_seg_len = _ptr(level), seg_off.data_ptr(), int(max_seg_len)
-        for j in range(m):
-            a.sel_level[j] = levels[j0 + j]
         _kcall("fm_forecast_dist", "fm_forecast_dist", L.C.byref(a), _stream())
         _remember("fm_forecast_dist", "fm_forecast_dist", a, seg_off, forecast, level, out)
     return out

@@ -30,8 +30,8 @@
  *   fm_solve_fixup  <- statsmodels' pinv semantics where fm_solve's normal equations do not
  *                      reach them (src/regressions.py:57-64): pinv(X) @ y with an infinite
  *                      return (+-inf/NaN params, NaN R2), and ill-conditioned / rank-
- *                      deficient months re-solved from their rows (Householder QR + SVD)
- *   fm_const_check  <- add_constant(has_constant='skip') nonzero-constant detection
+ *                      deficient months re-solved from their rows (Householder QR + SVD),
+ *                      and add_constant(has_constant='skip') nonzero-constant detection
  *                      (src/regressions.py:50, which leads to IndexError at :71)
  *   fm_ts_compact, fm_ts_summary <- fama_macbeth_summary + newey_west_mean_se
  *                      (src/regressions.py:78-131)
@@ -172,11 +172,18 @@ typedef struct fm_solve_args {
     double* moments;              /* [nseg][nprob][mom_stride] or NULL: n, means(K+1), centered (K+1)^2 */
     int32_t mom_stride;
     int32_t ab_ncols;             /* rows of add_back ([ab_ncols][nseg]; the panel's ncols) */
-    /* The statsmodels fix-ups of fm_solve_fixup (npairs = -1) inside this launch, by each
-     * month's own workgroup right after its solve (zw 16 only; fix_cols NULL -- the
-     * zero-initialised default -- leaves them to a separate fm_solve_fixup call).  The
-     * arguments are fm_solve_fixup's: the panel columns the Gram read, its cuts, standardizing
-     * shift / scale, universe levels; moments must be set. */
+    /* What the statsmodels fix-ups read besides the problem tables, add_back, moments, pmax, rec
+     * and status above: the panel columns the Gram read ([ncols][fix_stride], months
+     * fix_seg_off[nseg+1]), its cuts, the standardizing shift / scale and the universe levels;
+     * moments must be set.  The fix-ups take the same row set as fm_gram (clip to fix_lo /
+     * fix_hi, NaN drop, level >= the problem's); with fix_inv_scale the design value is
+     * (x - fix_shift) * fix_inv_scale (+ add_back), without it the raw clipped x (add_back
+     * must then restore the shift, as fm_solve assumes); fix_check_const != 0 adds the exact
+     * nonzero-constant test of the CONST_SUSPECT pairs.
+     *   fm_solve with these set (zw 16 and pmax <= 15 only): each month's own workgroup does the
+     *     fix-ups right after its solve, inside that launch;
+     *   fm_solve with all of them NULL / 0 (the zero-initialised default): none; set them on the
+     *     same struct afterwards and call fm_solve_fixup. */
     const double* fix_cols;
     int64_t fix_stride;
     const int64_t* fix_seg_off;
@@ -195,11 +202,14 @@ typedef struct fm_solve_args {
 
 const char* fm_version(void);
 const char* fm_last_error(void);
-int fm_abi_sizes(int32_t* gram_args, int32_t* solve_args);
-/* sizeof the named argument struct ("fm_gram_args", "fm_solve_args", "fm_select_args",
- * "fm_universe_args", "fm_ts_args", "fm_chars_args", "fm_port_args", "fm_rank_args",
- * "fm_fport_args", "fm_fdist_args"); -1 for an unknown name.  Bindings
- * check their struct layouts against it before the first call. */
+/* Every argument struct of this header, once: X(name) per struct.  A new struct is one more
+ * entry here (and its class in the bindings). */
+#define FM_ARG_STRUCTS(X)                                                                     \
+    X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
+    X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
+    X(fm_fdist_args)
+/* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
+ * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
 int fm_device_arch(char* buf, int32_t len);
 
@@ -312,27 +322,15 @@ int fm_gram(const fm_gram_args* args, void* stream);
 
 int fm_solve(const fm_solve_args* args, void* stream);
 
-/* fm_const_check / fm_solve_fixup: `pairs` lists (month, problem) int32 pairs; npairs < 0
- * (pairs may be NULL) scans every pair on the device and takes those whose status bits ask
- * for the fix-up (CONST_SUSPECT; FITTED|INF_IN_Y or FITTED|REFIT), so callers need no host
- * round trip.  With check_const != 0, fm_solve_fixup also runs fm_const_check's test on
- * the CONST_SUSPECT pairs (one launch for every fix-up).  It reads the same row set as fm_gram (clip to lo/hi, NaN drop,
- * level >= the problem's); with inv_scale the design value is (x - shift) * inv_scale
- * (+ add_back), without it the raw clipped x (add_back must then restore the shift, as
- * fm_solve assumes). */
-int fm_const_check(const double* cols, int64_t col_stride, int32_t ncols,
-                   const int64_t* seg_off, int32_t nseg,
-                   const double* lo, const double* hi, const uint8_t* level,
-                   int32_t nprob, const int32_t* prob_level, const int32_t* prob_z,
-                   const int32_t* prob_nz, const int32_t* pairs, int32_t npairs,
-                   uint32_t* status, void* stream);
-
-int fm_solve_fixup(const double* cols, int64_t col_stride, const int64_t* seg_off, int32_t nseg,
-                   const double* lo, const double* hi, const double* shift, const double* inv_scale,
-                   const double* add_back, const uint8_t* level, int32_t nprob,
-                   const int32_t* prob_level, const int32_t* prob_z, const int32_t* prob_nz,
-                   const int32_t* pairs, int32_t npairs, const double* moments, int32_t mom_stride,
-                   int32_t pmax, double* rec, uint32_t* status, int32_t check_const, void* stream);
+/* fm_solve_fixup: the statsmodels fix-ups as a launch of their own, for solves that did not
+ * run them inline (zw 32, or pmax > 15).  `args` is the struct of the preceding fm_solve call
+ * with its fix_* fields now set (see fm_solve_args): the launch reads those, the problem
+ * tables (prob_level, prob_z, prob_nz), add_back, moments, mom_stride, pmax, nseg and nprob,
+ * scans every (month, problem) status word on the device and fixes the pairs whose bits ask
+ * for it (CONST_SUSPECT with fix_check_const; FITTED|INF_IN_Y or FITTED|REFIT) in rec /
+ * status, so callers need no host round trip.  FP64 columns only: fix_cols is required and a
+ * plane set is FM_EINVAL. */
+int fm_solve_fixup(const fm_solve_args* args, void* stream);
 
 int fm_ts_compact(const uint32_t* status, int64_t s_seg, int64_t s_prob, int32_t nseg,
                   int32_t nprob, int32_t* idx, int32_t* count, void* stream);
@@ -459,61 +457,69 @@ typedef struct fm_port_args {
 
 int fm_portfolio_sort(const fm_port_args* args, void* stream);
 
-/* fm_forecast_portfolio_sort: nsel forecast sorts of one panel in one launch (grid (month,
- * sort)), each row's forecast computed in the sort kernel's load phase from the panel's own
- * layout instead of read from a vector (paper Table 5 inside the device pipeline; no reference
- * line).  Exactly one predictor source: FP64 columns (cols, col_stride) or the split planes
- * (hi_plane, lo_plane, plane_stride); both or neither: FM_EINVAL.  For sort j (K = sel_k[j] in
- * 1..FM_MAX_SORT_K predictors, panel columns sel_cols[j][0..K) in coefficient order), month t
- * with the coefficient row c = coef[(j * nseg + t) * coef_stride + 0..K] (coef_stride >= K + 1)
- * and row i:
+/* fm_forecast_src: the fused forecast -- nsel forecasts of one panel, each row's value computed
+ * in the consuming kernel's load phase from the panel's own layout instead of read from a vector.
+ * It is embedded as the field `src` of fm_fport_args and fm_fdist_args; nseg, seg_off and
+ * max_seg_len are the embedding struct's.  Exactly one predictor source: FP64 columns (cols,
+ * col_stride) or the split planes (hi_plane, lo_plane, plane_stride); both or neither: FM_EINVAL.
+ * For sort j (K = sel_k[j] in 1..FM_MAX_SORT_K predictors, panel columns sel_cols[j][0..K) in
+ * coefficient order), month t with the coefficient row c = coef[(j * nseg + t) * coef_stride +
+ * 0..K] (coef_stride >= K + 1) and row i:
  *   x'_k = clip(x_k) exactly as fm_clip clips with lo / hi [ncols][nseg] (x < lo -> lo, x > hi
  *          -> hi; a NaN bound is ignored, a NaN x stays NaN; lo == hi == NULL: no clipping);
  *   F    = c[0], then for k = 1..K in order F = F + c[k] * x'_k, every product and every sum
- *          rounded on its own (fm_forecast's bits on the fm_clip-ped columns);
- *   then fm_portfolio_sort's definition with forecast = F, ret = panel column ret_col (read
- *   raw, never clipped, from the same layout) and min_level = sel_level[j].
- * So a NaN in the coefficient row makes every F NaN and the month unsorted, and a NaN or +-inf
- * predictor makes the row ineligible.  Outputs are fm_port_args' with a leading [nsel]
- * dimension; forecast_out (optional) receives every row's F.  Months of more than 16,384 rows:
- * FM_ETOOBIG before any launch, outputs untouched.  nsel == 0 or nseg == 0 is a valid empty
- * call.  Zero-initialize the struct (it grows at the end). */
+ *          rounded on its own (fm_forecast's bits on the fm_clip-ped columns).
+ * So a NaN in the coefficient row makes every F of the month NaN, and a NaN or +-inf predictor
+ * makes the row's F not finite.  A row is eligible for sort j when F is finite and level >=
+ * sel_level[j]; forecast_out (optional) receives every row's F. */
 #define FM_MAX_SORTS 16
 #define FM_MAX_SORT_K 30
-typedef struct fm_fport_args {
+typedef struct fm_forecast_src {
     const double* cols;          /* [ncols][col_stride] or NULL (planes) */
     int64_t col_stride;
     const uint32_t* hi_plane;    /* [ncols][plane_stride] high / low words, or NULL (cols) */
     const uint32_t* lo_plane;
     int64_t plane_stride;
-    int32_t ncols;
-    int32_t ret_col;             /* panel column of the realised return */
     const double* lo;            /* [ncols][nseg] clip bounds, or both NULL */
     const double* hi;
-    const double* weight;        /* [rows] or NULL */
-    const uint8_t* level;        /* [rows] universe level or NULL */
-    const uint8_t* nyse;         /* [rows] nonzero = NYSE row, or NULL */
-    const int64_t* seg_off;      /* [nseg+1] */
-    int64_t nrows;               /* seg_off[nseg]: the row stride of port / forecast_out */
+    const double* coef;          /* [nsel][nseg][coef_stride] */
+    double* forecast_out;        /* [nsel][nrows] or NULL */
+    int64_t nrows;               /* seg_off[nseg]: the row stride of the per-row vectors */
+    int32_t ncols;
+    int32_t coef_stride;
+    int32_t nsel;                /* 0 .. FM_MAX_SORTS */
+    int32_t pad_src;
+    int32_t sel_k[FM_MAX_SORTS];
+    int32_t sel_level[FM_MAX_SORTS];
+    int32_t sel_cols[FM_MAX_SORTS][FM_MAX_SORT_K];
+} fm_forecast_src;
+
+/* fm_forecast_portfolio_sort: src.nsel forecast sorts of one panel in one launch (grid (month,
+ * sort)): fm_portfolio_sort's definition with forecast = the F of `src` (fm_forecast_src above),
+ * ret = panel column ret_col (read raw, never clipped, from the same layout) and min_level =
+ * src.sel_level[j] (paper Table 5 inside the device pipeline; no reference line).  A month whose
+ * coefficient row holds a NaN is unsorted.  Outputs are fm_port_args' with a leading [nsel]
+ * dimension.  Months of more than 16,384 rows: FM_ETOOBIG before any launch, outputs untouched.
+ * nsel == 0 or nseg == 0 is a valid empty call.  Zero-initialize the struct (it grows at the
+ * end). */
+typedef struct fm_fport_args {
+    fm_forecast_src src;
+    int32_t ret_col;             /* panel column of the realised return */
     int32_t nseg;
     int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
     int32_t nport;               /* 2 .. FM_MAX_PORTS */
     int32_t nyse_breakpoints;
     int32_t min_count;           /* >= 1 */
-    int32_t nsel;                /* 0 .. FM_MAX_SORTS */
+    const double* weight;        /* [rows] or NULL */
+    const uint8_t* level;        /* [rows] universe level or NULL */
+    const uint8_t* nyse;         /* [rows] nonzero = NYSE row, or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
     double q[FM_MAX_PORTS - 1];
-    int32_t sel_k[FM_MAX_SORTS];
-    int32_t sel_level[FM_MAX_SORTS];
-    int32_t sel_cols[FM_MAX_SORTS][FM_MAX_SORT_K];
-    const double* coef;          /* [nsel][nseg][coef_stride] */
-    int32_t coef_stride;
-    int32_t pad_fport;
     double* bp;                  /* [nsel][nseg][nport-1] or NULL */
     uint8_t* port;               /* [nsel][nrows] or NULL */
     double* rec;                 /* [nsel][nseg][nport+1][4] */
     int32_t* cnt;                /* [nsel][nseg][nport] */
     uint32_t* status;            /* [nsel][nseg] */
-    double* forecast_out;        /* [nsel][nrows] or NULL */
 } fm_fport_args;
 
 int fm_forecast_portfolio_sort(const fm_fport_args* args, void* stream);
@@ -535,13 +541,10 @@ int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count,
  * months seg_off[nseg+1] of at most 16,384 rows (it shares fm_portfolio_sort's selection; longer:
  * FM_ETOOBIG before any launch, outputs untouched).  Exactly one forecast source, anything else
  * FM_EINVAL:
- *   forecast [nsel][nrows]: the caller's vectors (forecast_out must then be NULL), or
- *   cols / col_stride, or hi_plane / lo_plane / plane_stride: the panel, and sort j's forecast
- *   is fm_forecast_portfolio_sort's, bit for bit: with K = sel_k[j], columns sel_cols[j][0..K),
- *   c = coef[(j * nseg + t) * coef_stride + 0..K] and lo / hi [ncols][nseg] (a NaN bound is
- *   ignored; both NULL: no clipping), F = c[0], then for k = 1..K in order
- *   F = F + c[k] * clip(x_k), every operation rounded on its own; forecast_out (optional)
- *   receives every row's F.
+ *   forecast [nsel][nrows]: the caller's vectors (of `src` only nsel, nrows and sel_level are
+ *   then read; its cols, planes and forecast_out must be NULL), or
+ *   the panel of `src` (fm_forecast_src above): sort j's forecast is its F, which is
+ *   fm_forecast_portfolio_sort's, bit for bit.
  * Per (sort j, month t), all outputs with a leading [nsel] dimension:
  *   eligible rows: isfinite(F) and level >= sel_level[j] (level NULL: every row);
  *   cnt    = the number of eligible rows;
@@ -561,34 +564,18 @@ int fm_lagged_coef(const double* roll, const int32_t* idx, const int32_t* count,
  * nseg == 0 is a valid empty call.  Zero-initialize the struct (it grows at the end). */
 #define FM_MAX_DIST_Q 8
 typedef struct fm_fdist_args {
-    const double* forecast;      /* [nsel][nrows] forecast vectors, or NULL (a panel source) */
-    const double* cols;          /* [ncols][col_stride], or NULL */
-    int64_t col_stride;
-    const uint32_t* hi_plane;    /* [ncols][plane_stride] high / low words, or NULL */
-    const uint32_t* lo_plane;
-    int64_t plane_stride;
-    const double* lo;            /* [ncols][nseg] clip bounds, or both NULL */
-    const double* hi;
-    const double* coef;          /* [nsel][nseg][coef_stride] (panel sources) */
+    fm_forecast_src src;
+    const double* forecast;      /* [nsel][nrows] forecast vectors, or NULL (the panel of src) */
     const uint8_t* level;        /* [rows] universe level or NULL */
     const int64_t* seg_off;      /* [nseg+1] */
-    int64_t nrows;               /* seg_off[nseg]: the row stride of forecast / forecast_out */
-    int32_t ncols;
-    int32_t coef_stride;
     int32_t nseg;
     int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
     int32_t min_count;           /* >= 1 */
-    int32_t nsel;                /* 0 .. FM_MAX_SORTS */
     int32_t nq;                  /* 0 .. FM_MAX_DIST_Q */
-    int32_t pad_fdist;
     double q[FM_MAX_DIST_Q];     /* [nq] levels, strictly ascending in (0, 1) */
-    int32_t sel_k[FM_MAX_SORTS];
-    int32_t sel_level[FM_MAX_SORTS];
-    int32_t sel_cols[FM_MAX_SORTS][FM_MAX_SORT_K];
     double* rec;                 /* [nsel][nseg][2+nq] */
     int32_t* cnt;                /* [nsel][nseg] */
     uint32_t* status;            /* [nsel][nseg] */
-    double* forecast_out;        /* [nsel][nrows] or NULL */
 } fm_fdist_args;
 
 int fm_forecast_dist(const fm_fdist_args* args, void* stream);

@@ -13,17 +13,20 @@ import fdist_oracle as FO
 
 
 def _args(L, **kw):
-    """A call with null pointers everywhere: one month, one sort, q = (0.1, 0.9)."""
+    """A call with null pointers everywhere: one month, one sort, q = (0.1, 0.9).  A keyword names
+    a field of the struct or of its embedded fm_forecast_src."""
     a = L.FDistArgs()
-    a.nseg, a.nsel, a.nrows, a.max_seg_len, a.min_count, a.nq = 1, 1, 10, 10, 1, 2
+    a.nseg, a.src.nsel, a.src.nrows, a.max_seg_len, a.min_count, a.nq = 1, 1, 10, 10, 1, 2
     a.q[0], a.q[1] = 0.1, 0.9
+    own = {f[0] for f in L.FDistArgs._fields_}
     for k, v in kw.items():
         if k == "q":
             a.nq = len(v)
             for i, x in enumerate(v[:L.FM_MAX_DIST_Q]):
                 a.q[i] = x
         else:
-            setattr(a, k, v)
+            assert k in own or hasattr(a.src, k), k
+            setattr(a if k in own else a.src, k, v)
     return a
 
 
@@ -66,6 +69,71 @@ def test_argument_checks_return_before_any_launch():
     # the empty calls are valid, pointers and all
     assert _rc(L, _args(L, nsel=0))[0] == 0 and _rc(L, _args(L, nseg=0))[0] == 0
     assert _rc(L, _args(L, nsel=0, q=[]))[0] == 0
+
+
+FAKE = 4096   # a device pointer that is never dereferenced: every call below is refused first
+
+
+def _good_src(f):
+    """A panel source that passes every check: 3 FP64 columns of 10 rows, one sort of K = 2."""
+    f.cols, f.col_stride, f.ncols, f.nrows, f.nsel = FAKE, 10, 3, 10, 1
+    f.sel_k[0], f.sel_cols[0][0], f.sel_cols[0][1] = 2, 1, 2
+    f.coef, f.coef_stride = FAKE, 3
+
+
+def _set(**kw):
+    return lambda f: [setattr(f, k, v) for k, v in kw.items()]
+
+
+def _sel(field, value):
+    def edit(f):
+        if field == "col":
+            f.sel_cols[0][1] = value
+        else:
+            getattr(f, field)[0] = value
+    return edit
+
+
+BAD_SOURCES = [
+    ("cols and planes together", _set(hi_plane=FAKE, lo_plane=FAKE, plane_stride=10), "exactly one"),
+    ("one plane only", _set(cols=None, hi_plane=FAKE, plane_stride=10), "both planes"),
+    ("the other plane only", _set(cols=None, lo_plane=FAKE, plane_stride=10), "both planes"),
+    ("stride below nrows", _set(col_stride=9), "stride below"),
+    ("plane stride below nrows", _set(cols=None, hi_plane=FAKE, lo_plane=FAKE, plane_stride=9), "stride below"),
+    ("K = 0", _sel("sel_k", 0), "K = 0"),
+    ("K = 31", _sel("sel_k", 31), "K = 31"),
+    ("coef_stride below K + 1", _set(coef_stride=2), "coef_stride 2 below K + 1 = 3"),
+    ("column -1", _sel("col", -1), "column -1 outside"),
+    ("column ncols", _sel("col", 3), "column 3 outside"),
+    ("sel_level 256", _sel("sel_level", 256), "sel_level"),
+    ("lo without hi", _set(lo=FAKE), "lo and hi"),
+    ("hi without lo", _set(hi=FAKE), "lo and hi"),
+    ("coef NULL", _set(coef=None), "null pointer"),
+]
+
+
+@pytest.mark.parametrize("what,edit,text", BAD_SOURCES, ids=[b[0] for b in BAD_SOURCES])
+def test_both_fused_entry_points_refuse_a_bad_source_alike(what, edit, text):
+    """fm_forecast_portfolio_sort and fm_forecast_dist embed one fm_forecast_src and check it with
+    one helper: the same bad source gets FM_EINVAL from both, in the same words after the prefix.
+    The outputs and seg_off stay NULL, so even the good source is refused before any launch."""
+    from fmcore import _lib as L
+    lib = L.load()
+    p = L.FPortArgs()
+    p.nseg, p.max_seg_len, p.nport, p.min_count, p.ret_col = 1, 10, 10, 1, 0
+    for j in range(9):
+        p.q[j] = (j + 1) / 10
+    d = _args(L)
+    msgs = []
+    for a, fn, who in ((p, lib.fm_forecast_portfolio_sort, "fm_forecast_portfolio_sort"), (d, lib.fm_forecast_dist, "fm_forecast_dist")):
+        _good_src(a.src)
+        assert fn(ctypes.byref(a), None) == -1 and lib.fm_last_error().decode() == who + ": null pointer"   # the outputs
+        edit(a.src)
+        assert fn(ctypes.byref(a), None) == -1, (what, who)
+        msg = lib.fm_last_error().decode()
+        assert msg.startswith(who + ": ") and text in msg, (what, msg)
+        msgs.append(msg[len(who) + 2:])
+    assert msgs[0] == msgs[1], (what, msgs)
 
 
 def test_restatement_vs_pandas_chain():

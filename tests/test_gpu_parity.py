@@ -1031,6 +1031,67 @@ def test_wide_model_fixup_and_per_stage_vs_oracle(E, monkeypatch):
     assert np.isnan(got_pred[unf, :3]).all()   # rows with no forecast: NaN slope, R2 and n
 
 
+def test_separate_fixup_launch_at_16_columns_equals_inline(E, monkeypatch):
+    """fixup_kernel<16> as its own launch (fm_solve, then fm_solve_fixup on the same struct),
+    which no model reaches by itself: a 16-wide solve does its fix-ups inline.  _wide_panel's
+    three edits on 5 regressors, once as is and once with engine.solve_fix_inline patched to
+    False.  Both launches build their context from the one fm_solve_args, so: the status words
+    of the wide test in both runs; records and moments of the months without FM_ST_REFIT equal
+    bit for bit; the two refit months (reduced over 192 threads inline, 256 in the launch, so
+    rounded differently) each within the wide test's bounds of the oracle."""
+    K = 5
+    df = cases._edge_base(8, 120, K, 313)
+    months = np.sort(df["mthcaldt"].unique())
+    rng = np.random.default_rng(314)
+    df.loc[df.index[(df["mthcaldt"] == months[0]).values][5], "retx"] = np.inf
+    df.loc[df["mthcaldt"] == months[2], "x4"] = 0.5
+    last = (df["mthcaldt"] == months[7]).values
+    df.loc[last, "x2"] = df.loc[last, "x1"] + 1e-7 * rng.standard_normal(int(last.sum()))
+    xs = [f"x{k}" for k in range(K)]
+    P, R2, N, const, _, _ = _wide_oracle(df, xs, months, 4, 2)
+    T = len(months)
+    assert np.isinf(P[0]).all() and np.isfinite(P[1:]).all() and const.tolist() == [t == 2 for t in range(T)]
+
+    names = ["retx"] + xs
+    panel = E.panel_from_arrays([df[c].values for c in names], names, df["mthcaldt"].values)
+    model = [E.Model("narrow", y=0, xs=list(range(1, K + 1)))]
+    assert E.solve_fix_inline(16, K + 1) and not E.solve_fix_inline(32, K + 1) and not E.solve_fix_inline(16, 16)
+    runs = []
+    for inline in (True, False):
+        if not inline:
+            monkeypatch.setattr(E, "solve_fix_inline", lambda zw, pmax: False)
+        with E.KernelTimer() as kt:
+            res = E.fm_pass(panel, model, moments=True)
+        assert ("fm_solve_fixup" in kt.names()) == (not inline) and "fm_solve" in kt.names()
+        assert res.pmax == K + 1
+        runs.append((res.status.cpu().numpy()[:, 0].astype(np.int64), res.rec.cpu().numpy()[:, 0],
+                     res.moments.cpu().numpy()[:, 0]))
+
+    F = E.L
+    want = np.full(T, F.FM_ST_FITTED, dtype=np.int64)
+    want[0] |= F.FM_ST_INF_IN_Y
+    want[2] |= F.FM_ST_CONST_SUSPECT | F.FM_ST_CONST_COL | F.FM_ST_RANK_DEF | F.FM_ST_REFIT
+    want[7] |= F.FM_ST_REFIT
+    (st_a, rec_a, mom_a), (st_b, rec_b, mom_b) = runs
+    assert np.array_equal(st_a, want) and np.array_equal(st_b, want)
+    keep = (want & F.FM_ST_REFIT) == 0
+    assert keep.sum() == T - 2
+    nmom = 1 + (K + 1) + (K + 1) ** 2
+    for a, b, what in ((rec_a, rec_b, "rec"), (mom_a[:, :nmom], mom_b[:, :nmom], "moments")):
+        a, b = a[keep], b[keep]
+        nan = np.isnan(a)
+        assert np.array_equal(nan, np.isnan(b)), what
+        assert np.array_equal(a[~nan].view(np.int64), b[~nan].view(np.int64)), what
+    pmax = K + 1
+    for st, rec, _ in runs:
+        assert np.array_equal(rec[:, pmax + 1].astype(np.int64), N)
+        for j in range(K + 2):
+            got, exp, what = (rec[:, j], P[:, j], f"param {j}") if j <= K else (rec[:, pmax], R2, "R2")
+            s = float(np.sqrt(np.mean(exp[1:7] ** 2)))   # the finite, well-conditioned months
+            assert_series_close(got[2:3], exp[2:3], what + " (constant column)", scale=s)
+            assert_series_close(got[7:], exp[7:], what + " (near-collinear)", rtol=1e-7, scale=s)
+
+
 def _degenerate_std_months(a):
     """A9 edge months: a predictor constant (exactly representable, so its std is exactly
     0) in one month and present in a single row of another: z is all-NaN there."""

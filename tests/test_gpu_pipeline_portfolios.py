@@ -225,11 +225,12 @@ def test_bad_arguments_raise(E, edge):
     # both layouts, neither: through the struct of the last good launch
     run([([1, 2], 0)])
     a = E.LAST_LAUNCH["fm_forecast_portfolio_sort"][1]
-    assert a.cols and not a.hi_plane
-    a.hi_plane, a.lo_plane, a.plane_stride = panel.planes[0].data_ptr(), panel.planes[1].data_ptr(), panel.planes.stride(1)
+    f = a.src
+    assert f.cols and not f.hi_plane
+    f.hi_plane, f.lo_plane, f.plane_stride = panel.planes[0].data_ptr(), panel.planes[1].data_ptr(), panel.planes.stride(1)
     with pytest.raises(L.FMError, match="exactly one"):
         L.call("fm_forecast_portfolio_sort", L.C.byref(a), E._stream())
-    a.cols = a.hi_plane = a.lo_plane = None
+    f.cols = f.hi_plane = f.lo_plane = None
     with pytest.raises(L.FMError, match="exactly one"):
         L.call("fm_forecast_portfolio_sort", L.C.byref(a), E._stream())
     # empty calls: no sort, no month

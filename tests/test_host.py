@@ -28,10 +28,70 @@ def test_library_exports_header_symbols():
         assert hasattr(lib, f), f
         assert f in L.EXPORTED, f"ctypes signature missing for {f}"
     assert L.version().startswith("libfm_hip")
-    a, b = ctypes.c_int32(), ctypes.c_int32()
-    lib.fm_abi_sizes(ctypes.byref(a), ctypes.byref(b))
-    assert a.value == ctypes.sizeof(L.GramArgs)
-    assert b.value == ctypes.sizeof(L.SolveArgs)
+    assert {"fm_gram_args", "fm_solve_args", "fm_forecast_src"} <= set(L._STRUCTS)
+    for name, cls in L._STRUCTS.items():
+        assert lib.fm_struct_size(name.encode()) == ctypes.sizeof(cls), name
+    # every struct the header lists has a binding class, and no other name is known
+    hdr = open(os.path.join(ROOT, "include", "fm_hip.h")).read()
+    listed = re.findall(r"X\((fm_\w+)\)", hdr[hdr.index("#define FM_ARG_STRUCTS"):hdr.index("int64_t fm_struct_size")])
+    assert sorted(listed) == sorted(L._STRUCTS)
+    assert lib.fm_struct_size(b"fm_no_such_args") == -1
+
+
+def _fixup_args(L, **kw):
+    """An fm_solve_fixup call that is valid on its arguments (3 months x 2 problems of up to 15
+    columns); the pointers are never dereferenced: each call below returns before any launch."""
+    fake = 4096
+    a = L.SolveArgs(nseg=3, nprob=2, zw=32, pmax=16, mom_stride=300, prob_level=fake, prob_z=fake, prob_nz=fake,
+                    rec=fake, status=fake, moments=fake, fix_cols=fake, fix_stride=100, fix_seg_off=fake,
+                    fix_check_const=1)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_solve_fixup_refuses_on_arguments_alone():
+    import ctypes
+    from fmcore import _lib as L
+    lib = L.load()
+
+    def rc(a):
+        r = lib.fm_solve_fixup(None if a is None else ctypes.byref(a), None)
+        return r, lib.fm_last_error().decode()
+
+    fake = 4096
+    bad = [(None, "null args"),
+           (_fixup_args(L, fix_cols=None), "null pointer"),
+           (_fixup_args(L, fix_hi_plane=fake, fix_lo_plane=fake), "plane"),
+           (_fixup_args(L, fix_cols=None, fix_hi_plane=fake, fix_lo_plane=fake), "plane"),
+           (_fixup_args(L, fix_hi_plane=fake), "plane"),
+           (_fixup_args(L, fix_lo=fake), "fix_lo and fix_hi"),
+           (_fixup_args(L, fix_hi=fake), "fix_lo and fix_hi"),
+           (_fixup_args(L, fix_inv_scale=fake), "fix_inv_scale needs fix_shift"),
+           (_fixup_args(L, moments=None), "moments"),
+           (_fixup_args(L, fix_seg_off=None), "fix_seg_off"),
+           (_fixup_args(L, pmax=1), "pmax"),
+           (_fixup_args(L, pmax=33), "pmax")]
+    for a, text in bad:
+        r, msg = rc(a)
+        assert r == -1 and msg.startswith("fm_solve_fixup: ") and text in msg, (text, r, msg)
+    # the same conditions refuse fm_solve's inline fix-ups, in the same words after the prefix
+    for kw in (dict(fix_lo=fake), dict(fix_inv_scale=fake), dict(moments=None), dict(fix_seg_off=None)):
+        a = _fixup_args(L, zw=16, pmax=15, partial=fake, seg_chunk_off=fake, pattern_models=fake, prob_model=fake,
+                        prob_flags=fake, npatterns=1, nlevels=1, **kw)
+        r1, m1 = rc(a)
+        r2 = lib.fm_solve(ctypes.byref(a), None)
+        m2 = lib.fm_last_error().decode()
+        assert r1 == r2 == -1 and m1.split(": ", 1)[1] == m2.split(": ", 1)[1] and m2.startswith("fm_solve: "), (kw, m1, m2)
+    # and fm_solve still refuses the fix-ups with the 32-wide solve
+    a = _fixup_args(L, partial=fake, seg_chunk_off=fake, pattern_models=fake, prob_model=fake, prob_flags=fake,
+                    npatterns=1, nlevels=1)
+    assert lib.fm_solve(ctypes.byref(a), None) == -1 and "zw 16" in lib.fm_last_error().decode()
+    # nothing to scan: valid, nothing launched
+    assert rc(_fixup_args(L, nseg=0))[0] == 0 and rc(_fixup_args(L, nprob=0))[0] == 0
+    # with every condition met the struct passes the checks of both entry points' shared helper:
+    # lo with hi and inv_scale with shift are accepted (nseg = 0, so still no launch)
+    assert rc(_fixup_args(L, nseg=0, fix_lo=fake, fix_hi=fake, fix_shift=fake, fix_inv_scale=fake))[0] == 0
 
 
 def test_library_is_gfx950_code_object(tmp_path):
