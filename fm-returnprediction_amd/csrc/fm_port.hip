@@ -30,6 +30,9 @@
 //
 // fm_forecast_dist (A14; paper Table 3) is fdist_kernel below: the same phases 1-2 from the same
 // three sources, then two fixed-order reductions of the forecasts instead of phases 3-4.
+//
+// fm_forecast_compare (A15; paper Table 4) is fcmp_kernel below, over a grid of (month, pair):
+// phase 1's load for the pair's two forecasts, then eleven of those reductions and no selection.
 #include <math.h>
 
 #include "fm_common.h"
@@ -842,6 +845,185 @@ int launch_fdist(const fm_fdist_args& a, size_t lds, hipStream_t st) {
     return check_launch(who);
 }
 
+// ---- fm_forecast_compare (extension A15; paper Table 4) --------------------------------------
+// Per (month, pair): forecast b regressed on forecast a over the rows where both are finite, then
+// the realised return regressed on that regression's residual.  Phase 1 is fdist_kernel's load,
+// twice (fused_forecast for the pair's two sorts, or the caller's two vectors); no order
+// statistics follow, so there are no keys: the month stays in registers and eleven tile_sums
+// (2 + 3 + 3 + 3) reduce it.  The register budget of the 1024 x 16 form (128 VGPRs) holds two row
+// sets of 16 doubles, not three: the deviations replace the forecasts, the residual replaces
+// F_b's deviation, and the return is loaded only then, into the registers F_a's deviation has
+// left.  Each forecast column is read from HBM once per pair, the return once.
+
+// The plain source of fm_forecast_compare: the caller's forecast vectors and return vector
+struct CmpVecSrc {
+    static constexpr bool FUSED = false;
+};
+
+// The fused 1024 x 16 form: F_a, F_b and the load's 16 panel values in flight are three row sets, so
+// F_a waits in dynamic LDS (8 bytes a row, 128 KB: the form has one workgroup per CU anyway)
+template <int VPT, class Src>
+constexpr bool fcmp_parks() {
+    return Src::FUSED && VPT > 10;
+}
+
+template <int NT, int VPT, class Src>
+__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fcmp_kernel(fm_fcmp_args a) {
+    constexpr int NW = NT / WAVE;
+    constexpr bool FUSED = Src::FUSED;
+    constexpr bool PARK = fcmp_parks<VPT, Src>();
+    extern __shared__ double s_park[];   // PARK: F_a while F_b's load has the registers
+    __shared__ double s_tile[NW * VPT + 1];
+    __shared__ int s_iscr[NW];
+    const int s = blockIdx.x, p = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int ja = a.pair_a[p], jb = a.pair_b[p], min_level = a.pair_level[p];
+    const int64_t r0 = a.seg_off[s];
+    int L = (int)(a.seg_off[s + 1] - r0);
+    L = L < a.max_seg_len ? L : a.max_seg_len;   // the workgroup's form was chosen from max_seg_len
+    const int last = L - 1;
+    const int64_t so = s + (int64_t)p * a.nseg;
+    double* rec = a.rec + so * FM_FCMP_NREC;
+
+    // ---- 1. the two forecasts, set E ----------------------------------------------------------
+    double fa[VPT], fb[VPT];   // F_a, F_b; then their deviations; fb then the residual, fa the return
+    uint32_t em = 0;           // bit v: row v of this thread is in E
+    if (L > 0) {               // block-uniform
+        if constexpr (FUSED) {
+            const Src sa{a.src, ja}, sb{a.src, jb};
+            fused_forecast<VPT>(sa, a.nseg, s, s + (int64_t)ja * a.nseg, r0 + (int64_t)ja * a.src.nrows, r0, L, w, lane, fa);
+            if constexpr (PARK) {   // each thread parks and fetches its own rows: no barrier
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) s_park[(w * VPT + v) * WAVE + lane] = fa[v];
+            }
+            fused_forecast<VPT>(sb, a.nseg, s, s + (int64_t)jb * a.nseg, r0 + (int64_t)jb * a.src.nrows, r0, L, w, lane, fb);
+            if constexpr (PARK) {
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) fa[v] = s_park[(w * VPT + v) * WAVE + lane];
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
+            const int idx = (w * VPT + v) * WAVE + lane;
+            const int ci = idx < L ? idx : last;
+            if constexpr (!FUSED) {
+                fa[v] = a.forecast[(int64_t)ja * a.src.nrows + r0 + ci];
+                fb[v] = a.forecast[(int64_t)jb * a.src.nrows + r0 + ci];
+            }
+            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
+            em |= (idx < L && isfinite(fa[v]) && isfinite(fb[v]) && lv >= min_level) ? 1u << v : 0u;
+        }
+    }
+    const int nE = block_sum<NW>((int)__popc(em), s_iscr);
+    const int need = a.min_count > 2 ? a.min_count : 2;
+
+    // the thread's returns (into x) and its rows of set R, read once, when the registers are free
+    uint32_t rm = 0;   // bit v: row v of this thread is in R
+    auto load_returns = [&](double (&x)[VPT]) {
+        if (L <= 0) return;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = (w * VPT + v) * WAVE + lane;
+            const int ci = idx < L ? idx : last;
+            if constexpr (FUSED) x[v] = Src{a.src, 0}.value(a.ret_col, r0 + ci);   // the same layout view
+            else x[v] = a.ret[r0 + ci];
+            rm |= (((em >> v) & 1u) && isfinite(x[v])) ? 1u << v : 0u;
+        }
+    };
+    if (nE < need) {   // block-uniform: the month has no regression
+        load_returns(fa);
+        const int nR = block_sum<NW>((int)__popc(rm), s_iscr);
+        if (tid == 0) {
+            a.cnt[so * 2] = nE;
+            a.cnt[so * 2 + 1] = nR;
+            a.status[so] = 0u;
+        }
+        if (tid < FM_FCMP_NREC) rec[tid] = NAN;
+        return;
+    }
+
+    // ---- 2. b on a over E: means, centered moments, the residual's own sum ---------------------
+    double x[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fa[v] : 0.0;
+    const double ma = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fb[v] : 0.0;
+    const double mb = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        fa[v] = fa[v] - ma;   // da
+        fb[v] = fb[v] - mb;   // db
+    }
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fa[v] * fa[v] : 0.0;
+    const double Saa = tile_sum<NW, VPT>(x, s_tile, w, lane);
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fb[v] * fb[v] : 0.0;
+    const double Sbb = tile_sum<NW, VPT>(x, s_tile, w, lane);
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fa[v] * fb[v] : 0.0;
+    const double Sab = tile_sum<NW, VPT>(x, s_tile, w, lane);
+    const double beta = Sab / Saa;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) fb[v] = fb[v] - beta * fa[v];   // e
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fb[v] * fb[v] : 0.0;
+    const double See0 = tile_sum<NW, VPT>(x, s_tile, w, lane);
+
+    // ---- 3. the return on the residual over R ---------------------------------------------------
+    load_returns(fa);   // r
+    const int nR = block_sum<NW>((int)__popc(rm), s_iscr);
+    double pslope = NAN, picept = NAN, pr2 = NAN;
+    if (nR >= 2) {   // block-uniform
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fb[v] : 0.0;
+        const double me = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fa[v] : 0.0;
+        const double mr = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            fb[v] = fb[v] - me;
+            fa[v] = fa[v] - mr;
+        }
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fb[v] * fb[v] : 0.0;
+        const double See = tile_sum<NW, VPT>(x, s_tile, w, lane);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fb[v] * fa[v] : 0.0;
+        const double Ser = tile_sum<NW, VPT>(x, s_tile, w, lane);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fa[v] * fa[v] : 0.0;
+        const double Srr = tile_sum<NW, VPT>(x, s_tile, w, lane);
+        pslope = Ser / See;
+        picept = mr - pslope * me;
+        pr2 = (Ser * Ser) / (See * Srr);
+    }
+    if (tid == 0) {
+        rec[0] = Sab / sqrt(Saa * Sbb);
+        rec[1] = beta;
+        rec[2] = mb - beta * ma;
+        rec[3] = sqrt(See0 / (double)(nE - 1));
+        rec[4] = pslope;
+        rec[5] = picept;
+        rec[6] = pr2;
+        a.cnt[so * 2] = nE;
+        a.cnt[so * 2 + 1] = nR;
+        a.status[so] = 1u;
+    }
+}
+
+template <int NT, int VPT, class Src>
+int launch_fcmp(const fm_fcmp_args& a, hipStream_t st) {
+    const char* who = "fm_forecast_compare";
+    const size_t lds = fcmp_parks<VPT, Src>() ? 8 * (size_t)NT * VPT : 0;
+    if (lds >= 64 * 1024 && raise_dynamic_lds<fcmp_kernel<NT, VPT, Src>>(lds, who) != FM_OK) return FM_EHIP;
+    hipLaunchKernelGGL((fcmp_kernel<NT, VPT, Src>), dim3(a.nseg, a.npair), dim3(NT), lds, st, a);
+    return check_launch(who);
+}
+
 }  // namespace
 }  // namespace fm
 
@@ -907,5 +1089,40 @@ extern "C" int fm_forecast_dist(const fm_fdist_args* args, void* stream) {
     return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
         if (vec) return launch_fdist<nt, vpt, VecSrc>(a, lds, st);
         return pl ? launch_fdist<nt, vpt, PanelSrc<true>>(a, lds, st) : launch_fdist<nt, vpt, PanelSrc<false>>(a, lds, st);
+    });
+}
+
+extern "C" int fm_forecast_compare(const fm_fcmp_args* args, void* stream) {
+    using namespace fm;
+    const char* who = "fm_forecast_compare";
+    FM_REQUIRE(args != nullptr, "%s: null args", who);
+    const fm_fcmp_args& a = *args;
+    FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
+    FM_REQUIRE(a.npair >= 0 && a.npair <= FM_MAX_PAIRS, "%s: npair must be 0..%d", who, FM_MAX_PAIRS);
+    FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
+    if (a.max_seg_len > PORT_MAX_ROWS) {
+        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
+        return FM_ETOOBIG;
+    }
+    const bool vec = a.forecast != nullptr;
+    if (const int rc = check_forecast_src(a.src, a.nseg, who, vec)) return rc;
+    for (int p = 0; p < a.npair; ++p) {
+        FM_REQUIRE(a.pair_a[p] >= 0 && a.pair_a[p] < a.src.nsel && a.pair_b[p] >= 0 && a.pair_b[p] < a.src.nsel,
+                   "%s: pair %d (%d, %d) outside the %d forecasts", who, p, a.pair_a[p], a.pair_b[p], a.src.nsel);
+        FM_REQUIRE(a.pair_level[p] >= 0 && a.pair_level[p] <= 255, "%s: pair_level must be 0..255", who);
+    }
+    if (a.nseg == 0 || a.npair == 0) return FM_OK;   // nothing is read: an empty call has no pointers
+    if (vec) {
+        FM_REQUIRE(a.ret != nullptr, "%s: forecast vectors need ret", who);
+    } else {
+        FM_REQUIRE(a.ret == nullptr, "%s: ret goes with forecast vectors (the panel's return is ret_col)", who);
+        FM_REQUIRE(a.ret_col >= 0 && a.ret_col < a.src.ncols, "%s: ret_col outside the panel", who);
+    }
+    FM_REQUIRE(a.seg_off && a.rec && a.cnt && a.status, "%s: null pointer", who);
+    const bool pl = a.src.hi_plane != nullptr;
+    const hipStream_t st = (hipStream_t)stream;
+    return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
+        if (vec) return launch_fcmp<nt, vpt, CmpVecSrc>(a, st);
+        return pl ? launch_fcmp<nt, vpt, PanelSrc<true>>(a, st) : launch_fcmp<nt, vpt, PanelSrc<false>>(a, st);
     });
 }

@@ -1455,6 +1455,146 @@ def forecast_dist_summary(d: ForecastDist, nw_lags=4):
     return ts_summary(d.rec, k, T * k, ix, T, S, k, nw_lags)
 
 
+@dataclass
+class ForecastCompare:
+    rec: torch.Tensor      # [npair, T, 7] float64: correlation, slope, intercept, residual sd (ddof 1) of
+    #                        F_b on F_a; slope, intercept, R2 of the return on the residual (NaN: status 0)
+    cnt: torch.Tensor      # [npair, T, 2] int32: rows with both forecasts; those with a return as well
+    status: torch.Tensor   # [npair, T] int32: 1 = the month has at least max(min_count, 2) such rows
+    forecast: Optional[torch.Tensor] = None   # [nsel, rows] float64 (forecast_compare, on request)
+
+
+def _pair_batches(who, pairs, nsel):
+    """``pairs`` = [(a, b, min_level), ...] cut greedily, in order, into launches of at most
+    FM_MAX_PAIRS pairs over at most FM_MAX_SORTS distinct forecasts -> (pairs, [(p0, part, js)]):
+    ``part`` the launch's pairs from pair p0 on with a and b as indices into ``js``, the launch's
+    forecasts in ascending order."""
+    pairs = [(int(a), int(b), int(lv)) for a, b, lv in pairs]
+    for a, b, _ in pairs:
+        if not (0 <= a < nsel and 0 <= b < nsel):
+            raise ValueError(f"{who}: pair ({a}, {b}) outside the {nsel} forecasts")
+    cuts, p0, js = [], 0, set()
+    for p, (a, b, _) in enumerate(pairs):
+        if p - p0 == L.FM_MAX_PAIRS or len(js | {a, b}) > L.FM_MAX_SORTS:
+            cuts.append((p0, p, sorted(js)))
+            p0, js = p, set()
+        js |= {a, b}
+    cuts.append((p0, len(pairs), sorted(js)))
+    return pairs, [(p0, [(js.index(a), js.index(b), lv) for a, b, lv in pairs[p0:p1]], js) for p0, p1, js in cuts]
+
+
+def _compare_plan(who, npair, T, nsel, n, forecast_out, out, dev):
+    """The ``ForecastCompare`` to fill (``out`` checked, else allocated) and ``fill(a, p0, part)``,
+    which sets an argument struct's pairs and its outputs from pair p0 on."""
+    shapes = dict(rec=((npair, T, L.FM_FCMP_NREC), torch.float64), cnt=((npair, T, 2), torch.int32),
+                  status=((npair, T), torch.int32))
+    if forecast_out:
+        shapes["forecast"] = ((nsel, n), torch.float64)
+    if out is None:
+        out = ForecastCompare(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    for k, (sh, dt) in shapes.items():
+        t = getattr(out, k)
+        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+
+    def fill(a, p0, part):
+        a.npair, a.nseg = len(part), T
+        for i, (ja, jb, lv) in enumerate(part):
+            a.pair_a[i], a.pair_b[i], a.pair_level[i] = ja, jb, lv
+        if npair:
+            a.rec, a.cnt, a.status = out.rec[p0:].data_ptr(), out.cnt[p0:].data_ptr(), out.status[p0:].data_ptr()
+        return a
+
+    return out, fill
+
+
+def _rows_of(t, js):
+    """Rows ``js`` (ascending) of ``t`` as one contiguous block: a view where they are consecutive."""
+    if js and js[-1] - js[0] + 1 == len(js):
+        return t[js[0]:js[-1] + 1]
+    return t[js].contiguous()
+
+
+def forecast_compare(panel: DevicePanel, coef, sel, pairs, cuts: Cuts = None, ret="retx", level=None, min_count=1,
+                     forecast_out=False, out: "ForecastCompare" = None):
+    """A15 (paper Table 4, model comparison): for every pair (a, b, min_level) of ``pairs`` -- a and b
+    indices into ``sel``, the forecasts of ``forecast_dist`` (``sel`` = [(xs, level), ...] whose level
+    is not read here, ``coef`` [nsel, T, >= K+1], ``cuts`` as there) -- and every month: forecast b
+    regressed on forecast a across the rows of the universe ``min_level`` where both are finite
+    (correlation, slope, intercept, residual standard deviation), then the panel column ``ret`` on
+    that residual (slope, intercept, R2).  Both forecasts are computed in the kernel's load phase,
+    bit for bit ``forecast_dist``'s (fm_forecast_compare; the definition is in fm_hip.h).  One launch
+    per FM_MAX_PAIRS pairs over at most FM_MAX_SORTS distinct forecasts, cut greedily in the pairs'
+    order.  Returns ``ForecastCompare`` with a leading [npair] dimension; ``forecast_out``: also the
+    forecasts [nsel, rows] (the rows of a forecast no pair names are NaN); ``out``: a
+    ``ForecastCompare`` of that shape to write into (else allocated)."""
+    src, sel, coef, lo, hi = _forecast_plan("forecast_compare", panel, coef, sel, cuts)
+    dev = src.device
+    n, T, nsel = panel.nrows, panel.nseg, len(sel)
+    pairs, batches = _pair_batches("forecast_compare", pairs, nsel)
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    out, fill = _compare_plan("forecast_compare", len(pairs), T, nsel, n, forecast_out, out, dev)
+    if forecast_out:
+        unused = sorted(set(range(nsel)) - {j for a, b, _ in pairs for j in (a, b)})
+        if unused:
+            out.forecast[unused] = float("nan")
+    for p0, part, js in batches:
+        a = fill(L.FCmpArgs(), p0, part)
+        cj = _rows_of(coef, js)
+        fj = _rows_of(out.forecast, js) if forecast_out else None
+        _fill_forecast_src(a.src, n, [sel[j] for j in js], 0, src, cj, lo, hi, fj)
+        a.ret_col = panel.col(ret) if isinstance(ret, str) else int(ret)
+        a.level, a.seg_off, a.max_seg_len, a.min_count = _ptr(level), panel.seg_off.data_ptr(), panel.max_seg_len, int(min_count)
+        _kcall("fm_forecast_compare", "fm_forecast_compare", L.C.byref(a), _stream())
+        _remember("fm_forecast_compare", "fm_forecast_compare", a, src, panel.planes, panel.seg_off, cj, fj, lo, hi, level, out)
+        if js and fj is not None and fj.data_ptr() != out.forecast[js[0]].data_ptr():   # a gathered copy
+            out.forecast[js] = fj
+    return out
+
+
+def forecast_compare_vector(seg_off, forecast, ret, pairs, level=None, min_count=1, max_seg_len=None):
+    """A15 on forecast vectors the caller holds: ``forecast`` float64 [nsel, rows] and the realised
+    return ``ret`` float64 [rows] on the device, months ``seg_off`` int64 [T+1]; ``pairs`` =
+    [(a, b, min_level), ...] regresses vector b on vector a over the rows with ``level`` >=
+    min_level where both are finite.  Returns ``ForecastCompare`` with a leading [npair] dimension.
+    ``max_seg_len``: the longest month if the caller knows it (otherwise read from ``seg_off``, one
+    host sync)."""
+    dev = forecast.device
+    if forecast.dtype != torch.float64 or forecast.dim() != 2:
+        raise ValueError("forecast_compare_vector: forecast must be a float64 [nsel, rows] tensor")
+    forecast = forecast.contiguous()
+    nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("forecast_compare_vector: seg_off must be an int64 [T+1] tensor on the forecast's device")
+    seg_off = seg_off.contiguous()
+    T = int(seg_off.shape[0]) - 1
+    ret = _row_vector(ret, torch.float64, n, dev, "ret")
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    pairs, batches = _pair_batches("forecast_compare_vector", pairs, nsel)
+    if max_seg_len is None:
+        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    out, fill = _compare_plan("forecast_compare_vector", len(pairs), T, nsel, n, False, None, dev)
+    for p0, part, js in batches:
+        a = fill(L.FCmpArgs(), p0, part)
+        fj = _rows_of(forecast, js)
+        _fill_forecast_src(a.src, n, [((), 0)] * len(js))
+        a.forecast, a.ret = fj.data_ptr() if js else None, _ptr(ret)
+        a.level, a.seg_off, a.max_seg_len, a.min_count = _ptr(level), seg_off.data_ptr(), int(max_seg_len), int(min_count)
+        _kcall("fm_forecast_compare", "fm_forecast_compare", L.C.byref(a), _stream())
+        _remember("fm_forecast_compare", "fm_forecast_compare", a, seg_off, fj, ret, level, out)
+    return out
+
+
+def forecast_compare_summary(c: ForecastCompare, nw_lags=4):
+    """FM mean, Newey-West s.e., t and nobs of the 7 monthly series of ``c.rec`` over the months with
+    status 1, NaN entries dropped per series (a constant forecast, a zero residual, a month without
+    returns) -> ``Summary`` with [npair, 7] tensors: every pair is one problem of the two launches
+    ``forecast_dist_summary`` issues."""
+    S, T, k = c.rec.shape
+    ix = ts_compact(c.status, 1, T, T, S)
+    return ts_summary(c.rec, k, T * k, ix, T, S, k, nw_lags)
+
+
 # fm_rank_transform's month limit (FM_RANK_MAX_ROWS): up to 16,384 rows one workgroup per (month,
 # column) sorts the month's keys in LDS; a longer month is ranked in parts of 16,384 rows, at a cost
 # quadratic in the part count, so four parts are the limit

@@ -11,6 +11,9 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
     problem (paper Table 5, build-defined A12) in one more launch that forecasts and sorts
  -> optionally (``PipelineConfig.forecast_dist``) each month's mean, standard deviation and
     quantiles of those forecasts (paper Table 3, build-defined A14), likewise in one launch
+ -> optionally (``PipelineConfig.forecast_compare``) per universe and pair of Table-2 models the
+    monthly regression of one model's forecast on the other's and of returns on its residual
+    (paper Table 4, build-defined A15), likewise in one launch
 All stages are libfm_hip kernels; the panel is read from HBM twice (cuts, Gram).
 """
 from __future__ import annotations
@@ -92,6 +95,11 @@ class PipelineConfig:
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
     forecast_dist: bool = field(default=False, kw_only=True)
     forecast_dist_q: Sequence[float] = field(default=(0.1, 0.9), kw_only=True)
+    # A15 inside the pipeline (paper Table 4, model comparison): for every universe and every pair
+    # i < j of the Table-2 models (not Figure 1), each month's regression of forecast j on forecast i
+    # and of the return on its residual, from the same forecasts under the same two rules as
+    # ``portfolios``; off = no launch more.
+    forecast_compare: bool = field(default=False, kw_only=True)
     rank: Optional[str] = None     # A13: predictors -> per-month ranks, a scale name ("raw", "pct", "uniform")
 
 
@@ -115,6 +123,9 @@ class PipelineResult:
     forecast_dist: Optional[E.ForecastDist] = None       # cfg.forecast_dist: [nsort, T, 2+nq] and [nsort, T]
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
+    forecast_compare: Optional[E.ForecastCompare] = None     # cfg.forecast_compare: [npair, T, 7], [npair, T, 2], [npair, T]
+    forecast_compare_summary: Optional[E.Summary] = None     # [npair, 7]
+    forecast_compare_pairs: Optional[List[tuple]] = None     # (problem_a, problem_b) of each pair: b regressed on a
 
 
 def build_models(panel: E.DevicePanel, model_cols: Dict[str, List[str]], y="retx", fig1=True,
@@ -222,7 +233,8 @@ def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo
 def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=None, y="retx"):
     cfg = cfg or PipelineConfig()
     model_cols = model_cols or table2_models()
-    for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist")):
+    for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
+                     (cfg.forecast_compare, "forecast_compare")):
         if on and cfg.standardize:
             raise ValueError(f"PipelineConfig: {what} excludes standardize (coefficients on z-scores "
                              "need the moment tables)")
@@ -235,8 +247,9 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
         psumm, _ = E.summarize_predictive(pred, pst, cfg.nw_lags)
     ports = port_summ = port_probs = None
     dist = dist_summ = dist_probs = None
-    if cfg.portfolios is not None or cfg.forecast_dist:
-        # Tables 5 and 3: every Table-2 problem's forecast, sorted or summarized in one launch each
+    comp = comp_summ = comp_pairs = None
+    if cfg.portfolios is not None or cfg.forecast_dist or cfg.forecast_compare:
+        # Tables 5, 3 and 4: every Table-2 problem's forecast, sorted, summarized or compared in one launch each
         # on the panel the Gram read, with the pipeline's cuts and the coefficient rows the
         # predictive stage read
         probs = [k for k, p in enumerate(res.problems) if names[p.model] != "Figure 1"]
@@ -246,6 +259,14 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
         dist_probs = probs
         dist = E.forecast_dist(gpanel, coef, sel, cuts=cuts, level=level, q=cfg.forecast_dist_q)
         dist_summ = E.forecast_dist_summary(dist, cfg.nw_lags)
+    if cfg.forecast_compare:
+        # universe by universe, model j's forecast on model i's for i < j (both fitted on that universe)
+        at = {(res.problems[k].level, res.problems[k].model): j for j, k in enumerate(probs)}
+        pairs = [(at[u, mi], at[u, mj], u) for u in sorted({u for u, _ in at})
+                 for mi in range(len(names)) for mj in range(mi + 1, len(names)) if (u, mi) in at and (u, mj) in at]
+        comp_pairs = [(probs[a], probs[b]) for a, b, _ in pairs]
+        comp = E.forecast_compare(gpanel, coef, sel, pairs, cuts=cuts, ret=gpanel.col(y), level=level)
+        comp_summ = E.forecast_compare_summary(comp, cfg.nw_lags)
     if cfg.portfolios is not None:
         port_probs = probs
         ports = E.forecast_portfolio_sort(gpanel, coef, sel, cuts=cuts, ret=gpanel.col(y), weight=gpanel.me,
@@ -256,7 +277,8 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                           res=res, ix=ix, summary=summ, rolling=roll, pred=pred, pred_status=pst,
                           pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
                           portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
-                          forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs)
+                          forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
+                          forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

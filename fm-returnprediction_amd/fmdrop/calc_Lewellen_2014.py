@@ -10,7 +10,7 @@ Mirrored (same names, signatures, return types and row/column/index order):
 Extensions the north star names (not in the reference; parity unpinned):
   standardize, rank_transform, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
   predictive_slope_regressions, forecast_sorted_portfolios, forecast_distribution,
-  lewellen_pipeline, build_table_5, build_table_3.
+  forecast_comparison, lewellen_pipeline, build_table_5, build_table_3, build_table_4.
 Firm-axis characteristic builders (§8(f) row 2; one fused device pass, fm_firm_chars):
   calc_log_size, calc_log_bm, calc_return_12_2, calc_accruals, calc_roa,
   calc_log_assets_growth, calc_dy, calc_log_return_13_36, calc_log_issues_12,
@@ -764,6 +764,46 @@ def _dist_frames(status, rec, cnt, mean, tstat, nobs, months, q, date_col="mthca
     return monthly, summary
 
 
+COMPARISON_COLUMNS = ["corr", "slope", "intercept", "res_std", "pred_slope", "pred_intercept", "pred_r2"]
+
+
+def forecast_comparison(df: pd.DataFrame, forecast_a, forecast_b, return_col: str = "retx", universe: str = None,
+                        date_col: str = "mthcaldt", nw_lags: int = 4):
+    """A15 (paper Table 4, model comparison): each month, ``forecast_b`` regressed on ``forecast_a``
+    across the rows where both are finite (corr, slope, intercept and the residual's ddof-1 standard
+    deviation res_std), then ``return_col`` regressed on that residual over the rows that also have
+    a return (pred_slope, pred_intercept, pred_r2), on the device (fm_forecast_compare).
+    ``universe`` in {None, "all_but_tiny", "large"} keeps the rows of that get_subsets universe
+    (from ``me`` and ``primaryexch``).
+    Returns (monthly, summary): ``monthly`` is indexed by month with those seven columns, n (rows
+    with both forecasts) and n_ret (those with a return), months of fewer than two rows absent;
+    ``summary`` is indexed by the seven columns with columns mean / se / tstat / nobs: the
+    time-series average, its Newey-West(nw_lags) standard error and t-statistic."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    fa, fb = (np.asarray(f, dtype=np.float64) for f in (forecast_a, forecast_b))
+    if fa.shape != (len(df),) or fb.shape != (len(df),):
+        raise ValueError("forecast_a and forecast_b must hold one value per row of df")
+    order = np.lexsort((df["permno"].to_numpy(), df[date_col].to_numpy()))
+    d = df.iloc[order]
+    me = _api.as_f64(d["me"]) if universe is not None else None
+    nyse = (d["primaryexch"] == "N").to_numpy().astype(np.uint8) if universe is not None else None
+    panel = _E.panel_from_arrays([fa[order], fb[order], _api.as_f64(d[return_col])], ["a", "b", return_col],
+                                 d[date_col].values, me=me, nyse=nyse)
+    level = _E.universe(panel)[2] if universe is not None else None
+    c = _E.forecast_compare_vector(panel.seg_off, panel.cols[:2], panel.cols[2], [(0, 1, _UNIVERSE_LEVEL[universe])],
+                                   level=level, max_seg_len=panel.max_seg_len)
+    s = _E.forecast_compare_summary(c, nw_lags)
+    ok = c.status[0].cpu().numpy() == 1
+    monthly = pd.DataFrame(c.rec[0].cpu().numpy()[ok], index=pd.Index(np.asarray(panel.months)[ok], name=date_col),
+                           columns=COMPARISON_COLUMNS)
+    cnt = c.cnt[0].cpu().numpy()[ok].astype(np.int64)
+    monthly["n"], monthly["n_ret"] = cnt[:, 0], cnt[:, 1]
+    summary = pd.DataFrame({k: getattr(s, k)[0].cpu().numpy() for k in ("mean", "se", "tstat", "nobs")},
+                           index=pd.Index(COMPARISON_COLUMNS, name="statistic"))
+    return monthly, summary
+
+
 def _pipeline_panel(crsp_comp: pd.DataFrame, variables_dict: dict = None):
     """The device panel and the Table-2 models of a crsp_comp frame (rows by (month, permno))."""
     vd = variables_dict or _LW.VARIABLES_DICT
@@ -831,3 +871,26 @@ def build_table_3(crsp_comp: pd.DataFrame, variables_dict: dict = None, q=(0.1, 
         rows.append(list(dmean[j]) + [pmean[k, 0], pse[k, 0], pt[k, 0], pmean[k, 1]])
     return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(keys, names=["model", "universe"]),
                         columns=["Avg", "Std"] + _dist_columns(q) + ["Slope", "S.E.", "t-stat", "R2"])
+
+
+def build_table_4(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):
+    """Paper Table 4 (model comparison) from ONE device pipeline run (build-defined; no reference
+    line): for every universe and every pair i < j of the Table-2 models, how much of model j's
+    out-of-sample forecast model i's already holds -- the time-series averages of each month's
+    cross-sectional ``Correlation``, ``Slope`` and residual standard deviation (``Res. std.``) of
+    forecast j regressed on forecast i -- and whether the rest predicts returns: the Fama-MacBeth
+    slope of returns on that residual (``Pred. slope``) with its Newey-West standard error and
+    t-statistic.  ``cfg``: further PipelineConfig fields (window, min_periods, lag, nw_lags, ...).
+    Returns a DataFrame indexed by (universe, "Model j on Model i")."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    out = _LW.run_pipeline(panel, _LW.PipelineConfig(**dict(cfg, forecast_compare=True)), model_cols=model_cols)
+    s = out.forecast_compare_summary
+    mean, se, t = s.mean.cpu().numpy(), s.se.cpu().numpy(), s.tstat.cpu().numpy()
+    keys, rows = [], []
+    for p, (ka, kb) in enumerate(out.forecast_compare_pairs):
+        pa, pb = out.res.problems[ka], out.res.problems[kb]
+        short = [out.model_names[q.model].split(":")[0] for q in (pb, pa)]
+        keys.append((_LW.SUBSET_NAMES[pa.level], "%s on %s" % tuple(short)))
+        rows.append([mean[p, 0], mean[p, 1], mean[p, 3], mean[p, 4], se[p, 4], t[p, 4]])
+    return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(keys, names=["universe", "comparison"]),
+                        columns=["Correlation", "Slope", "Res. std.", "Pred. slope", "S.E.", "t-stat"])

@@ -50,6 +50,9 @@
  *   fm_forecast_dist <- build-defined extension A14: per-month mean, standard deviation and
  *                      quantiles of the forecasts (paper Table 3's univariate properties); no
  *                      reference line
+ *   fm_forecast_compare <- build-defined extension A15: per month and pair of forecasts, the
+ *                      cross-sectional regression of one forecast on the other and of returns
+ *                      on its residual (paper Table 4, "model comparison"); no reference line
  *   fm_rank_transform <- build-defined extension A13: per-month cross-sectional ranks of the
  *                      characteristics (pandas groupby(month)[x].rank); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
@@ -207,7 +210,7 @@ const char* fm_last_error(void);
 #define FM_ARG_STRUCTS(X)                                                                     \
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
-    X(fm_fdist_args)
+    X(fm_fdist_args) X(fm_fcmp_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -459,7 +462,7 @@ int fm_portfolio_sort(const fm_port_args* args, void* stream);
 
 /* fm_forecast_src: the fused forecast -- nsel forecasts of one panel, each row's value computed
  * in the consuming kernel's load phase from the panel's own layout instead of read from a vector.
- * It is embedded as the field `src` of fm_fport_args and fm_fdist_args; nseg, seg_off and
+ * It is embedded as the field `src` of fm_fport_args, fm_fdist_args and fm_fcmp_args; nseg, seg_off and
  * max_seg_len are the embedding struct's.  Exactly one predictor source: FP64 columns (cols,
  * col_stride) or the split planes (hi_plane, lo_plane, plane_stride); both or neither: FM_EINVAL.
  * For sort j (K = sel_k[j] in 1..FM_MAX_SORT_K predictors, panel columns sel_cols[j][0..K) in
@@ -579,6 +582,75 @@ typedef struct fm_fdist_args {
 } fm_fdist_args;
 
 int fm_forecast_dist(const fm_fdist_args* args, void* stream);
+
+/* fm_forecast_compare: per month and per pair (a, b) of expected-return forecasts, how much of
+ * forecast b forecast a already holds, and whether the rest predicts returns: the cross-sectional
+ * regression of F_b on F_a and of the realised return on its residual, npair pairs in one launch,
+ * grid (month, pair) (build-defined extension A15; no reference line; paper Table 4, "model
+ * comparison").  Rows sorted by (month, permno), months seg_off[nseg+1] of at most 16,384 rows
+ * (its siblings' limit and their three workgroup shapes; longer: FM_ETOOBIG before any launch,
+ * outputs untouched).  Exactly one forecast source, anything else FM_EINVAL:
+ *   forecast [nsel][nrows]: the caller's vectors, with the returns in ret [rows] (of `src` only
+ *   nsel and nrows are then read; its cols, planes and forecast_out must be NULL), or
+ *   the panel of `src` (fm_forecast_src above): forecast j is its F -- fm_forecast_dist's and
+ *   fm_forecast_portfolio_sort's, bit for bit -- and the return is panel column ret_col, read raw
+ *   (never clipped) through the same layout; ret must be NULL.  src.forecast_out, if set, receives
+ *   every row's F of the forecasts some pair names (each workgroup that computes a forecast
+ *   writes the same bytes).
+ * Pair p regresses forecast pair_b[p] on forecast pair_a[p] (indices into the nsel forecasts) over
+ * the universe pair_level[p] (0..255); src.sel_level is not read.  Per (pair p, month t), all
+ * outputs with a leading [npair] dimension:
+ *   set E: the rows with F_a and F_b finite and level >= pair_level[p] (level NULL: every row);
+ *   set R: the rows of E with a finite return;
+ *   cnt[0] = nE, cnt[1] = nR;
+ *   nE < max(min_count, 2): status = 0 and rec[0..7) NaN; otherwise status = 1 and, over E,
+ *   ma = sum(F_a) / nE, mb = sum(F_b) / nE; with da = F_a - ma and db = F_b - mb:
+ *   Saa = sum(da * da), Sbb = sum(db * db), Sab = sum(da * db);
+ *   rec[1] = the slope beta = Sab / Saa;
+ *   rec[0] = the correlation Sab / sqrt(Saa * Sbb);
+ *   rec[2] = the intercept mb - beta * ma;
+ *   the row's residual e = db - beta * da;
+ *   rec[3] = sqrt(sum(e * e) / (nE - 1)): the residual's ddof-1 standard deviation
+ *            (fm_forecast_dist's convention), from a pass of its own over e -- two identical
+ *            forecasts give beta == 1.0 and rec[3] == 0.0 exactly;
+ *   over R with the same e (nR < 2: rec[4..7) NaN): me = sum(e) / nR, mr = sum(r) / nR,
+ *   See = sum((e - me)^2), Ser = sum((e - me) * (r - mr)), Srr = sum((r - mr)^2);
+ *   rec[4] = the predictive slope Ser / See;
+ *   rec[5] = its intercept mr - rec[4] * me;
+ *   rec[6] = its R2 (Ser * Ser) / (See * Srr).
+ * Degenerate months have no special cases, IEEE arithmetic decides them: a constant F_a gives
+ * 0 / 0 = NaN for the slope, the correlation and all that follows, a zero residual a NaN
+ * predictive slope.  Every product, sum and quotient above is rounded on its own, in the order
+ * written, and each of the eleven sums runs in fm_forecast_dist's fixed order (tiles of 64 rows in
+ * row order, rows outside the set or past the month's end as +0.0, the wave butterfly, lane l
+ * adding the tile sums l, l + 64, ... from +0.0, the butterfly again).  So a month's bits depend
+ * on that month's rows alone: not on the source, the panel's layout, the grid, the other months,
+ * the other pairs or max_seg_len; two calls, or a month-sharded call, give the same bits.
+ * npair == 0 or nseg == 0 is a valid empty call.  Zero-initialize the struct (it grows at the
+ * end). */
+#define FM_MAX_PAIRS 16
+#define FM_FCMP_NREC 7
+typedef struct fm_fcmp_args {
+    fm_forecast_src src;
+    const double* forecast;      /* [nsel][nrows] forecast vectors, or NULL (the panel of src) */
+    const double* ret;           /* [rows] returns of the vector source, else NULL */
+    const uint8_t* level;        /* [rows] universe level or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int32_t ret_col;             /* panel column of the realised return (panel source) */
+    int32_t nseg;
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t min_count;           /* >= 1 */
+    int32_t npair;               /* 0 .. FM_MAX_PAIRS */
+    int32_t pad_fcmp;
+    int32_t pair_a[FM_MAX_PAIRS];     /* the regressor forecast, in [0, nsel) */
+    int32_t pair_b[FM_MAX_PAIRS];     /* the regressed forecast, in [0, nsel) */
+    int32_t pair_level[FM_MAX_PAIRS]; /* the pair's universe, 0..255 */
+    double* rec;                 /* [npair][nseg][FM_FCMP_NREC] */
+    int32_t* cnt;                /* [npair][nseg][2] */
+    uint32_t* status;            /* [npair][nseg] */
+} fm_fcmp_args;
+
+int fm_forecast_compare(const fm_fcmp_args* args, void* stream);
 
 /* fm_rank_transform: every chosen column's cross-sectional rank within its month (build-defined
  * extension A13; no reference line).  It is pandas' groupby(month)[x].rank(method, pct) and is
