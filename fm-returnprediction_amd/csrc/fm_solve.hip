@@ -619,6 +619,10 @@ __device__ __forceinline__ void infy_pair(int s, int p, InfySmem& sm, const FixC
 // floor (~N eps sigma_max), which must be cut; genuine near-dependences down to 1e-13 are
 // kept.
 constexpr double SVD_REL = 1e-13;
+// A centered sum of squares below this was summed from squares near or under the subnormal
+// range (absolute error ~2^-1075 each): the normal equations cannot be trusted, whatever the
+// pivot ratios say, and the problem is refitted from its rows with the column scaled.
+constexpr double TINY_SS = 0x1p-1000;
 
 __device__ __forceinline__ double wave_sum_dpp(double v) {
     v += xor_lanes_f64(v, 1);
@@ -693,6 +697,19 @@ __device__ void refit_pair(int s, int p, RefitSmem<NC, NT / WAVE>& sm, const Fix
     const int* zi = fx.prob_z + p * 32;
     constexpr int NW = NT / WAVE;
     for (int e = tid; e < NW * NC * (NC + 1); e += NT) (&sm.R[0][0][0])[e] = 0.0;
+    // A regressor whose centered sum of squares is below TINY_SS (its squares were subnormal in
+    // the Gram) is scaled by a power of two that brings the sum near 1, and its slope scaled
+    // back at the end: both exact.  Every other column's factor is 1.0 (x * 1.0 keeps its bits).
+    // The factors sit in sm.bv until the slopes replace them.
+    if (tid < NC) {
+        double f = 1.0;
+        if (tid >= 1 && tid <= P - 1) {
+            const int K1 = P;
+            const double sd = fx.moments[((int64_t)s * fx.nprob + p) * fx.mom_stride + 1 + K1 + (tid - 1) * K1 + (tid - 1)];
+            if (sd > 0.0 && sd < TINY_SS) f = __builtin_ldexp(1.0, -ilogb(sd) / 2);
+        }
+        sm.bv[tid] = f;
+    }
     __syncthreads();
     int zc[NC];   // panel column of z index q (q >= 1)
     static_for<0, NC>([&](auto qc) {
@@ -723,7 +740,7 @@ __device__ void refit_pair(int s, int p, RefitSmem<NC, NT / WAVE>& sm, const Fix
                         if (fx.add_back) x += fx.add_back[(int64_t)c * fx.nseg + s];
                     }
                     if (isnan(x)) valid = false;
-                    v = x;
+                    v = x * sm.bv[q];
                 }
             }
             a[q] = v;
@@ -803,6 +820,10 @@ __device__ void refit_pair(int s, int p, RefitSmem<NC, NT / WAVE>& sm, const Fix
             const double cj = wave_sum_dpp(aj * ry) / s2;
             if (li) bi += sm.Vc[j][lane] * cj;
         }
+        const double cs = li ? sm.bv[lane] : 1.0;   // this lane's column factor (read before the slopes go there)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (li) sm.bv[lane] = bi;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -814,7 +835,7 @@ __device__ void refit_pair(int s, int p, RefitSmem<NC, NT / WAVE>& sm, const Fix
         const double ssr = wave_sum_dpp(e * e) + rho * rho;
         const double tss = wave_sum_dpp((li && lane >= 1) ? ry * ry : 0.0) + rho * rho;
         const int64_t ro = ((int64_t)s * fx.nprob + p) * (fx.pmax + 2);
-        if (li) fx.rec[ro + lane] = bi;
+        if (li) fx.rec[ro + lane] = bi * cs;
         if (lane == 0) {
             fx.rec[ro + fx.pmax] = 1.0 - ssr / tss;
             const uint32_t st = fx.status[(int64_t)s * fx.nprob + p];
@@ -863,13 +884,18 @@ __device__ __forceinline__ void fix_one(int s, int p, uint32_t st, FixSmem<NC, N
 // factorizations run in the time of one.  Rank-deficient problems (rare) take the Jacobi
 // pseudo-inverse path one at a time.
 
-// 1 / sqrt(x) for a positive normal x: v_rsq_f64 refined by two Newton steps
+// 1 / sqrt(x) for a positive x: v_rsq_f64 refined by two Newton steps.  As the compiler's own
+// sqrt lowering does, an x below 2^-767 is scaled by 2^768 first and the result by 2^384 (both
+// exact), so the estimate and the steps' 0.5 * x never work on a subnormal.  v_ldexp_f64 by 0
+// changes nothing, so every x >= 2^-767 keeps its bits.
 __device__ __forceinline__ double rsq_nr(double x) {
-    double y = __builtin_amdgcn_rsq(x);
-    const double h = 0.5 * x;
+    const int e = x < 0x1p-767 ? 768 : 0;
+    const double xs = __builtin_ldexp(x, e);
+    double y = __builtin_amdgcn_rsq(xs);
+    const double h = 0.5 * xs;
     y = y * fma(-h * y, y, 1.5);
     y = y * fma(-h * y, y, 1.5);
-    return y;
+    return __builtin_ldexp(y, e >> 1);
 }
 
 template <int L>
@@ -886,6 +912,191 @@ __device__ __forceinline__ double rowbc(double v) {
 __device__ __forceinline__ double rowsum(double v) { return row16_sum(v); }
 
 constexpr int G16 = 16;   // lanes per problem
+constexpr int Z16 = G16 * (G16 + 1) / 2;   // packed z-space Gram of the 16-wide solve
+constexpr int TT = G16 * (G16 + 1);        // one transpose tile (row stride 17)
+
+// Packed z-space offsets of row i of a problem's Gram: entry (z_i, z_j), j = 0..NJ-1, of the
+// 16 lanes of the problem's row (they depend on the problem's z map only)
+template <int NJ>
+__device__ __forceinline__ void gram_offsets(int zi, int (&off)[NJ]) {
+    static_for<0, NJ>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const int zj = rowbc_i<j>(zi);
+        const int r = zi < zj ? zi : zj, c = zi < zj ? zj : zi;
+        off[j] = r * G16 - (r * (r - 1)) / 2 + (c - r);
+    });
+}
+
+// The month's level-cumulative bucket sums and the patterns' model sets (LDS)
+struct Buckets16 {
+    const double* bs;
+    const uint32_t* pat;
+    int npat, nl;
+};
+
+// Row i (its first NJ columns) of the Gram of problem (model m, level u): one level-cumulative
+// bucket per pattern with m, from 0.0 in ascending pattern order.  A pattern's NJ LDS reads are
+// issued together and waited for once (left to the compiler, each read was followed by its own
+// wait: NJ round trips per pattern on the wave's chain).
+template <int NJ>
+__device__ __forceinline__ void gram_row(const Buckets16& B, int m, int u, int zi, double (&G)[NJ]) {
+    int off[NJ];
+    gram_offsets<NJ>(zi, off);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) G[j] = 0.0;
+    for (int q = 0; q < B.npat; ++q) {
+        if (!((B.pat[q] >> m) & 1u)) continue;   // per problem
+        const double* bq = B.bs + (q * B.nl + u) * Z16;
+        double v[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) v[j] = bq[off[j]];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) G[j] += v[j];   // columns past the problem's: unused
+    }
+}
+
+// One wave slot's problem (a 16-lane row of the wave) and what its factorization leaves
+struct Slot16 {
+    int s, pp, m, u, K, zi;   // month, problem, its model and level, regressors, z index of this lane's row
+    bool live;
+    int flags;
+};
+struct Fact16 {
+    double n, mu, sii, sxy, t;   // t: lane i's slope of x_{i-1} where ok
+    bool act0, ok, illc;
+    uint32_t st;
+};
+
+// Gram rows -> centered moments -> augmented Cholesky -> back substitution of a wave's four
+// problems, for waves whose largest K is at most KW: every loop runs to the constant, so the
+// body is straight-line code.  Columns and pivots past a problem's own K are computed and
+// never read (as for a K = 7 problem beside three K = 14 ones), so a wave may take any bound
+// >= its largest K.
+template <int KW>
+__device__ __forceinline__ Fact16 factor16(const fm_solve_args& a, const Slot16& q, const Buckets16& B, double* T,
+                                           uint32_t* t_st) {
+    static_assert(KW >= 1 && KW <= G16 - 2, "factor16: 1..14 regressors");
+    const int lane = lane_id(), g = lane >> 4, i = lane & 15;
+    const int K = q.K, K1 = K + 1;
+    double G[KW + 2];   // row i of the problem Gram
+    gram_row<KW + 2>(B, q.m, q.u, q.zi, G);
+    const double n = rowbc<0>(G[0]);
+    const double ninv = 1.0 / n;   // one division per lane (centering below multiplies)
+    // centered moments: lane i (1 <= i <= K1) holds S row r = i - 1, S[r][c] in row[c]
+    const bool srow = i >= 1 && i <= K1;
+    double row[KW + 1];
+    double sii = 0.0, sxy = 0.0, gdiag = 0.0;
+    static_for<0, KW + 2>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        gdiag = i == j ? G[j] : gdiag;   // selects, not conditional stores (see below)
+    });
+    static_for<0, KW + 1>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const double g0j = rowbc<0>(G[j + 1]);   // G[0][j+1]
+        const double c = G[j + 1] - G[0] * g0j * ninv;
+        const double v = (srow & (j < K1)) ? c : 0.0;
+        row[j] = v;
+        // conditional assignments to these per-lane scalars were merged by the
+        // compiler into a store through a selected address, which kept them in
+        // scratch memory; plain selects keep them in registers
+        sii = i == j + 1 ? v : sii;
+        sxy = j == K ? v : sxy;
+    });
+    FM_PROBE_AT(solve, 4);
+    const double mu = G[0] * ninv;   // lane i: mean of its variable
+    const uint64_t gm = 0xFFFFull << (16 * g);
+    uint32_t st = 0;
+    if ((__ballot(i >= 1 && i <= K && isinf(gdiag)) & gm) != 0) st |= FM_ST_INF_IN_X;
+    if ((__ballot(i == K1 && isinf(gdiag)) & gm) != 0) st |= FM_ST_INF_IN_Y;
+    const int rs = a.pmax + 2;
+    const int64_t ro = ((int64_t)q.s * a.nprob + q.pp) * rs;
+    const bool skip = !(n >= (double)(K + 1));
+    if (q.live && skip) {
+        for (int k = i; k < rs; k += G16) a.rec[ro + k] = k == a.pmax + 1 ? n : NAN;
+        if (i == 0) a.status[(int64_t)q.s * a.nprob + q.pp] = t_st[q.pp] = FM_ST_SKIPPED;
+    }
+    const bool act0 = q.live && !skip;
+    if (act0 && a.moments) {
+        double* mo = a.moments + ((int64_t)q.s * a.nprob + q.pp) * a.mom_stride;
+        if (i == 0) mo[0] = n;
+        if (srow) {
+            mo[i] = mu;   // mo[1 + r]
+            // S is exactly symmetric (S[r][c] and S[c][r] are the same products of the
+            // same packed sums), so lane r stores column r of S: S[c][r] for every c, and
+            // each store instruction writes K1 consecutive doubles (a row-per-lane store
+            // strides K1 doubles between lanes)
+#pragma unroll
+            for (int c = 0; c < KW + 1; ++c)
+                if (c < K1) mo[1 + K1 + c * K1 + (i - 1)] = row[c];
+        }
+    }
+    if (act0 && (q.flags & 1) != 0) {
+        if ((__ballot(i >= 1 && i <= K && !(sii > 1e-10 * gdiag)) & gm) != 0) st |= FM_ST_CONST_SUSPECT;
+    }
+    FM_PROBE_AT(solve, 5);
+    // ---- augmented Cholesky of S (pivot r = k sits in lane k + 1)
+    bool ok = act0;
+    // a regressor whose sum of squares lost its bits to the subnormal range: refit from the rows
+    int illc = (act0 && (__ballot(i >= 1 && i <= K && sii > 0.0 && sii < TINY_SS) & gm) != 0) ? 1 : 0;
+    const int tr = i >= 1 ? i - 1 : G16 - 1;   // this lane's tile row (lane 0: the spare last row)
+    double dinv = 0.0;   // lane k + 1: 1 / L[k][k] (the back substitution multiplies by it)
+    static_for<0, KW>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        const bool act = ok & (k < K);
+        const double orig = rowbc<k + 1>(sii);
+        const double piv = rowbc<k + 1>(row[k]);
+        illc |= (act & !(piv > REFIT_REL * orig)) ? 1 : 0;
+        // pinned here: left to the end of the factorization (its only use), the test would
+        // keep every step's pivot and diagonal live
+        asm volatile("" : "+v"(illc));
+        const bool bad = act & (!(orig > 0.0) | !(piv > CHOL_REL * orig));
+        ok = ok & !bad;
+        const bool go = act & !bad;
+        // 1 / sqrt(piv) by the hardware estimate and two Newton steps (error ~1 ulp), sqrt
+        // as piv times it: no IEEE sqrt and division sequences on the pivot chain
+        const double rinv = rsq_nr(piv);
+        const double lkk = piv * rinv;
+        const double lik = row[k] * rinv;
+        // unguarded: the entries a guard would keep are never read again -- columns past
+        // the problem's K (and, once k >= K, everything this step touches) are not used by
+        // the back substitution, and a problem whose pivot failed is refactored from G by
+        // the Jacobi path -- so the two selects per entry are not needed
+        static_for<k + 1, KW + 1>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            const double sj = rowbc<k + 1>(row[j]) * rinv;   // L[j][k] = S(k)[k][j] / lkk
+            row[j] = row[j] - lik * sj;
+        });
+        row[k] = go ? (i == k + 1 ? lkk : lik) : row[k];
+        dinv = i == k + 1 ? rinv : dinv;
+        // column k of the factor is final: to its transpose tile now (frees its registers);
+        // unguarded, lanes outside the problem's rows write tile rows that are never read
+        T[tr * (G16 + 1) + k] = row[k];
+    });
+    FM_PROBE_AT(solve, 6);
+    // ---- back substitution L' b = l on the transposed factor: lane i then holds
+    // column r = i - 1 of L (col[c] = L[c][r]) and t = l_r
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    double col[KW];
+    const int rr = i >= 1 ? i - 1 : 0;
+#pragma unroll
+    for (int c = 0; c < KW; ++c) col[c] = T[c * (G16 + 1) + rr];
+    double t = (i >= 1 && i <= K) ? T[K * (G16 + 1) + rr] : 0.0;
+    static_for<0, KW>([&](auto jc) {
+        constexpr int j = KW - 1 - decltype(jc)::value;   // descending
+        const double bj = rowbc<j + 1>(t) * rowbc<j + 1>(dinv);   // t_j / L[j][j]
+        const double tm = t - col[j] * bj;
+        const double tn = i == j + 1 ? bj : (((i >= 1) & (i - 1 < j)) ? tm : t);
+        t = (ok & (j < K)) ? tn : t;
+    });
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    FM_PROBE_AT(solve, 7);
+    return Fact16{n, mu, sii, sxy, t, act0, ok, illc != 0, st};
+}
 
 // 192 threads (three waves, twelve problems at a time: a Table-2 month's 11 problems in ONE
 // round, so no wave factors twice) at two waves per SIMD: 256 VGPRs (the factorization's
@@ -898,14 +1109,13 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
     extern __shared__ double bs[];   // [nb][136] packed bucket sums of this month
     // per wave: four transpose tiles, or (afterwards, one problem at a time) the Jacobi
     // fallback's scratch (a union)
-    constexpr int TT = G16 * (G16 + 1);
     static_assert(sizeof(WaveScratch<16>) <= 4 * TT * sizeof(double), "scratch union");
     __shared__ double wsc[S16W][4 * TT];
     static_assert(sizeof(FixSmem<G16, S16T>) <= sizeof(wsc), "solve16's inline fix-ups reuse its per-wave scratch");
     const int s = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
-    constexpr int zw = 16, zz = 136;
+    constexpr int zz = Z16;
     const int nl = a.nlevels, npat = a.npatterns, nb = npat * nl;
     // The small per-problem tables and this month's add-back values go to LDS first, all
     // loads issued together with the partials' (read in place, each would be a dependent
@@ -924,8 +1134,8 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
         t_nz[tid] = nzp;
         t_flags[tid] = a.prob_flags[tid];
         // Problems go to wave slots by descending K (ties: index order): the factorization
-        // loops run to the largest K of the wave's four problems, so grouping similar K
-        // cuts the issued work (Table 2: 3 x K 14, 3 x 7, 2 x 5, 3 x 3 per month)
+        // loops run to a bound on the largest K of the wave's four problems, so grouping
+        // similar K cuts the issued work (Table 2: 3 x K 14, 3 x 7, 2 x 5, 3 x 3 per month)
         int rank = 0;
         for (int q = 0; q < a.nprob; ++q) {
             const int nzq = a.prob_nz[q];
@@ -953,167 +1163,41 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
         }
     }
     __syncthreads();
-    FM_PROBE_AT(solve, 2);
+    const Buckets16 B{bs, t_pat, npat, nl};
     const int g = lane >> 4, i = lane & 15;
     const int rs = a.pmax + 2;
     double* T = wsc[w] + g * TT;
+    FM_PROBE_AT(solve, 2);
     for (int p0 = w * 4; p0 < a.nprob; p0 += S16W * 4) {
         const int p = p0 + g;
         const bool live = p < a.nprob;
         const int pp = t_slot[live ? p : p0];
         const int m = t_model[pp], u = t_level[pp], nz = t_nz[pp];
-        const int K = nz - 2, K1 = K + 1;
-        // wave-uniform loop bound: the largest K of this wave's problems (slots by
-        // descending K: the first live slot's)
-        const int kw = __builtin_amdgcn_readfirstlane(K);
+        const int K = nz - 2;
         const int zi = i < nz ? t_z[pp][i] : 0;   // z index of this lane's row
-        // ---- row i of the problem Gram: one level-cumulative bucket per pattern with m.
-        // A lambda, so the rare rank-deficient path re-reads G from LDS instead of keeping it
-        // (and the offsets) live through the factorization: 48 VGPRs, no spills at 3 waves/SIMD
-        auto gram_row = [&](double (&G)[G16]) {
-            int off[G16];
-            static_for<0, G16>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                const int zj = rowbc_i<j>(zi);
-                const int r = zi < zj ? zi : zj, c = zi < zj ? zj : zi;
-                off[j] = r * zw - (r * (r - 1)) / 2 + (c - r);
-            });
-#pragma unroll
-            for (int j = 0; j < G16; ++j) G[j] = 0.0;
-            for (int q = 0; q < npat; ++q) {
-                if (!((t_pat[q] >> m) & 1u)) continue;   // per problem
-                const double* bq = bs + (q * nl + u) * zz;
-#pragma unroll
-                for (int j = 0; j < G16; ++j)
-                    if (j < kw + 2) G[j] += bq[off[j]];   // columns past the wave's K: unused
-            }
-        };
-        double G[G16];
-        gram_row(G);
-        const double n = rowbc<0>(G[0]);
-        const double ninv = 1.0 / n;   // one division per lane (centering below multiplies)
-        // centered moments: lane i (1 <= i <= K1) holds S row r = i - 1, S[r][c] in row[c]
-        const bool srow = i >= 1 && i <= K1;
-        double row[G16];
-        double sii = 0.0, sxy = 0.0, gdiag = 0.0;
-        static_for<0, G16>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            gdiag = i == j ? G[j] : gdiag;   // selects, not conditional stores (see below)
-            if constexpr (j + 1 < G16) {
-                if (j > kw) {   // wave-uniform: past every problem's last column
-                    row[j] = 0.0;
-                    return;
-                }
-                const double g0j = rowbc<0>(G[j + 1]);   // G[0][j+1]
-                const double v = srow && j < K1 ? G[j + 1] - G[0] * g0j * ninv : 0.0;
-                row[j] = v;
-                // conditional assignments to these per-lane scalars were merged by the
-                // compiler into a store through a selected address, which kept them in
-                // scratch memory; plain selects keep them in registers
-                sii = i == j + 1 ? v : sii;
-                sxy = j == K ? v : sxy;
-            } else {
-                row[j] = 0.0;
-            }
-        });
-        FM_PROBE_AT(solve, 4);
-        const double mu = G[0] * ninv;   // lane i: mean of its variable
-        const uint64_t gm = 0xFFFFull << (16 * g);
-        uint32_t st = 0;
-        if ((__ballot(i >= 1 && i <= K && isinf(gdiag)) & gm) != 0) st |= FM_ST_INF_IN_X;
-        if ((__ballot(i == K1 && isinf(gdiag)) & gm) != 0) st |= FM_ST_INF_IN_Y;
+        const Slot16 sl{s, pp, m, u, K, zi, live, t_flags[pp]};
+        // One instantiation per column bound, chosen once per wave on the largest K of its
+        // problems (slots by descending K: the first live slot's): the Table-2 values
+        const int kw = __builtin_amdgcn_readfirstlane(K);
+        Fact16 F;
+        if (kw <= 3) F = factor16<3>(a, sl, B, T, t_st);
+        else if (kw <= 5) F = factor16<5>(a, sl, B, T, t_st);
+        else if (kw <= 7) F = factor16<7>(a, sl, B, T, t_st);
+        else F = factor16<14>(a, sl, B, T, t_st);
+        const double n = F.n, mu = F.mu, sii = F.sii, sxy = F.sxy;
+        const bool act0 = F.act0, ok = F.ok;
+        uint32_t st = F.st;
+        const int K1 = K + 1;
         const int64_t ro = ((int64_t)s * a.nprob + pp) * rs;
-        const bool skip = !(n >= (double)(K + 1));
-        if (live && skip) {
-            for (int k = i; k < rs; k += G16) a.rec[ro + k] = k == a.pmax + 1 ? n : NAN;
-            if (i == 0) a.status[(int64_t)s * a.nprob + pp] = t_st[pp] = FM_ST_SKIPPED;
-        }
-        const bool act0 = live && !skip;
-        if (act0 && a.moments) {
-            double* mo = a.moments + ((int64_t)s * a.nprob + pp) * a.mom_stride;
-            if (i == 0) mo[0] = n;
-            if (srow) {
-                mo[i] = mu;   // mo[1 + r]
-                // S is exactly symmetric (S[r][c] and S[c][r] are the same products of the
-                // same packed sums), so lane r stores column r of S: S[c][r] for every c, and
-                // each store instruction writes K1 consecutive doubles (a row-per-lane store
-                // strides K1 doubles between lanes)
-#pragma unroll
-                for (int c = 0; c < G16 - 1; ++c)
-                    if (c < K1) mo[1 + K1 + c * K1 + (i - 1)] = row[c];
-            }
-        }
-        if (act0 && (t_flags[pp] & 1) != 0) {
-            if ((__ballot(i >= 1 && i <= K && !(sii > 1e-10 * gdiag)) & gm) != 0) st |= FM_ST_CONST_SUSPECT;
-        }
-        FM_PROBE_AT(solve, 5);
-        // ---- augmented Cholesky of S (pivot r = k sits in lane k + 1)
-        bool ok = act0, illc = false;
-        double dinv = 0.0;   // lane k + 1: 1 / L[k][k] (the back substitution multiplies by it)
-        static_for<0, G16 - 1>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            if (k >= kw) return;   // wave-uniform: no problem of the wave has pivot k
-            const bool act = ok && k < K;
-            const double orig = rowbc<k + 1>(sii);
-            const double piv = rowbc<k + 1>(row[k]);
-            if (act && !(piv > REFIT_REL * orig)) illc = true;
-            const bool bad = act && (!(orig > 0.0) || !(piv > CHOL_REL * orig));
-            if (bad) ok = false;
-            const bool go = act && !bad;
-            // 1 / sqrt(piv) by the hardware estimate and two Newton steps (error ~1 ulp), sqrt
-            // as piv times it: no IEEE sqrt and division sequences on the pivot chain
-            const double rinv = rsq_nr(piv);
-            const double lkk = piv * rinv;
-            const double lik = row[k] * rinv;
-            // unguarded: the entries a guard would keep are never read again -- columns past
-            // the problem's K (and, once k >= K, everything this step touches) are not used by
-            // the back substitution, and a problem whose pivot failed is refactored from G by
-            // the Jacobi path below -- so the two selects per entry are not needed
-            static_for<k + 1, G16>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                if (j > kw) return;   // wave-uniform
-                const double sj = rowbc<k + 1>(row[j]) * rinv;   // L[j][k] = S(k)[k][j] / lkk
-                row[j] = row[j] - lik * sj;
-            });
-            row[k] = go ? (i == k + 1 ? lkk : lik) : row[k];
-            dinv = i == k + 1 ? rinv : dinv;
-        });
-        FM_PROBE_AT(solve, 6);
         // lanes of a live, unskipped problem with a collapsed pivot: rank deficient
         const bool rank_def = act0 && !ok;
-        // ---- back substitution L' b = l on the transposed factor: lane i then holds
-        // column r = i - 1 of L (col[c] = L[c][r]) and t = l_r
-        if (srow) {
-#pragma unroll
-            for (int c = 0; c < G16; ++c) T[(i - 1) * (G16 + 1) + c] = row[c];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        double col[G16];
-        const int rr = i >= 1 ? i - 1 : 0;
-#pragma unroll
-        for (int c = 0; c < G16 - 1; ++c) col[c] = T[c * (G16 + 1) + rr];
-        col[G16 - 1] = 0.0;
-        double t = (i >= 1 && i <= K) ? T[K * (G16 + 1) + rr] : 0.0;
-        static_for<0, G16 - 1>([&](auto jc) {
-            constexpr int j = 14 - decltype(jc)::value;   // descending
-            if (j >= kw) return;   // wave-uniform
-            const double bj = rowbc<j + 1>(t) * rowbc<j + 1>(dinv);   // t_j / L[j][j]
-            if (ok && j < K) {
-                if (i == j + 1) t = bj;
-                else if (i >= 1 && i - 1 < j) t -= col[j] * bj;
-            }
-        });
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        FM_PROBE_AT(solve, 7);
-        double bi = (ok && i >= 1 && i <= K) ? t : 0.0;   // slope of x_{i-1}
-        // ---- rank-deficient problems of this wave: Jacobi pseudo-inverse, one at a time
+        double bi = (ok && i >= 1 && i <= K) ? F.t : 0.0;   // slope of x_{i-1}
+        // ---- rank-deficient problems of this wave: Jacobi pseudo-inverse, one at a time.
+        // G is read again from the buckets instead of kept (and its offsets) live through the
+        // factorization
         const uint64_t rd = __ballot(rank_def && i == 0);
         double G2[G16];
-        if (rd) gram_row(G2);   // wave-uniform
+        if (rd) gram_row<G16>(B, m, u, zi, G2);   // wave-uniform
         for (uint64_t q = rd; q; q &= q - 1) {
             const int gq = __builtin_ctzll(q) >> 4;   // wave-uniform
             WaveScratch<16>& J = *reinterpret_cast<WaveScratch<16>*>(wsc[w]);
@@ -1141,7 +1225,7 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
             wave_sync();
         }
         if (rank_def) st |= FM_ST_RANK_DEF;
-        if (illc) st |= FM_ST_REFIT;
+        if (F.illc) st |= FM_ST_REFIT;
         // ---- R^2 = 1 - SSR/SST (centered), raw-coordinate intercept
         const bool xl = i >= 1 && i <= K;
         double t_sxy = xl ? bi * sxy : 0.0;
