@@ -265,7 +265,14 @@ __global__ __launch_bounds__(ST) void select_fixup_kernel(SelArgs a, double* zs,
     fixup_body<VPT>(a, zs, zs_len, blockIdx.x, gridDim.x, sm);
 }
 
-template <int VPT>
+// universe_month's high-word breakpoint path (hk_select): histogram bins and list capacity
+#ifndef FM_UNI_HB
+#define FM_UNI_HB 1024
+#endif
+#ifndef FM_UNI_CAP
+#define FM_UNI_CAP 128
+#endif
+template <int VPT, int HBN = FM_UNI_HB, int CAP = FM_UNI_CAP>
 __device__ __forceinline__ void universe_month(const double* __restrict__ me, const uint8_t* __restrict__ nyse,
                                                const int64_t* __restrict__ seg_off, double qa, double qb,
                                                double* __restrict__ cut_a, double* __restrict__ cut_b,
@@ -1727,23 +1734,27 @@ void launch_select_wave(const SelArgs& a, hipStream_t st) {
 
 // get_subsets' NYSE breakpoints AND the nested universe levels in one launch (reference
 // src/calc_Lewellen_2014.py:69-105): one 256-thread workgroup per month holds the month's
-// `me` in registers (VPT per thread, one coalesced read, the NYSE flags as a bit mask),
-// finds the pandas groupby.quantile(q_a, q_b) order statistics of the NYSE rows (NaN me
-// skipped) by the adaptive histogram select, lerps them the pandas way, and writes every
-// row's level (me >= me_20) + (me >= me_50) from the same registers (NaN compares False).
-template <int VPT>
+// `me` in registers (VPT per thread, one coalesced read) next to the high words of the NYSE
+// rows' order keys (HK_ABSENT for every row that does not count: past the month, non-NYSE,
+// NaN me), finds the pandas groupby.quantile(q_a, q_b) order statistics of the NYSE rows on
+// those 32-bit keys (hk_select: count / min / max, the histogram and the candidate tests
+// are one 32-bit compare per value; only the few candidates become 64-bit keys), lerps them
+// the pandas way, and writes every row's level (me >= me_20) + (me >= me_50) from the FP64
+// registers (NaN compares False).  A month whose located bin overflows its list (a crowd,
+// ties, values that differ in the low word only) runs the 64-bit hist_select from scratch:
+// block-uniform, rare, the same exact order statistics either way.
+template <int VPT, int HBN, int CAP>
 __device__ __forceinline__ void universe_month(const double* __restrict__ me, const uint8_t* __restrict__ nyse,
                                                const int64_t* __restrict__ seg_off, double qa, double qb,
                                                double* __restrict__ cut_a, double* __restrict__ cut_b,
                                                uint8_t* __restrict__ level, int s, SelSmem& sm) {
-    static_assert(VPT <= 64, "universe_kernel: NYSE flags are one 64-bit mask per thread");
     FM_PROBE_AT(sel, 0);
     const int tid = threadIdx.x;
     const int64_t r0 = seg_off[s];
     const int L = (int)(seg_off[s + 1] - r0);
     const int last = L > 0 ? L - 1 : 0;
     double xm[VPT];
-    uint64_t nb = 0;
+    uint32_t hk[VPT];
 #pragma unroll
     for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
         const int idx = tid + v * ST;
@@ -1751,49 +1762,42 @@ __device__ __forceinline__ void universe_month(const double* __restrict__ me, co
         const double x = me[r0 + ci];
         const uint8_t m = nyse[r0 + ci];
         xm[v] = idx < L ? x : NAN;
-        if (idx < L && m != 0 && !isnan(x)) nb |= 1ull << v;
+        hk[v] = idx < L && m != 0 && !isnan(x) ? dkey_hi(x) : HK_ABSENT;
     }
-    // each pass re-forms the masked value (opaque to the optimizer): kept across the
-    // histogram passes, the per-value NaN tests become 2 x VPT SGPRs spilled to VGPR lanes
-    auto for_each = [&](auto&& f) {
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            double x = ((nb >> v) & 1ull) ? xm[v] : NAN;
-            asm volatile("" : "+v"(x));
-            f(x);
-        }
-    };
+    // hk_select's histogram, zeroed while the loads are in flight
+    for (int i = tid; i < HBN; i += ST) sm.hist[i] = 0u;
     int cnt = 0;
-    uint64_t kmn = SENT, kmx = 0;
-    for_each([&](double x) {
-        if (!isnan(x)) {
-            ++cnt;
-            const uint64_t k = dkey(x);
-            kmn = k < kmn ? k : kmn;
-            kmx = k > kmx ? k : kmx;
-        }
-    });
+    uint32_t hmn = HK_ABSENT, hmx1 = 0u;   // hmx1: the largest valid key + 1 (HK_ABSENT + 1 wraps to 0)
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        cnt += hk[v] != HK_ABSENT ? 1 : 0;
+        hmn = min(hmn, hk[v]);
+        hmx1 = max(hmx1, hk[v] + 1u);
+    }
     // count, min and max in one exchange (one barrier; nothing of sm is in use yet)
     {
         const int c = wave_sum(cnt);
-        const uint64_t mn = wave_min_u64(kmn), mx = wave_max_u64(kmx);
+        const uint32_t mn = wave_reduce(hmn, [](uint32_t p, uint32_t q) { return min(p, q); });
+        const uint32_t mx = wave_reduce(hmx1, [](uint32_t p, uint32_t q) { return max(p, q); });
         const int w = tid / WAVE;
         if ((tid & (WAVE - 1)) == 0) {
             sm.ints[w] = c;
-            sm.u64s[w] = mn;
-            sm.u64s[SNW + w] = mx;
+            sm.u64s[w] = ((uint64_t)mx << 32) | mn;
         }
     }
     __syncthreads();
     int n = sm.ints[0];
-    kmn = sm.u64s[0];
-    kmx = sm.u64s[SNW];
+    hmn = (uint32_t)sm.u64s[0];
+    hmx1 = (uint32_t)(sm.u64s[0] >> 32);
 #pragma unroll
     for (int q = 1; q < SNW; ++q) {
         n += sm.ints[q];
-        kmn = sm.u64s[q] < kmn ? sm.u64s[q] : kmn;
-        kmx = sm.u64s[SNW + q] > kmx ? sm.u64s[SNW + q] : kmx;
+        hmn = min(hmn, (uint32_t)sm.u64s[q]);
+        hmx1 = max(hmx1, (uint32_t)(sm.u64s[q] >> 32));
     }
+    n = __builtin_amdgcn_readfirstlane(n);
+    hmn = (uint32_t)__builtin_amdgcn_readfirstlane((int)hmn);
+    hmx1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)hmx1);
     double a = NAN, b = NAN;
     FM_PROBE_AT(sel, 1);
     if (n > 0) {   // block-uniform
@@ -1801,8 +1805,32 @@ __device__ __forceinline__ void universe_month(const double* __restrict__ me, co
         double g0, g1;
         qranks(n, qa, 1, rk[0], rk[1], g0);
         qranks(n, qb, 1, rk[2], rk[3], g1);
-        uint64_t ko[4] = {kmn, kmn, kmx, kmx};
-        hist_select(for_each, 4, rk, kmn, kmx, ko, sm);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) rk[t] = __builtin_amdgcn_readfirstlane(rk[t]);
+        uint64_t ko[4];
+        if (!hk_select<SNW, HBN, CAP>(hk, xm, rk, hmn, hmx1 - 1u, ko, sm)) {   // block-uniform
+            // each pass re-forms the masked value (opaque to the optimizer): kept across the
+            // histogram passes, the per-value NaN tests become 2 x VPT SGPRs spilled to VGPR lanes
+            auto for_each = [&](auto&& f) {
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    double x = hk[v] != HK_ABSENT ? xm[v] : NAN;
+                    asm volatile("" : "+v"(x));
+                    f(x);
+                }
+            };
+            uint64_t kmn = SENT, kmx = 0;
+            for_each([&](double x) {
+                if (!isnan(x)) {
+                    const uint64_t k = dkey(x);
+                    kmn = k < kmn ? k : kmn;
+                    kmx = k > kmx ? k : kmx;
+                }
+            });
+            kmn = block_min_u64<SNW>(kmn, sm.u64s);
+            kmx = block_max_u64<SNW>(kmx, sm.u64s + SNW);
+            hist_select(for_each, 4, rk, kmn, kmx, ko, sm);
+        }
         a = qlerp(kval(ko[0]), kval(ko[1]), g0, 1);
         b = qlerp(kval(ko[2]), kval(ko[3]), g1, 1);
     }

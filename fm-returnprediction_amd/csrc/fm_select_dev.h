@@ -648,6 +648,142 @@ __device__ __forceinline__ void hist_select(ForEach&& for_each, int nr, const in
     hist_select_t<NW, HB, HCAP>(for_each, nr, rk, kmin, kmax, out, sm);
 }
 
+// ---------------------------------------------------------------------------------------
+// hk_select: hist_select's first level on the keys' HIGH words (the NYSE breakpoints of
+// universe_month).  hk[v] = (uint32_t)(dkey(xv[v]) >> 32) for the values that count and
+// HK_ABSENT for the rest (absent, NaN, masked out).  The high word is a monotone coarsening
+// of the 64-bit key over every non-NaN double and no valid key has high word 0xFFFFFFFF
+// (+inf's is 0xFFF00000), so one unsigned compare (hk - lo) <= span is the validity test and
+// both bound compares at once.  A bin of high words is a contiguous range of 64-bit keys:
+// the rank bookkeeping is hist_select's.
+//   histogram: bin = (hk - hmin) >> shift over <= HBN bins, one LDS pass, one block scan;
+//   lists:     the values of each located bin (one compare per value and distinct bin; a
+//              wave without a hit skips the append) go to LDS as full 64-bit keys and one
+//              wave sorts each list.
+// Returns false (block-uniform, `out` untouched) when a located bin holds more than CAP keys
+// (a crowd, ties, keys that differ in the low word only): the caller then runs the 64-bit
+// hist_select from scratch.  The caller has zeroed sm.hist[0 .. HBN) and passed a barrier;
+// rk[0 .. 4) are ranks among the n >= 1 valid values, hmin / hmax their extreme high words.
+constexpr uint32_t HK_ABSENT = 0xFFFFFFFFu;
+__device__ __forceinline__ uint32_t dkey_hi(double x) {
+    const uint32_t h = (uint32_t)((uint64_t)__double_as_longlong(x) >> 32);
+    return (h >> 31) ? ~h : (h | 0x80000000u);
+}
+
+template <int NW, int HBN, int CAP, int VPT, typename Sm>
+__device__ __forceinline__ bool hk_select(const uint32_t (&hk)[VPT], const double (&xv)[VPT], const int* rk,
+                                          uint32_t hmin, uint32_t hmax, uint64_t* out, Sm& sm) {
+    constexpr int NT = NW * WAVE;
+    constexpr int BPT = HBN / NT;
+    constexpr int LB = HBN == 2048 ? 11 : HBN == 1024 ? 10 : HBN == 512 ? 9 : 8;
+    static_assert((1 << LB) == HBN && HBN <= HB && BPT >= 1, "hk_select: HBN is a power of two, NT .. HB");
+    static_assert(CAP == WAVE || CAP == 2 * WAVE || CAP == 4 * WAVE, "hk_select: CAP is 64, 128 or 256");
+    static_assert(4 * CAP <= CAND_CAP, "hk_select: four lists in sm.buf");
+    const int tid = threadIdx.x, lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const uint32_t span = hmax - hmin;
+    const int shift = span < (uint32_t)HBN ? 0 : 32 - __clz(span) - LB;   // span >> shift < HBN
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const uint32_t d = hk[v] - hmin;
+        if (d <= span) atomicAdd(&sm.hist[d >> shift], 1u);
+    }
+    __syncthreads();
+    FM_HS_PROBE(4);
+    // block scan: thread tid owns bins [BPT tid, BPT tid + BPT)
+    uint32_t h[BPT];
+    int loc = 0;
+#pragma unroll
+    for (int j = 0; j < BPT; ++j) {
+        h[j] = sm.hist[BPT * tid + j];
+        loc += (int)h[j];
+    }
+    const int incl = wave_incl_scan(loc);
+    if (lane == WAVE - 1) sm.ints[w] = incl;
+    if (tid < 4) sm.hcnt[tid] = 0u;
+    __syncthreads();
+    int run = incl - loc;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) run += i < w ? sm.ints[i] : 0;
+#pragma unroll
+    for (int j = 0; j < BPT; ++j) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (run <= rk[t] && rk[t] < run + (int)h[j]) {
+                sm.hs[3 * t] = BPT * tid + j;
+                sm.hs[3 * t + 1] = run;
+                sm.hs[3 * t + 2] = (int)h[j];
+            }
+        run += (int)h[j];
+    }
+    __syncthreads();
+    FM_HS_PROBE(5);
+    int bin[4], lrank[4], lst[4];
+    bool over = false;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        bin[t] = __builtin_amdgcn_readfirstlane(sm.hs[3 * t]);
+        lrank[t] = rk[t] - __builtin_amdgcn_readfirstlane(sm.hs[3 * t + 1]);
+        over = over || __builtin_amdgcn_readfirstlane(sm.hs[3 * t + 2]) > CAP;
+    }
+    if (over) return false;   // block-uniform
+    // one list per distinct bin (the two ranks of a breakpoint usually share one)
+    int nl = 0;
+    uint32_t ulo[4] = {0u, 0u, 0u, 0u}, uw[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        int u = -1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q < t && bin[q] == bin[t]) u = lst[q];
+        lst[t] = u >= 0 ? u : nl++;
+        const uint32_t lo = hmin + ((uint32_t)bin[t] << shift);   // <= hmax: the bin holds a key
+        const uint32_t wd = shift == 0 ? 0u : (1u << shift) - 1u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q == lst[t]) ulo[q] = lo, uw[q] = hmax - lo < wd ? hmax - lo : wd;
+    }
+    // per value one compare per list and ONE wave-uniform branch (nearly every slot misses)
+    auto append = [&](auto nlc) {
+        constexpr int NL = decltype(nlc)::value;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            bool hit[NL], any = false;
+#pragma unroll
+            for (int u = 0; u < NL; ++u) {
+                hit[u] = hk[v] - ulo[u] <= uw[u];   // HK_ABSENT - lo > hmax - lo >= uw
+                any = any || hit[u];
+            }
+            if (__ballot(any) != 0ull) {
+#pragma unroll
+                for (int u = 0; u < NL; ++u)
+                    if (hit[u]) {
+                        const uint32_t pos = atomicAdd(&sm.hcnt[u], 1u);
+                        if (pos < (uint32_t)CAP) sm.buf[u * CAP + pos] = dkey(xv[v]);
+                    }
+            }
+        }
+    };
+    if (nl == 1) append(std::integral_constant<int, 1>{});   // block-uniform
+    else if (nl == 2) append(std::integral_constant<int, 2>{});
+    else if (nl == 3) append(std::integral_constant<int, 3>{});
+    else append(std::integral_constant<int, 4>{});
+    __syncthreads();
+    FM_HS_PROBE(6);
+    for (int l = w; l < nl; l += NW) {   // one wave per list
+        const int c = (int)sm.hcnt[l];
+        uint64_t* L = sm.buf + l * CAP;
+        if (CAP <= WAVE || c <= WAVE) wave_sort_lds<1>(L, c);
+        else if (CAP <= 2 * WAVE || c <= 2 * WAVE) wave_sort_lds<(CAP > WAVE ? 2 : 1)>(L, c);
+        else wave_sort_lds<(CAP > 2 * WAVE ? 4 : 1)>(L, c);
+    }
+    __syncthreads();
+    FM_HS_PROBE(7);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) out[t] = sm.buf[lst[t] * CAP + lrank[t]];
+    return true;
+}
+
 // Number of entries of the ascending list L[0..64) that precede v in the merged order:
 // entries < v, or <= v when the list's wave comes first (ties broken by wave).
 __device__ __forceinline__ int merge_count(const uint64_t* L, uint64_t v, bool inclusive) {

@@ -3,7 +3,7 @@
 #   tools/build_variant.sh <name> "<extra hipcc flags>" source.hip [source.hip ...]
 # The flags the sources still take: -DFM_PROBE=1 (tools/tail_probe.py), -DFM_GRAM_WGTIME=1
 # (tools/gram_wgtime.py) and the numeric parameters (FM_GRAM_MINW, FM_STD_T / _R / _LP,
-# FM_TS_RROWS, FM_SELECT_STREAM_VPT / _SB, FM_PAIR_HK_WGS, FM_NP_MOM_DEPTH) for
+# FM_TS_RROWS, FM_SELECT_STREAM_VPT / _SB, FM_UNI_HB / _CAP, FM_PAIR_HK_WGS, FM_NP_MOM_DEPTH) for
 # tools/kbench.py A/B runs.  The sources hold no ablation or strategy switches any more.
 # Reuses the in-tree objects and recompiles only the listed sources with the extra flags
 # into build_variants/<name>/libfm_hip.so.

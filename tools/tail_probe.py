@@ -84,6 +84,7 @@ def main():
     cfg = LW.PipelineConfig()
     for _ in range(3):
         LW.run_pipeline(panel, cfg)
+    E.universe(panel)   # the pipeline runs universe_month inside the select fix-up's launch: here on its own
     torch.cuda.synchronize()
     for tag, (buf, names) in TAGS.items():
         if tag in E.LAST_LAUNCH:
