@@ -164,6 +164,23 @@ class RankArgs(C.Structure):
     ]
 
 
+FM_MAX_HORIZON = 60
+
+
+class LinksArgs(C.Structure):
+    _fields_ = [
+        ("ids", _p), ("seg_off", _p), ("month_index", _p), ("nrows", _i64), ("nseg", _i32), ("step", _i32),
+        ("link", _p), ("bad", _p),
+    ]
+
+
+class HorizonArgs(C.Structure):
+    _fields_ = [
+        ("ret", _p), ("link", _p), ("seg_off", _p), ("nrows", _i64), ("nseg", _i32), ("horizon", _i32),
+        ("out", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -203,6 +220,8 @@ _SIGS = {
     "fm_forecast_dist": (_i32, [C.POINTER(FDistArgs), _p]),
     "fm_forecast_compare": (_i32, [C.POINTER(FCmpArgs), _p]),
     "fm_rank_transform": (_i32, [C.POINTER(RankArgs), _p]),
+    "fm_month_links": (_i32, [C.POINTER(LinksArgs), _p]),
+    "fm_horizon_return": (_i32, [C.POINTER(HorizonArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -220,7 +239,7 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs,
             "fm_port_args": PortArgs, "fm_rank_args": RankArgs, "fm_forecast_src": ForecastSrc,
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs,
-            "fm_fcmp_args": FCmpArgs}
+            "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs}
 
 _lib = None
 

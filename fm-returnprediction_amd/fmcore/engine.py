@@ -132,10 +132,20 @@ class DevicePanel:
     chunk_policy: Optional[tuple] = None    # Gram plan of the GLOBAL panel (chunk_policy()), sharded runs
     row_origin: int = 0                     # global row of this panel's row 0 (balanced plans)
     planes_version: int = -1                # cols._version when the planes were made from cols
+    ids: Optional[torch.Tensor] = None      # [n] int64: each row's firm id, month-major, ascending within a month
+    month_index: Optional[np.ndarray] = None   # [T] int32 (host): each segment's calendar month number, ascending
 
     @property
     def device(self):
         return (self.cols if self.cols is not None else self.planes).device
+
+    def month_index_device(self):
+        """``month_index`` on the device (int32 [T]), uploaded once and kept."""
+        t = self.__dict__.get("_month_index_dev")
+        if t is None:
+            t = torch.from_numpy(np.ascontiguousarray(self.month_index, dtype=np.int32)).to(self.device)
+            self.__dict__["_month_index_dev"] = t
+        return t
 
     def values(self):
         """The FP64 columns [C, n]: ``cols``, or for a planes-only panel a device merge of the
@@ -211,6 +221,40 @@ def month_segments(labels):
     return codes, uniq, order, seg_off
 
 
+def month_index(labels):
+    """The calendar month number of each segment label -> int32 [T], strictly ascending:
+    datetime64 labels map to year * 12 + month - 1, integer labels are taken as they are (a count
+    of months).  Anything else, a missing date, or two labels of one month (or labels out of
+    order) raise ValueError: the month links compare these numbers to tell neighbouring months
+    from a gap in the calendar."""
+    a = np.asarray(labels)
+    if a.dtype.kind == "M":
+        if np.isnat(a).any():
+            raise ValueError("month_index: a month label is NaT")
+        m = a.astype("datetime64[M]").astype(np.int64) + 1970 * 12
+    elif a.dtype.kind in "iu":
+        m = a.astype(np.int64)
+    else:
+        raise ValueError(f"month_index: month labels must be datetime64 or integers, not {a.dtype}")
+    if m.ndim != 1:
+        raise ValueError("month_index: month labels must be one-dimensional")
+    if len(m) and (m.min() < -(2 ** 31) or m.max() >= 2 ** 31):
+        raise ValueError("month_index: month numbers must fit 32 bits")
+    if len(m) > 1 and not bool(np.all(np.diff(m) > 0)):
+        raise ValueError("month_index: two segment labels fall in the same calendar month (or the labels "
+                         "do not ascend)")
+    return m.astype(np.int32)
+
+
+def _set_ids(panel, ids_t):
+    """Firm identity of a freshly built panel: the month-major ids and the segments' calendar
+    month numbers (host and device)."""
+    panel.ids = ids_t
+    panel.month_index = month_index(panel.months)
+    panel.month_index_device()
+    return panel
+
+
 def gather_layout(raw, perm, layout="f64"):
     """The device gather of an ingest: FP64 columns ``raw`` [C, n_in] (input row order) ->
     month-major rows in the panel's layout, (cols, planes): "f64" the FP64 columns, "planes"
@@ -231,11 +275,20 @@ def gather_layout(raw, perm, layout="f64"):
 
 
 def panel_from_arrays(arrays: Sequence[np.ndarray], names, labels, me=None, nyse=None,
-                      device=None, layout="f64"):
+                      device=None, layout="f64", ids=None):
     """Upload host columns (original row order) and permute them month-major on device, into
-    the panel's ``layout`` ("f64", "planes": the split layout only, "both")."""
+    the panel's ``layout`` ("f64", "planes": the split layout only, "both").  ``ids``: each input
+    row's integer firm id; the panel then carries firm identity (``ids``, ``month_index``), which
+    the month links and the multi-month returns need: the labels must then be datetime64 or
+    integer month numbers (``month_index``), and a month's rows must arrive in ascending id order
+    (``month_links`` checks it)."""
     device = device or require_device()
     _, uniq, order, seg_off = month_segments(labels)
+    if ids is not None:
+        month_index(uniq)   # refuse labels without a calendar before any upload
+        ids = np.asarray(ids)
+        if ids.dtype.kind not in "iu" or ids.shape != (len(labels),):
+            raise ValueError("panel_from_arrays: ids must hold one integer firm id per input row")
     n_in = len(labels)
     host = np.empty((len(arrays), n_in), dtype=np.float64)
     for i, a in enumerate(arrays):
@@ -252,6 +305,8 @@ def panel_from_arrays(arrays: Sequence[np.ndarray], names, labels, me=None, nyse
                     seg_off_h=seg_off, months=uniq, me=me_t, nyse=nyse_t, order=order, planes=planes)
     if cols is not None and planes is not None:
         p.planes_version = cols._version
+    if ids is not None:
+        _set_ids(p, torch.from_numpy(ids.astype(np.int64)).to(device).index_select(0, perm))
     return p
 
 
@@ -309,7 +364,8 @@ def panel_synthetic(nmonths, nfirms, seed, month0=0, nan_rate=0.02, nyse_rate=0.
     """Generate a balanced synthetic panel directly in HBM (fm_gen_panel; identical to
     fmcore.synth.synth_arrays with present_rate=1).  ``layout``: "f64" the FP64 columns,
     "planes" only the split layout (fm_gen_panel_planes writes the high / low words itself:
-    no FP64 columns, no layout pass), "both"."""
+    no FP64 columns, no layout pass), "both".  The firm ids are 10000 + the position in the
+    month, the month numbers month0, month0 + 1, ..."""
     from .synth import WINSOR_VARS
     if layout not in PANEL_LAYOUTS:
         raise ValueError(f"layout must be one of {PANEL_LAYOUTS}")
@@ -336,7 +392,24 @@ def panel_synthetic(nmonths, nfirms, seed, month0=0, nan_rate=0.02, nyse_rate=0.
                     planes=planes)
     if cols is not None and planes is not None:
         p.planes_version = cols._version
+    _set_ids(p, _balanced_ids(nmonths, nfirms, device))
     return p
+
+
+def _balanced_ids(nmonths, nfirms, device):
+    """The ids of a balanced panel, 10000 + the position in the month, for every month: one month
+    uploaded, then doubled by contiguous device copies (memcpys only, so generating a panel still
+    loads no kernel but the generator's)."""
+    n = nmonths * nfirms
+    ids = torch.empty(n, dtype=torch.int64, device=device)
+    if n:
+        ids[:nfirms].copy_(torch.from_numpy(np.arange(nfirms, dtype=np.int64) + 10000))
+    k = nfirms
+    while 0 < k < n:
+        m = min(k, n - k)
+        ids[k:k + m].copy_(ids[:m])
+        k += m
+    return ids
 
 
 # ------------------------------------------------------------------------------------------
@@ -1610,8 +1683,8 @@ def rank_transform(panel: DevicePanel, cols=None, method="average", scale="pct",
     pct)``, the exact definition is in fm_hip.h), every other column copied unchanged.
     ``scale``: "raw" r, "pct" r / n, "uniform" r / (n + 1) - 0.5.  ``level`` (uint8 per row) with
     ``min_level`` ranks within that universe and gives NaN outside it.  Returns a new f64-layout
-    ``DevicePanel`` that shares the input's segments, ``me``, ``nyse``, ``months`` and ``order``
-    (``out``: its [C, n] float64 column block, not the input's); the [len(cols), T] int32 table
+    ``DevicePanel`` that shares the input's segments, ``me``, ``nyse``, ``months``, ``order``, ``ids``
+    and ``month_index`` (``out``: its [C, n] float64 column block, not the input's); the [len(cols), T] int32 table
     of ranked rows per month is its ``rank_nvalid`` attribute."""
     if method not in RANK_METHODS:
         raise ValueError(f"rank_transform: method must be one of {sorted(RANK_METHODS)} "
@@ -1657,8 +1730,114 @@ def rank_transform(panel: DevicePanel, cols=None, method="average", scale="pct",
     res = DevicePanel(cols=out, names=list(panel.names), seg_off=panel.seg_off, seg_off_h=panel.seg_off_h,
                       months=panel.months, me=panel.me, nyse=panel.nyse, order=panel.order,
                       chunk_rows=panel.chunk_rows, chunk_split=panel.chunk_split, chunk_policy=panel.chunk_policy,
-                      row_origin=panel.row_origin)
+                      row_origin=panel.row_origin, ids=panel.ids, month_index=panel.month_index)
+    _share_links(panel, res)
     res.rank_nvalid = nvalid
+    return res
+
+
+# ------------------------------------------------------------------------------------------
+# Multi-month return horizons (A16): firm links between neighbouring months, compounded returns
+# ------------------------------------------------------------------------------------------
+MAX_HORIZON = L.FM_MAX_HORIZON
+
+
+def _share_links(src: DevicePanel, dst: DevicePanel):
+    """A panel built from ``src`` with the same rows and ids keeps the links ``src`` has."""
+    links = src.__dict__.get("_links")
+    if links is not None:
+        dst.__dict__["_links"] = links
+
+
+def month_links(panel: DevicePanel, step=1):
+    """A16: for every row, the position inside the neighbouring calendar month (``step`` +1: the
+    following one, -1: the preceding one) of the same firm's row, -1 where there is none -- no such
+    segment, a gap in the calendar (``panel.month_index``), or the firm is absent there
+    (fm_month_links; the definition is in fm_hip.h).  int32 [rows] on the device, computed once per
+    panel and step and kept.  The panel needs ``ids``, strictly ascending inside every month:
+    ValueError otherwise (one host sync on the order check, at ingest)."""
+    if step not in (1, -1):
+        raise ValueError(f"month_links: step must be +1 or -1, got {step!r}")
+    if panel.ids is None or panel.month_index is None:
+        raise ValueError("month_links: the panel carries no firm ids (build it with ids=...)")
+    cache = panel.__dict__.setdefault("_links", {})
+    if step in cache:
+        return cache[step]
+    _check_ids(panel.ids)
+    n, T = panel.nrows, panel.nseg
+    if panel.ids.shape[0] != n or len(panel.month_index) != T:
+        raise ValueError("month_links: ids / month_index do not match the panel's rows / months")
+    dev = panel.device
+    link = torch.empty(n, dtype=torch.int32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    mi = panel.month_index_device()
+    a = L.LinksArgs(ids=panel.ids.data_ptr(), seg_off=panel.seg_off.data_ptr(), month_index=mi.data_ptr(),
+                    nrows=n, nseg=T, step=int(step), link=link.data_ptr(), bad=bad.data_ptr())
+    _kcall("fm_month_links", "fm_month_links", L.C.byref(a), _stream())
+    _remember("fm_month_links", "fm_month_links", a, panel.ids, panel.seg_off, mi, link, bad)
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"month_links: {nbad} rows have a firm id that is not greater than the previous row's "
+                         "in the same month (ids must be unique and ascending inside a month)")
+    cache[step] = link
+    return link
+
+
+def horizon_return(seg_off, ret, link, horizon, out=None):
+    """A16: the compounded ``horizon``-month return of every row, (1 + r_t)(1 + r_t+1) ... - 1 over the
+    firm's rows of the following months, found through ``link`` (``month_links`` with step +1); NaN
+    where a month of the chain is missing (fm_horizon_return; the definition, exact to the bit, is
+    in fm_hip.h).  Plain device tensors: ``seg_off`` int64 [T+1], ``ret`` float64 [rows], ``link``
+    int32 [rows]; returns (or fills ``out``) float64 [rows]."""
+    n = int(ret.shape[0])
+    dev = ret.device
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("horizon_return: seg_off must be an int64 [T+1] tensor on the returns' device")
+    seg_off = seg_off.contiguous()
+    for t, dt, what in ((ret, torch.float64, "ret"), (link, torch.int32, "link")):
+        if t.dtype != dt or t.dim() != 1 or t.shape[0] != n or t.device != dev:
+            raise ValueError(f"horizon_return: {what} must be a {dt} [{n}] tensor on {dev}")
+    ret, link = ret.contiguous(), link.contiguous()
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.shape != (n,) or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"horizon_return: out must be a contiguous float64 [{n}] tensor on {dev}")
+    a = L.HorizonArgs(ret=ret.data_ptr(), link=link.data_ptr(), seg_off=seg_off.data_ptr(), nrows=n,
+                      nseg=int(seg_off.shape[0]) - 1, horizon=int(horizon), out=out.data_ptr())
+    _kcall("fm_horizon_return", "fm_horizon_return", L.C.byref(a), _stream())
+    _remember("fm_horizon_return", "fm_horizon_return", a, ret, link, seg_off, out)
+    return out
+
+
+def horizon_panel(panel: DevicePanel, h, ret="retx", name=None):
+    """A16: the panel with one more column, the compounded ``h``-month return of column ``ret``
+    (``horizon_return`` over ``month_links(panel, +1)``), named ``f"{ret}_{h}m"`` unless ``name`` is
+    given and appended last; every other column is copied unchanged.  Returns a new f64-layout
+    ``DevicePanel`` that shares the input's segments, ``me``, ``nyse``, ``months``, ``order``, ``ids`` and
+    ``month_index``, as ``rank_transform`` returns its panel.  This is an ingest-time copy of the whole
+    panel (one more [C+1, n] block in HBM), made once per horizon, not a per-step stage.  The panel
+    needs ``ids``; ValueError for a horizon outside 1..MAX_HORIZON, a column name that exists
+    already, or more than FM_MAX_COLS columns."""
+    h = int(h)
+    if h < 1 or h > MAX_HORIZON:
+        raise ValueError(f"horizon_panel: the horizon must be 1..{MAX_HORIZON}, got {h}")
+    ci = panel.col(ret) if isinstance(ret, str) else int(ret)
+    name = f"{panel.names[ci]}_{h}m" if name is None else str(name)
+    if name in panel.names:
+        raise ValueError(f"horizon_panel: the panel already has a column {name!r}")
+    if panel.ncols + 1 > L.FM_MAX_COLS:
+        raise ValueError(f"horizon_panel: at most {L.FM_MAX_COLS} columns per panel")
+    link = month_links(panel, 1)
+    src = panel.values()
+    C, n = panel.ncols, panel.nrows
+    out = torch.empty((C + 1, n), dtype=torch.float64, device=src.device)
+    out[:C].copy_(src[:, :n])
+    horizon_return(panel.seg_off, src[ci], link, h, out=out[C])
+    res = DevicePanel(cols=out, names=list(panel.names) + [name], seg_off=panel.seg_off, seg_off_h=panel.seg_off_h,
+                      months=panel.months, me=panel.me, nyse=panel.nyse, order=panel.order,
+                      chunk_rows=panel.chunk_rows, chunk_split=panel.chunk_split, chunk_policy=panel.chunk_policy,
+                      row_origin=panel.row_origin, ids=panel.ids, month_index=panel.month_index)
+    _share_links(panel, res)
     return res
 
 

@@ -14,6 +14,8 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
  -> optionally (``PipelineConfig.forecast_compare``) per universe and pair of Table-2 models the
     monthly regression of one model's forecast on the other's and of returns on its residual
     (paper Table 4, build-defined A15), likewise in one launch
+With ``PipelineConfig.horizon`` = k > 1 the dependent variable of all of this is the compounded
+k-month return (paper Section 4, Tables 8 and 9; build-defined A16), a column built once at ingest.
 All stages are libfm_hip kernels; the panel is read from HBM twice (cuts, Gram).
 """
 from __future__ import annotations
@@ -95,6 +97,16 @@ class PipelineConfig:
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
     forecast_dist: bool = field(default=False, kw_only=True)
     forecast_dist_q: Sequence[float] = field(default=(0.1, 0.9), kw_only=True)
+    # A16 (paper Section 4, Tables 8 and 9): the dependent variable of every stage is the compounded
+    # ``horizon``-month return y_t .. y_{t+horizon-1} (column f"{y}_{horizon}m", built once by
+    # engine.horizon_panel when the panel lacks it; the panel then needs firm ids).  1 = monthly
+    # returns and no launch more or less; 1..engine.MAX_HORIZON, ValueError otherwise.  Above 1 the
+    # forecast lag must be at least the horizon (ValueError): the coefficients of month t - lag are
+    # fitted on returns that end in month t - lag + horizon - 1, which must lie before t.  ``nw_lags``
+    # stays the caller's choice: overlapping k-month returns are autocorrelated to k - 1 lags, and
+    # the paper uses 10 lags for 6 months and 16 for 12.
+    # Keyword-only and in front of ``forecast_compare``: the two trailing fields are pinned by tests.
+    horizon: int = field(default=1, kw_only=True)
     # A15 inside the pipeline (paper Table 4, model comparison): for every universe and every pair
     # i < j of the Table-2 models (not Figure 1), each month's regression of forecast j on forecast i
     # and of the return on its residual, from the same forecasts under the same two rules as
@@ -123,6 +135,7 @@ class PipelineResult:
     forecast_dist: Optional[E.ForecastDist] = None       # cfg.forecast_dist: [nsort, T, 2+nq] and [nsort, T]
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
+    y_col: str = "retx"                                   # the dependent column (cfg.horizon > 1: f"{y}_{h}m")
     forecast_compare: Optional[E.ForecastCompare] = None     # cfg.forecast_compare: [npair, T, 7], [npair, T, 2], [npair, T]
     forecast_compare_summary: Optional[E.Summary] = None     # [npair, 7]
     forecast_compare_pairs: Optional[List[tuple]] = None     # (problem_a, problem_b) of each pair: b regressed on a
@@ -230,9 +243,34 @@ def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo
         sum_range=sum_range, roll_own=roll_own)
 
 
+def check_horizon(cfg: PipelineConfig):
+    """The rules of ``PipelineConfig.horizon`` (no device work)."""
+    h = cfg.horizon
+    if not isinstance(h, (int, np.integer)) or isinstance(h, bool) or h < 1 or h > E.MAX_HORIZON:
+        raise ValueError(f"PipelineConfig: horizon must be an integer in 1..{E.MAX_HORIZON}, got {h!r}")
+    if h > 1 and cfg.lag < h:
+        raise ValueError(f"PipelineConfig: horizon={h} needs lag >= horizon, got lag={cfg.lag} (the coefficients "
+                         "of month t - lag would be fitted on returns that end after month t)")
+
+
+def horizon_column(panel: E.DevicePanel, cfg: PipelineConfig, y="retx"):
+    """The panel and dependent column of a run: (panel, y) at horizon 1; else the column
+    f"{y}_{h}m", appended by engine.horizon_panel when the panel lacks it."""
+    if cfg.horizon == 1:
+        return panel, y
+    y_col = f"{y}_{cfg.horizon}m"
+    if y_col not in panel.names:
+        panel = E.horizon_panel(panel, cfg.horizon, ret=y, name=y_col)
+    return panel, y_col
+
+
 def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=None, y="retx"):
+    """The whole pass on one device.  ``cfg.horizon`` = h > 1 (A16): every stage -- the Gram, the
+    fix-ups, the predictive records and the returns of the portfolio and comparison stages -- takes
+    the compounded h-month return f"{y}_{h}m" as the dependent variable (``PipelineResult.y_col``)."""
     cfg = cfg or PipelineConfig()
     model_cols = model_cols or table2_models()
+    check_horizon(cfg)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare")):
         if on and cfg.standardize:
@@ -240,6 +278,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                              "need the moment tables)")
         if on and not cfg.forecasts:
             raise ValueError(f"PipelineConfig: {what} needs forecasts=True (the lagged rolling coefficients)")
+    panel, y = horizon_column(panel, cfg, y)
     res, names, cuts, level, bp, gpanel, models = _local_stage(panel, cfg, model_cols, y)
     ix, summ, roll, pred, pst = time_series_stage(res, cfg)
     psumm = None
@@ -278,7 +317,8 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                           pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
                           portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
                           forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
-                          forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs)
+                          forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
+                          y_col=y)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

@@ -30,6 +30,10 @@ class ShardedStep:
     def __init__(self, panel: E.DevicePanel, cfg: LW.PipelineConfig, model_cols, world=1, rank=0,
                  seg_lo=0, seg_hi=None, global_months=None, counts=None, group=None, exchange=None,
                  shard_ts=None):
+        if cfg.horizon != 1:
+            # a shard's last horizon - 1 months need the next shard's rows (no halo exchange)
+            raise ValueError("ShardedStep: cfg.horizon must be 1 (multi-month returns need the following "
+                             "months' rows, which a month shard does not hold)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols
         self.world, self.rank, self.group = world, rank, group
         self.seg_lo = seg_lo

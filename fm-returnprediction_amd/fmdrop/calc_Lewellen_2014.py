@@ -10,7 +10,9 @@ Mirrored (same names, signatures, return types and row/column/index order):
 Extensions the north star names (not in the reference; parity unpinned):
   standardize, rank_transform, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
   predictive_slope_regressions, forecast_sorted_portfolios, forecast_distribution,
-  forecast_comparison, lewellen_pipeline, build_table_5, build_table_3, build_table_4.
+  forecast_comparison, lewellen_pipeline, build_table_5, build_table_3, build_table_4,
+  horizon_returns, build_table_2_horizon (multi-month returns: paper Tables 8 and 9; every
+  build_table_* takes horizon=k, lag>=k, nw_lags=...).
 Firm-axis characteristic builders (§8(f) row 2; one fused device pass, fm_firm_chars):
   calc_log_size, calc_log_bm, calc_return_12_2, calc_accruals, calc_roa,
   calc_log_assets_growth, calc_dy, calc_log_return_13_36, calc_log_issues_12,
@@ -813,15 +815,58 @@ def _pipeline_panel(crsp_comp: pd.DataFrame, variables_dict: dict = None):
     me = _api.as_f64(df["me"])
     nyse = (df["primaryexch"] == "N").to_numpy().astype(np.uint8)
     panel = _E.panel_from_arrays([_api.as_f64(df[c]) for c in cols], cols, df["mthcaldt"].values,
-                                 me=me, nyse=nyse)
+                                 me=me, nyse=nyse, ids=_firm_ids(df["permno"], df["mthcaldt"]))
     return panel, model_cols
+
+
+def _firm_ids(ids, dates):
+    """The int64 firm ids a panel can carry, or None where the frame has no firm identity the
+    month links could use: ids that are not whole numbers, or dates that are neither datetime64
+    nor integer month numbers (such a panel runs everything but the multi-month horizons)."""
+    p = np.asarray(ids)
+    if np.asarray(dates).dtype.kind not in "Miu":
+        return None
+    if p.dtype.kind in "iu":
+        return p.astype(np.int64)
+    if p.dtype.kind == "f" and len(p) and bool(np.all(np.isfinite(p))) and bool(np.all(p == np.floor(p))) \
+            and float(np.abs(p).max()) < 2.0 ** 53:
+        return p.astype(np.int64)
+    return None
+
+
+def horizon_returns(df: pd.DataFrame, h: int, return_col: str = "retx", date_col: str = "mthcaldt",
+                    id_col: str = "permno") -> pd.DataFrame:
+    """A16 (paper Section 4): the compounded ``h``-month return (1 + r_t)(1 + r_t+1) ... (1 + r_t+h-1) - 1
+    of every row, over the same firm's rows of the following h - 1 calendar months, as the new column
+    f"{return_col}_{h}m"; NaN where one of those months is missing for the firm (a gap in its
+    history, or the end of the sample).  Each factor and product is rounded on its own, in that
+    order, on the device (fm_month_links, fm_horizon_return).  Returns are decimals.  ``date_col``
+    must be datetime64 or integer month numbers, with one row per (month, firm): ValueError
+    otherwise.  Returns a copy of the frame, index and row order preserved; rows with a missing date
+    get NaN."""
+    ids = _firm_ids(df[id_col], df[date_col])
+    if ids is None:
+        raise ValueError(f"horizon_returns: {id_col!r} must hold whole-number firm ids and {date_col!r} "
+                         "datetime64 or integer months")
+    dates = df[date_col].to_numpy()
+    order = np.lexsort((ids, dates))
+    panel = _E.panel_from_arrays([_api.as_f64(df[return_col])[order]], [return_col], dates[order], ids=ids[order])
+    link = _E.month_links(panel, 1)
+    r = _E.horizon_return(panel.seg_off, panel.cols[0], link, h).cpu().numpy()
+    col = np.full(len(df), np.nan)
+    col[order[panel.order]] = r
+    out = df.copy()
+    out[f"{return_col}_{h}m"] = col
+    return out
 
 
 def lewellen_pipeline(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):
     """The whole Table-2 / Figure-1 / forecast pass device-resident from one frame
     (winsorize -> universes -> 3 models x 3 universes + Figure 1 -> NW -> rolling ->
     predictive slopes; with ``portfolios=nport`` also the forecast-sorted portfolios of every
-    Table-2 problem).  Returns fmcore.lewellen.PipelineResult (device tensors)."""
+    Table-2 problem; with ``horizon=k, lag>=k`` on compounded k-month returns, the paper's
+    Section 4, ``nw_lags`` being the caller's choice: the paper takes 10 for 6 and 16 for 12
+    months).  Returns fmcore.lewellen.PipelineResult (device tensors)."""
     panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
     return _LW.run_pipeline(panel, _LW.PipelineConfig(**cfg), model_cols=model_cols)
 
@@ -894,3 +939,35 @@ def build_table_4(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):
         rows.append([mean[p, 0], mean[p, 1], mean[p, 3], mean[p, 4], se[p, 4], t[p, 4]])
     return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(keys, names=["universe", "comparison"]),
                         columns=["Correlation", "Slope", "Res. std.", "Pred. slope", "S.E.", "t-stat"])
+
+
+def build_table_2_horizon(crsp_comp: pd.DataFrame, horizon: int, variables_dict: dict = None, **cfg):
+    """Paper Tables 8a / 8b (horizon 6 / 12) from ONE device pipeline run (build-defined A16; no
+    reference line): Table 2 with the compounded ``horizon``-month return as the dependent variable --
+    Fama-MacBeth slopes, Newey-West t-statistics, mean R^2 and mean N of Models 1-3 on each universe,
+    in build_table_2's frame format.  ``cfg``: further PipelineConfig fields; ``nw_lags`` is the
+    caller's choice (the paper uses 10 lags for 6-month and 16 for 12-month returns; the default is
+    PipelineConfig's 4) and ``lag`` defaults to the horizon.  Returns are decimals, so the slopes are
+    1/100 of the paper's, which regresses percent returns."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    pcfg = _LW.PipelineConfig(**dict({"lag": max(int(horizon), 1)}, **cfg, horizon=horizon))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    res, s = out.res, out.summary
+    status_h = res.status.cpu().numpy()
+    order = sorted(range(len(res.problems)), key=lambda k: (res.problems[k].model, res.problems[k].level))
+    for k in order:
+        if out.model_names[res.problems[k].model] != "Figure 1":
+            _api.raise_like_reference(status_h[:, k], res.problems[k].K)
+    mean, se, t, nobs = (x.cpu().numpy() for x in (s.mean, s.se, s.tstat, s.nobs))
+    stats = {}
+    for k, p in enumerate(res.problems):
+        name = out.model_names[p.model]
+        if name == "Figure 1":
+            continue
+        xs = model_cols[name]
+        ser = _api.summary_from_device(mean[k], se[k], t[k], nobs[k], xs, k_slope0=1, k_r2=res.pmax,
+                                       k_n=res.pmax + 1)
+        stats[(name, _LW.SUBSET_NAMES[p.level])] = {
+            "coef": [ser[f"{x}_coef"] for x in xs], "tstat": [ser[f"{x}_tstat"] for x in xs],
+            "mean_R2": ser["mean_R2"], "mean_N": ser["mean_N"]}
+    return _format_table_2(stats, list(_LW.SUBSET_NAMES))

@@ -55,6 +55,11 @@
  *                      on its residual (paper Table 4, "model comparison"); no reference line
  *   fm_rank_transform <- build-defined extension A13: per-month cross-sectional ranks of the
  *                      characteristics (pandas groupby(month)[x].rank); no reference line
+ *   fm_month_links, fm_horizon_return <- build-defined extension A16: each row's position in the
+ *                      same firm's row of the neighbouring calendar month, and from those links
+ *                      the compounded k-month return (1 + r_t) ... (1 + r_{t+k-1}) - 1 (the
+ *                      dependent variable of the paper's Tables 8 and 9, "longer-horizon
+ *                      expected returns"); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -210,7 +215,7 @@ const char* fm_last_error(void);
 #define FM_ARG_STRUCTS(X)                                                                     \
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
-    X(fm_fdist_args) X(fm_fcmp_args)
+    X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -703,6 +708,61 @@ typedef struct fm_rank_args {
 } fm_rank_args;
 
 int fm_rank_transform(const fm_rank_args* args, void* stream);
+
+/* fm_month_links: for every row of a month-sorted panel, where the same firm's row lies in the
+ * neighbouring calendar month (build-defined extension A16; no reference line).  Rows sorted by
+ * (month, firm id), months seg_off[nseg+1] of any length below 2^31 rows, nrows = seg_off[nseg];
+ * ids are full int64 and strictly ascending inside a month; month_index[s] is the calendar month
+ * number of segment s (year * 12 + month - 1, or any integer count of months), strictly ascending.
+ * For row i of segment s, with t = s + step:
+ *   link[i] = the position inside segment t (0-based) of the row of t with ids == ids[i], when
+ *             0 <= t < nseg, month_index[t] == month_index[s] + step and such a row exists;
+ *   link[i] = -1 otherwise (no neighbouring segment, a gap in the calendar, the firm is absent).
+ * bad[0] (zeroed by the caller) receives the number of rows whose id is not greater than their
+ * predecessor's in the month.  The links of a call with bad != 0 are unspecified (the searches
+ * assume the order), but every access stays inside ids[0, nrows).  Arguments are refused with
+ * FM_EINVAL before any launch: step other than +1 / -1, nseg or nrows below zero, a NULL pointer
+ * (the message names the field).  nseg == 0 or nrows == 0 is a valid empty call.  Zero-initialize
+ * the struct (it grows at the end). */
+typedef struct fm_links_args {
+    const int64_t* ids;          /* [nrows] firm id of each row */
+    const int64_t* seg_off;      /* [nseg+1] */
+    const int32_t* month_index;  /* [nseg] calendar month number, strictly ascending */
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t nseg;
+    int32_t step;                /* +1: the following month, -1: the preceding one */
+    int32_t* link;               /* [nrows] */
+    int32_t* bad;                /* [1], zeroed by the caller */
+} fm_links_args;
+
+int fm_month_links(const fm_links_args* args, void* stream);
+
+/* fm_horizon_return: the compounded `horizon`-month return of every row from the step +1 links
+ * of fm_month_links (build-defined extension A16; no reference line; the dependent variable of
+ * the paper's Tables 8a/8b and 9a/9b).  Returns are decimals.  For row i of segment s:
+ *   row_0 = i; for j = 1 .. horizon-1: row_j = seg_off[s+j] + link[row_{j-1}];
+ *   a hop is missing when s + j >= nseg, when the link is negative or not below the length of
+ *   segment s + j (a stale or foreign link array gives NaN, never a read outside [0, nrows));
+ *   a missing hop: out[i] = NaN; otherwise p = 1 + ret[row_0], then p = p * (1 + ret[row_j]) for
+ *   j = 1 .. horizon-1 in that order, and out[i] = p - 1.
+ * Every operation is rounded on its own, so the output is specified to the bit: a NaN or infinite
+ * return propagates by the IEEE rules, and horizon 1 gives (1 + r) - 1, not r.  A month's output
+ * depends on that month's rows and the following horizon-1 months' rows alone.  Refused with
+ * FM_EINVAL before any launch: horizon outside 1..FM_MAX_HORIZON, nseg or nrows below zero, a NULL
+ * pointer, out overlapping ret or link.  nseg == 0 or nrows == 0 is a valid empty call.
+ * Zero-initialize the struct (it grows at the end). */
+#define FM_MAX_HORIZON 60
+typedef struct fm_horizon_args {
+    const double* ret;           /* [nrows] one-month returns */
+    const int32_t* link;         /* [nrows] fm_month_links with step +1 */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t nseg;
+    int32_t horizon;             /* 1 .. FM_MAX_HORIZON */
+    double* out;                 /* [nrows] */
+} fm_horizon_args;
+
+int fm_horizon_return(const fm_horizon_args* args, void* stream);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
