@@ -930,10 +930,25 @@ def _problems(models, nlevels):
     return problems
 
 
-def fm_pass(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, cuts: Cuts = None,
-            shift=None, inv_scale=None, add_back=None, moments=False, cols=None, const_check=True):
-    """One batched cross-sectional pass: every (model, universe level) problem for every
-    month from one read of the panel per model group.  Returns an FMResult."""
+@dataclass
+class GramGroup:
+    """One model group's Gram launch: its plan, the chunk plan it ran under and what it wrote."""
+    group: _GroupPlan
+    plan: _Plan
+    partial: torch.Tensor   # [nchunks, nb, zw*(zw+1)/2], nb = group.npatterns * nlevels
+    flags: torch.Tensor     # [T, nmodels] int32, reserved: never read
+    zw: int
+
+
+def gram_partials(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, cuts: Cuts = None,
+                  shift=None, inv_scale=None, cols=None, const_check=True, partial_out=None, problems=None):
+    """The Gram half of fm_pass: one fm_gram launch per model group, under the panel's chunk plan.
+    Returns a GramGroup per model group.  ``partial[chunk, pattern * nlevels + level]`` is the packed
+    upper triangle (entry (i, j >= i) at i*zw - i*(i-1)/2 + (j-i)) of Z'Z over the chunk's rows of
+    that validity pattern and universe level, z = [1, (clip(x) - shift) * inv_scale ...]; a bucket
+    without rows is stored as zeros (fm_solve sums every image).  ``shift`` / ``inv_scale`` None:
+    0 / 1 (fm_pass passes its pivot).  ``partial_out``: the caller's own contiguous FP64 buffer
+    [nchunks, nb, PK] to write into (a list of them, one per group, when there are several)."""
     src = _source(panel, cols)
     ncols = src.ncols
     if ncols > L.FM_MAX_COLS:
@@ -942,25 +957,27 @@ def fm_pass(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, 
     T = panel.nseg
     zw = 16 if ncols <= 15 else 32
     cap = 16 if zw == 16 else 8
-    if shift is None:
-        shift = pilot_shift(panel, cols)
-    if add_back is None and inv_scale is None:
-        add_back = shift
-    problems = _problems(models, nlevels)
-    pmax = max(2, max(p.K + 1 for p in problems))
-    nprob = len(problems)
-    rs = pmax + 2
-    rec = torch.empty((T, nprob, rs), dtype=torch.float64, device=dev)
-    status = torch.empty((T, nprob), dtype=torch.int32, device=dev)   # every problem is in one group
-    mom_stride = 1 + (pmax + 1) + (pmax + 1) ** 2
-    mom = torch.empty((T, nprob, mom_stride), dtype=torch.float64, device=dev) if moments else None
+    if problems is None:
+        problems = _problems(models, nlevels)
     plan = _chunk_plan(panel)
     lo = cuts.lo if cuts is not None else None
     hi = cuts.hi if cuts is not None else None
     groups = _group_plans(panel, models, problems, nlevels, cap, const_check, dev)
-    for gpl in groups:
+    if partial_out is not None and not isinstance(partial_out, (list, tuple)):
+        partial_out = [partial_out]
+    if partial_out is not None and len(partial_out) != len(groups):
+        raise ValueError(f"partial_out: {len(groups)} model groups need as many buffers")
+    out = []
+    for k, gpl in enumerate(groups):
         nb = gpl.npatterns * nlevels
-        partial = torch.empty((plan.nchunks, nb, zw * (zw + 1) // 2), dtype=torch.float64, device=dev)
+        shape = (plan.nchunks, nb, zw * (zw + 1) // 2)
+        if partial_out is None:
+            partial = torch.empty(shape, dtype=torch.float64, device=dev)
+        else:
+            partial = partial_out[k]
+            if tuple(partial.shape) != shape or partial.dtype != torch.float64 or \
+                    not partial.is_contiguous() or partial.device != dev:
+                raise ValueError(f"partial_out: group {k} needs a contiguous float64 {shape} tensor on {dev}")
         flags = torch.empty((T, gpl.nmodels), dtype=torch.int32, device=dev)   # reserved: never read
         ga = L.GramArgs(
             cols=src.ptr, col_stride=src.stride if src.f64 is not None else 0, ncols=ncols, nseg=T,
@@ -975,11 +992,42 @@ def fm_pass(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, 
         _kcall("fm_gram", "fm_gram", L.C.byref(ga), _stream())
         _remember("fm_gram", "fm_gram", ga, src.f64, panel.planes, partial, flags, lo, hi, shift, inv_scale, level,
                   plan, gpl)
-        grec, gst, gmom = _solve_group(panel, src, gpl, partial, plan.seg_chunk_off, zw, nlevels, T, pmax,
+        out.append(GramGroup(gpl, plan, partial, flags, zw))
+    return out
+
+
+def fm_pass(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, cuts: Cuts = None,
+            shift=None, inv_scale=None, add_back=None, moments=False, cols=None, const_check=True):
+    """One batched cross-sectional pass: every (model, universe level) problem for every
+    month from one read of the panel per model group.  Returns an FMResult."""
+    src = _source(panel, cols)
+    dev = src.device
+    T = panel.nseg
+    if src.ncols > L.FM_MAX_COLS:
+        raise ValueError(f"at most {L.FM_MAX_COLS} columns per pass")
+    if shift is None:
+        shift = pilot_shift(panel, cols)
+    if add_back is None and inv_scale is None:
+        add_back = shift
+    problems = _problems(models, nlevels)
+    pmax = max(2, max(p.K + 1 for p in problems))
+    nprob = len(problems)
+    rs = pmax + 2
+    mom_stride = 1 + (pmax + 1) + (pmax + 1) ** 2
+    rec = torch.empty((T, nprob, rs), dtype=torch.float64, device=dev)
+    status = torch.empty((T, nprob), dtype=torch.int32, device=dev)   # every problem is in one group
+    mom = torch.empty((T, nprob, mom_stride), dtype=torch.float64, device=dev) if moments else None
+    lo = cuts.lo if cuts is not None else None
+    hi = cuts.hi if cuts is not None else None
+    grams = gram_partials(panel, models, level, nlevels, cuts, shift, inv_scale, cols, const_check,
+                          problems=problems)
+    for g in grams:
+        gpl, plan = g.group, g.plan
+        grec, gst, gmom = _solve_group(panel, src, gpl, g.partial, plan.seg_chunk_off, g.zw, nlevels, T, pmax,
                                        mom_stride, lo, hi, shift, inv_scale, add_back, level,
-                                       const_check, (src.f64, panel.planes, flags, lo, hi, shift, inv_scale,
+                                       const_check, (src.f64, panel.planes, g.flags, lo, hi, shift, inv_scale,
                                                      level, plan))
-        if len(groups) == 1:
+        if len(grams) == 1:
             rec, status = grec, gst
             mom = gmom if moments else None
         else:
