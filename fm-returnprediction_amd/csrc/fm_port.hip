@@ -33,6 +33,10 @@
 //
 // fm_forecast_compare (A15; paper Table 4) is fcmp_kernel below, over a grid of (month, pair):
 // phase 1's load for the pair's two forecasts, then eleven of those reductions and no selection.
+//
+// fm_forecast_horizon (A17; paper Section 4, second approach) is fhor_kernel below: fdist_kernel's
+// phases 1-2, the forecasts scaled around their mean in place, then eight of those reductions, the
+// last five against the long-horizon return vector.
 #include <math.h>
 
 #include "fm_common.h"
@@ -80,8 +84,8 @@ __device__ __forceinline__ void lds_bitonic(uint64_t* buf, int P) {
 }
 
 // What a month's workgroup sorts by.  PlainSrc: the caller's forecast and return vectors
-// (fm_portfolio_sort).  PanelSrc<PL>: sort j of the fm_forecast_src that fm_fport_args and
-// fm_fdist_args embed as `src`, panel values from the FP64 columns or (PL) from the planes, two
+// (fm_portfolio_sort).  PanelSrc<PL>: sort j of the fm_forecast_src that fm_fport_args,
+// fm_fdist_args and fm_fhor_args embed as `src`, panel values from the FP64 columns or (PL) from the planes, two
 // 4-byte loads joined in registers.
 struct PlainSrc {
     static constexpr bool FUSED = false;
@@ -719,11 +723,12 @@ __device__ __forceinline__ void order_stat_keys(const double (&fe)[VPT], uint32_
     __syncthreads();
 }
 
-// The plain source of fm_forecast_dist: sort j's forecasts are the caller's vector j
+// The plain source of fm_forecast_dist and fm_forecast_horizon: sort j's forecasts are the caller's vector j
 struct VecSrc {
     static constexpr bool FUSED = false;
     int j;   // blockIdx.y
-    __device__ static VecSrc make(const fm_fdist_args&) { return {(int)blockIdx.y}; }
+    template <class A>
+    __device__ static VecSrc make(const A&) { return {(int)blockIdx.y}; }
 };
 
 // The fixed-order sum of one term per row of the month (x[v] for the thread's row v; +0.0 for
@@ -1024,6 +1029,189 @@ int launch_fcmp(const fm_fcmp_args& a, hipStream_t st) {
     return check_launch(who);
 }
 
+// ---- fm_forecast_horizon (extension A17; the paper's Section 4, second approach) --------------
+// Per (month, sort): the monthly forecast F scaled to G = a m + g (F - m) around the month's mean
+// m, G's mean, standard deviation and quantiles, and the realised long-horizon return regressed on
+// G.  Phases 1-2 are fdist_kernel's (the same loads, fused_forecast, order_stat_keys on F: G is
+// non-decreasing in F, so F's order statistics mapped to G are G's); the mean comes first, since
+// the mapping needs it.  Then G replaces F in the fe registers, and eight tile_sums in all reduce
+// the month.  The return vector is read last, once, into registers of its own: with fe and the
+// term being summed that is fcmp_kernel's budget of two row sets and a transient third.
+
+// G of one forecast: three operations, each rounded on its own
+__device__ __forceinline__ double fhor_scale(double f, double m, double base, double g) {
+    const double d = f - m;
+    return base + g * d;
+}
+
+template <int NT, int VPT, class Src>
+__global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_args a) {
+    constexpr int NW = NT / WAVE;
+    constexpr bool FUSED = Src::FUSED;
+    const Src src = Src::make(a);
+    extern __shared__ uint64_t pbuf[];   // the keys of the order statistics
+    __shared__ OrderSh<NW> sh;
+    __shared__ double s_g[FM_MAX_DIST_Q];
+    __shared__ double s_tile[NW * VPT + 1];
+    const int s = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
+    const int nq = a.nq, nrec = FM_FHOR_NREC + nq;
+    const int64_t r0 = a.seg_off[s];
+    int L = (int)(a.seg_off[s + 1] - r0);
+    L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
+    const int last = L - 1;
+    const int64_t so = s + (int64_t)src.j * a.nseg, ro = r0 + (int64_t)src.j * a.src.nrows;
+    const int min_level = a.src.sel_level[src.j];
+
+    // ---- 1. load, set E -------------------------------------------------------------------------
+    double fe[VPT];    // the rows' forecasts F, NaN outside E; from phase 3 on G, then G - mg
+    uint32_t em = 0;   // bit v: row v of this thread is in E
+    if (L > 0) {       // block-uniform
+        if constexpr (FUSED) fused_forecast<VPT>(src, a.nseg, s, so, ro, r0, L, w, lane, fe);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
+            const int idx = (w * VPT + v) * WAVE + lane;
+            const int ci = idx < L ? idx : last;
+            double f;
+            if constexpr (FUSED) f = fe[v];
+            else f = a.forecast[ro + ci];
+            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
+            const bool elig = idx < L && isfinite(f) && lv >= min_level;
+            fe[v] = elig ? f : NAN;
+            em |= elig ? 1u << v : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) fe[v] = NAN;
+    }
+    const int nE = block_sum<NW>((int)__popc(em), sh.iscr);
+    double* rec = a.rec + so * nrec;
+    double* gout = a.scaled_out != nullptr ? a.scaled_out + ro : nullptr;
+
+    // the thread's returns (into x) and its rows of set R, read once, when the registers are free
+    uint32_t rm = 0;   // bit v: row v of this thread is in R
+    auto load_returns = [&](double (&x)[VPT]) {
+        if (L <= 0) return;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = (w * VPT + v) * WAVE + lane;
+            x[v] = a.ret[r0 + (idx < L ? idx : last)];
+            rm |= (((em >> v) & 1u) && isfinite(x[v])) ? 1u << v : 0u;
+        }
+    };
+    double x[VPT];
+    if (nE < a.min_count) {   // block-uniform: the month has no scaled forecast
+        load_returns(x);
+        const int nR = block_sum<NW>((int)__popc(rm), sh.iscr);
+        if (tid == 0) {
+            a.cnt[so * 2] = nE;
+            a.cnt[so * 2 + 1] = nR;
+            a.status[so] = 0u;
+        }
+        if (tid < nrec) rec[tid] = NAN;
+        if (gout != nullptr) {
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) {
+                const int idx = (w * VPT + v) * WAVE + lane;
+                if (idx < L) gout[idx] = NAN;
+            }
+        }
+        return;
+    }
+
+    // ---- 2. the mean of F, then the quantiles of G from F's order statistics -------------------
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fe[v] : 0.0;
+    const double m = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
+    const double g = a.gain, base = a.level_mult * m;
+    if (nq > 0) {   // block-uniform
+        if (tid < nq) {
+            int i, j;
+            double gam;
+            qranks(nE, a.q[tid], 0, i, j, gam);
+            sh.trank[2 * tid] = i;
+            sh.trank[2 * tid + 1] = j;
+            s_g[tid] = gam;
+        }
+        if (tid == 0) {
+            sh.n = 0;
+            sh.over = 0;
+        }
+        order_stat_keys<NT, VPT>(fe, em, nE, 2 * nq, pbuf, sh);
+        if (tid < nq)
+            rec[FM_FHOR_NREC + tid] = qlerp(fhor_scale(kval(sh.okey[2 * tid]), m, base, g),
+                                            fhor_scale(kval(sh.okey[2 * tid + 1]), m, base, g), s_g[tid], 0);
+    }
+
+    // ---- 3. G in place of F; its mean and standard deviation over E ----------------------------
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        fe[v] = ((em >> v) & 1u) ? fhor_scale(fe[v], m, base, g) : NAN;
+        const int idx = (w * VPT + v) * WAVE + lane;
+        if (gout != nullptr && idx < L) gout[idx] = fe[v];
+    }
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fe[v] : 0.0;
+    const double mG = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const double d = fe[v] - mG;
+        x[v] = ((em >> v) & 1u) ? d * d : 0.0;
+    }
+    const double ss = tile_sum<NW, VPT>(x, s_tile, w, lane);
+
+    // ---- 4. the return on G over R ----------------------------------------------------------------
+    double r[VPT];
+    load_returns(r);
+    const int nR = block_sum<NW>((int)__popc(rm), sh.iscr);
+    double pslope = NAN, picept = NAN, pr2 = NAN;
+    if (nR >= 2) {   // block-uniform
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fe[v] : 0.0;
+        const double mg = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? r[v] : 0.0;
+        const double mr = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            fe[v] = fe[v] - mg;
+            r[v] = r[v] - mr;
+        }
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fe[v] * fe[v] : 0.0;
+        const double Sgg = tile_sum<NW, VPT>(x, s_tile, w, lane);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fe[v] * r[v] : 0.0;
+        const double Sgr = tile_sum<NW, VPT>(x, s_tile, w, lane);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? r[v] * r[v] : 0.0;
+        const double Srr = tile_sum<NW, VPT>(x, s_tile, w, lane);
+        pslope = Sgr / Sgg;
+        picept = mr - pslope * mg;
+        pr2 = (Sgr * Sgr) / (Sgg * Srr);
+    }
+    if (tid == 0) {
+        rec[0] = mG;
+        rec[1] = nE > 1 ? sqrt(ss / (double)(nE - 1)) : NAN;
+        rec[2] = pslope;
+        rec[3] = picept;
+        rec[4] = pr2;
+        rec[5] = m;
+        a.cnt[so * 2] = nE;
+        a.cnt[so * 2 + 1] = nR;
+        a.status[so] = 1u;
+    }
+}
+
+template <int NT, int VPT, class Src>
+int launch_fhor(const fm_fhor_args& a, size_t lds, hipStream_t st) {
+    const char* who = "fm_forecast_horizon";
+    if (lds >= 64 * 1024 && raise_dynamic_lds<fhor_kernel<NT, VPT, Src>>(8 * pow2_ceil(NT * VPT), who) != FM_OK) return FM_EHIP;
+    hipLaunchKernelGGL((fhor_kernel<NT, VPT, Src>), dim3(a.nseg, a.src.nsel), dim3(NT), lds, st, a);
+    return check_launch(who);
+}
+
 }  // namespace
 }  // namespace fm
 
@@ -1089,6 +1277,38 @@ extern "C" int fm_forecast_dist(const fm_fdist_args* args, void* stream) {
     return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
         if (vec) return launch_fdist<nt, vpt, VecSrc>(a, lds, st);
         return pl ? launch_fdist<nt, vpt, PanelSrc<true>>(a, lds, st) : launch_fdist<nt, vpt, PanelSrc<false>>(a, lds, st);
+    });
+}
+
+extern "C" int fm_forecast_horizon(const fm_fhor_args* args, void* stream) {
+    using namespace fm;
+    const char* who = "fm_forecast_horizon";
+    FM_REQUIRE(args != nullptr, "%s: null args", who);
+    const fm_fhor_args& a = *args;
+    FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
+    FM_REQUIRE(a.nq >= 0 && a.nq <= FM_MAX_DIST_Q, "%s: nq must be 0..%d", who, FM_MAX_DIST_Q);
+    for (int i = 0; i < a.nq; ++i) {
+        const double lo = i == 0 ? 0.0 : a.q[i - 1];
+        FM_REQUIRE(a.q[i] > lo && a.q[i] < 1.0, "%s: q must be strictly ascending in (0, 1)", who);
+    }
+    FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
+    FM_REQUIRE(isfinite(a.gain) && a.gain > 0.0, "%s: gain must be finite and > 0", who);
+    FM_REQUIRE(isfinite(a.level_mult), "%s: level_mult must be finite", who);
+    if (a.max_seg_len > PORT_MAX_ROWS) {
+        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
+        return FM_ETOOBIG;
+    }
+    const bool vec = a.forecast != nullptr;
+    if (const int rc = check_forecast_src(a.src, a.nseg, who, vec)) return rc;
+    if (a.nseg == 0 || a.src.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
+    FM_REQUIRE(a.ret != nullptr, "%s: ret is needed (the realised return is always a vector)", who);
+    FM_REQUIRE(a.seg_off && a.rec && a.cnt && a.status, "%s: null pointer", who);
+    const bool pl = a.src.hi_plane != nullptr;
+    const size_t lds = port_lds_bytes(a.max_seg_len);
+    const hipStream_t st = (hipStream_t)stream;
+    return with_form(a.max_seg_len, [&](auto nt, auto vpt) {
+        if (vec) return launch_fhor<nt, vpt, VecSrc>(a, lds, st);
+        return pl ? launch_fhor<nt, vpt, PanelSrc<true>>(a, lds, st) : launch_fhor<nt, vpt, PanelSrc<false>>(a, lds, st);
     });
 }
 

@@ -31,6 +31,7 @@ FM_MAX_SORT_K = 30
 FM_MAX_DIST_Q = 8
 FM_MAX_PAIRS = 16
 FM_FCMP_NREC = 7
+FM_FHOR_NREC = 6
 FM_TS_FUSED_MAX_LDS = 128 * 1024
 FM_RANK_AVERAGE, FM_RANK_MIN, FM_RANK_MAX = 0, 1, 2
 FM_RANK_RAW, FM_RANK_PCT, FM_RANK_UNIFORM = 0, 1, 2
@@ -120,7 +121,7 @@ class PortArgs(C.Structure):
 
 
 class ForecastSrc(C.Structure):
-    """fm_forecast_src: the fused forecast FPortArgs, FDistArgs and FCmpArgs embed as ``src``."""
+    """fm_forecast_src: the fused forecast FPortArgs, FDistArgs, FCmpArgs and FHorArgs embed as ``src``."""
     _fields_ = [
         ("cols", _p), ("col_stride", _i64), ("hi_plane", _p), ("lo_plane", _p), ("plane_stride", _i64),
         ("lo", _p), ("hi", _p), ("coef", _p), ("forecast_out", _p), ("nrows", _i64),
@@ -153,6 +154,14 @@ class FCmpArgs(C.Structure):
         ("ret_col", _i32), ("nseg", _i32), ("max_seg_len", _i32), ("min_count", _i32), ("npair", _i32),
         ("pad_fcmp", _i32), ("pair_a", _i32 * FM_MAX_PAIRS), ("pair_b", _i32 * FM_MAX_PAIRS),
         ("pair_level", _i32 * FM_MAX_PAIRS), ("rec", _p), ("cnt", _p), ("status", _p),
+    ]
+
+
+class FHorArgs(C.Structure):
+    _fields_ = [
+        ("src", ForecastSrc), ("forecast", _p), ("ret", _p), ("level", _p), ("seg_off", _p), ("nseg", _i32),
+        ("max_seg_len", _i32), ("min_count", _i32), ("nq", _i32), ("q", _f64 * FM_MAX_DIST_Q),
+        ("level_mult", _f64), ("gain", _f64), ("scaled_out", _p), ("rec", _p), ("cnt", _p), ("status", _p),
     ]
 
 
@@ -219,6 +228,7 @@ _SIGS = {
     "fm_lagged_coef": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p, _p]),
     "fm_forecast_dist": (_i32, [C.POINTER(FDistArgs), _p]),
     "fm_forecast_compare": (_i32, [C.POINTER(FCmpArgs), _p]),
+    "fm_forecast_horizon": (_i32, [C.POINTER(FHorArgs), _p]),
     "fm_rank_transform": (_i32, [C.POINTER(RankArgs), _p]),
     "fm_month_links": (_i32, [C.POINTER(LinksArgs), _p]),
     "fm_horizon_return": (_i32, [C.POINTER(HorizonArgs), _p]),
@@ -239,7 +249,8 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_universe_args": UniverseArgs, "fm_ts_args": TsArgs, "fm_chars_args": CharsArgs,
             "fm_port_args": PortArgs, "fm_rank_args": RankArgs, "fm_forecast_src": ForecastSrc,
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs,
-            "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs}
+            "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
+            "fm_fhor_args": FHorArgs}
 
 _lib = None
 

@@ -1716,6 +1716,136 @@ def forecast_compare_summary(c: ForecastCompare, nw_lags=4):
     return ts_summary(c.rec, k, T * k, ix, T, S, k, nw_lags)
 
 
+@dataclass
+class ForecastHorizon:
+    rec: torch.Tensor      # [nsel, T, 6+nq] float64: mean and sd (ddof 1) of the scaled forecast G; slope, intercept
+    #                        and R2 of the k-month return on G; the mean of the monthly forecast; G's nq quantiles
+    cnt: torch.Tensor      # [nsel, T, 2] int32: eligible rows; those with a k-month return as well
+    status: torch.Tensor   # [nsel, T] int32: 1 = the month has at least min_count eligible rows
+    scaled: Optional[torch.Tensor] = None     # [nsel, rows] float64 G (on request; NaN: the row is not eligible)
+    forecast: Optional[torch.Tensor] = None   # [nsel, rows] float64 (forecast_horizon, on request)
+
+
+def extrapolation_gain(k, decay):
+    """g = 1 + decay + ... + decay^(k-1) in double, terms added in that order: the factor that
+    scales a monthly forecast's deviation from the cross-sectional mean to k months when it decays
+    geometrically (the paper's Section 4: decay 0.9; decay 1 gives k exactly)."""
+    g, p = 1.0, 1.0
+    for _ in range(int(k) - 1):
+        p = p * float(decay)
+        g = g + p
+    return g
+
+
+def _horizon_plan(who, nsel, T, n, q, min_count, level_mult, gain, scaled_out, forecast_out, out, dev):
+    """What the two forecast-horizon entry points share: the ``ForecastHorizon`` to fill (``out``
+    checked, else allocated) and ``fill(a, j0)``, which sets the fields of an argument struct
+    outside its ``src`` for the sorts from j0."""
+    qs = [float(v) for v in q]
+    nq = min(len(qs), L.FM_MAX_DIST_Q)   # output shapes of a call the library will refuse
+    shapes = dict(rec=((nsel, T, L.FM_FHOR_NREC + nq), torch.float64), cnt=((nsel, T, 2), torch.int32),
+                  status=((nsel, T), torch.int32))
+    if scaled_out:
+        shapes["scaled"] = ((nsel, n), torch.float64)
+    if forecast_out:
+        shapes["forecast"] = ((nsel, n), torch.float64)
+    if out is None:
+        out = ForecastHorizon(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    for k, (sh, dt) in shapes.items():
+        t = getattr(out, k)
+        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+
+    def fill(a, j0):
+        a.nq, a.min_count, a.nseg = len(qs), int(min_count), T
+        a.level_mult, a.gain = float(level_mult), float(gain)
+        for i, v in enumerate(qs[:L.FM_MAX_DIST_Q]):
+            a.q[i] = v
+        if nsel:
+            a.rec, a.cnt, a.status = out.rec[j0:].data_ptr(), out.cnt[j0:].data_ptr(), out.status[j0:].data_ptr()
+            a.scaled_out = out.scaled[j0:].data_ptr() if scaled_out else None
+        return a
+
+    return out, fill
+
+
+def forecast_horizon(panel: DevicePanel, coef, sel, ret, level_mult, gain, cuts: Cuts = None, level=None,
+                     q=(0.1, 0.9), min_count=1, scaled_out=False, forecast_out=False, out: "ForecastHorizon" = None):
+    """A17 (the paper's Section 4, second approach): for every sort j of ``sel`` = [(xs, min_level), ...]
+    and every month, the monthly forecast of ``forecast_dist`` (``coef`` [nsel, T, >= K+1], ``cuts``,
+    ``level`` as there; bit for bit, computed in the kernel's load phase) is scaled around its
+    cross-sectional mean m to G = ``level_mult`` * m + ``gain`` * (F - m); the month's mean, ddof-1
+    standard deviation and ``q`` quantiles of G, and the regression of ``ret`` -- a float64 [rows]
+    device vector, e.g. ``horizon_return``'s k-month return -- on G (slope, intercept, R2) follow
+    (fm_forecast_horizon; the definition is in fm_hip.h).  With ``level_mult`` = k and ``gain`` =
+    ``extrapolation_gain(k, 0.9)`` G is the paper's extrapolated k-month forecast.  One launch per
+    FM_MAX_SORTS sorts.  Returns ``ForecastHorizon``; ``scaled_out``: also G [nsel, rows];
+    ``forecast_out``: also the monthly forecasts [nsel, rows]; ``out``: a ``ForecastHorizon`` of that
+    shape to write into (else allocated)."""
+    src, sel, coef, lo, hi = _forecast_plan("forecast_horizon", panel, coef, sel, cuts)
+    dev = src.device
+    n, T, nsel = panel.nrows, panel.nseg, len(sel)
+    ret = _row_vector(ret, torch.float64, n, dev, "ret")
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    out, fill = _horizon_plan("forecast_horizon", nsel, T, n, q, min_count, level_mult, gain, scaled_out,
+                              forecast_out, out, dev)
+    for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
+        a = fill(L.FHorArgs(), j0)
+        _fill_forecast_src(a.src, n, sel[j0:j0 + L.FM_MAX_SORTS], j0, src, coef, lo, hi,
+                           out.forecast if forecast_out else None)
+        a.ret, a.level, a.seg_off, a.max_seg_len = _ptr(ret), _ptr(level), panel.seg_off.data_ptr(), panel.max_seg_len
+        _kcall("fm_forecast_horizon", "fm_forecast_horizon", L.C.byref(a), _stream())
+        _remember("fm_forecast_horizon", "fm_forecast_horizon", a, src, panel.planes, panel.seg_off, coef, lo, hi,
+                  ret, level, out)
+    return out
+
+
+def forecast_horizon_vector(seg_off, forecast, ret, level_mult, gain, level=None, min_level=0, q=(0.1, 0.9),
+                            min_count=1, max_seg_len=None, scaled_out=False):
+    """A17 on forecast vectors the caller holds: ``forecast`` float64 [rows] or [nsel, rows] and the
+    realised return ``ret`` float64 [rows] on the device, months ``seg_off`` int64 [T+1]; eligible rows
+    are the finite forecasts with ``level`` >= ``min_level`` (one value, or one per vector).  Returns
+    ``ForecastHorizon`` with a leading [nsel] dimension (1 for a 1-D forecast).  ``max_seg_len``: the
+    longest month if the caller knows it (otherwise read from ``seg_off``, one host sync)."""
+    dev = forecast.device
+    if forecast.dtype != torch.float64 or forecast.dim() not in (1, 2):
+        raise ValueError("forecast_horizon_vector: forecast must be a float64 [rows] or [nsel, rows] tensor")
+    forecast = forecast.view(1, -1) if forecast.dim() == 1 else forecast
+    forecast = forecast.contiguous()
+    nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("forecast_horizon_vector: seg_off must be an int64 [T+1] tensor on the forecast's device")
+    seg_off = seg_off.contiguous()
+    T = int(seg_off.shape[0]) - 1
+    ret = _row_vector(ret, torch.float64, n, dev, "ret")
+    level = _row_vector(level, torch.uint8, n, dev, "level")
+    levels = [int(min_level)] * nsel if np.ndim(min_level) == 0 else [int(v) for v in min_level]
+    if len(levels) != nsel:
+        raise ValueError(f"forecast_horizon_vector: min_level must be one value or {nsel}")
+    if max_seg_len is None:
+        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    out, fill = _horizon_plan("forecast_horizon_vector", nsel, T, n, q, min_count, level_mult, gain, scaled_out,
+                              False, None, dev)
+    for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
+        a = fill(L.FHorArgs(), j0)
+        _fill_forecast_src(a.src, n, [((), lv) for lv in levels[j0:j0 + L.FM_MAX_SORTS]])
+        a.forecast = forecast[j0:].data_ptr() if nsel else None
+        a.ret, a.level, a.seg_off, a.max_seg_len = _ptr(ret), _ptr(level), seg_off.data_ptr(), int(max_seg_len)
+        _kcall("fm_forecast_horizon", "fm_forecast_horizon", L.C.byref(a), _stream())
+        _remember("fm_forecast_horizon", "fm_forecast_horizon", a, seg_off, forecast, ret, level, out)
+    return out
+
+
+def forecast_horizon_summary(h: ForecastHorizon, nw_lags=4):
+    """FM mean, Newey-West s.e., t and nobs of the 6 + nq monthly series of ``h.rec`` over the months
+    with status 1, NaN entries dropped per series (a constant forecast, a month without k-month
+    returns, the sd of a one-row month) -> ``Summary`` with [nsel, 6+nq] tensors: every sort is one
+    problem of the two launches ``forecast_compare_summary`` issues."""
+    S, T, k = h.rec.shape
+    ix = ts_compact(h.status, 1, T, T, S)
+    return ts_summary(h.rec, k, T * k, ix, T, S, k, nw_lags)
+
+
 # fm_rank_transform's month limit (FM_RANK_MAX_ROWS): up to 16,384 rows one workgroup per (month,
 # column) sorts the month's keys in LDS; a longer month is ranked in parts of 16,384 rows, at a cost
 # quadratic in the part count, so four parts are the limit
@@ -1887,6 +2017,19 @@ def horizon_panel(panel: DevicePanel, h, ret="retx", name=None):
                       row_origin=panel.row_origin, ids=panel.ids, month_index=panel.month_index)
     _share_links(panel, res)
     return res
+
+
+def column_vector(panel: DevicePanel, col):
+    """Column ``col`` (name or index) as a contiguous float64 [rows] device vector: a view of the FP64
+    columns, or for a planes-only panel a merge of that column's two planes alone (fm_merge_planes)."""
+    i = panel.col(col) if isinstance(col, str) else int(col)
+    n = panel.nrows
+    if panel.cols is not None:
+        return panel.cols[i, :n]
+    out = torch.empty(n, dtype=torch.float64, device=panel.planes.device)
+    _kcall("fm_merge_planes", "fm_merge_planes", panel.planes[0, i].data_ptr(), panel.planes[1, i].data_ptr(),
+           panel.planes.stride(1), 1, n, out.data_ptr(), n, _stream())
+    return out
 
 
 def segment_moments(panel: DevicePanel, level=None, min_level=0, finite_only=True, cols=None):

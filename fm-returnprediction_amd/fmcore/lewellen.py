@@ -14,6 +14,9 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
  -> optionally (``PipelineConfig.forecast_compare``) per universe and pair of Table-2 models the
     monthly regression of one model's forecast on the other's and of returns on its residual
     (paper Table 4, build-defined A15), likewise in one launch
+With ``PipelineConfig.extrapolate`` = k the monthly run also scales every month's forecasts to k
+months and regresses the compounded k-month return on them (paper Section 4's second approach, the
+lower panels of Tables 9a and 9b; build-defined A17), in one more launch.
 With ``PipelineConfig.horizon`` = k > 1 the dependent variable of all of this is the compounded
 k-month return (paper Section 4, Tables 8 and 9; build-defined A16), a column built once at ingest.
 All stages are libfm_hip kernels; the panel is read from HBM twice (cuts, Gram).
@@ -97,6 +100,19 @@ class PipelineConfig:
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
     forecast_dist: bool = field(default=False, kw_only=True)
     forecast_dist_q: Sequence[float] = field(default=(0.1, 0.9), kw_only=True)
+    # A17 (paper Section 4, second approach): ``extrapolate`` = k in 2..engine.MAX_HORIZON keeps the
+    # monthly regressions and forecasts and, in one more launch, scales every month's forecasts to k
+    # months, G = k * mean + (1 + rho + ... + rho^(k-1)) (F - mean) with rho = ``extrapolate_decay`` in
+    # (0, 1] (the paper rounds the forecasts' autocorrelation to 0.9; 1 = plain k-fold scaling) and the
+    # mean taken over the problem's universe, then regresses the compounded k-month return on G
+    # (engine.forecast_horizon), over the same problems and universes and under the same two rules as
+    # ``portfolios``.  The alternative to ``horizon`` > 1, so the two exclude each other; the panel
+    # needs firm ids.  ``extrapolate_nw_lags`` (None: ``nw_lags``) is the caller's choice, as for
+    # ``horizon``: the paper uses 10 lags for 6 months and 16 for 12.  None = no launch more.
+    extrapolate: Optional[int] = field(default=None, kw_only=True)
+    extrapolate_decay: float = field(default=0.9, kw_only=True)
+    extrapolate_q: Sequence[float] = field(default=(0.1, 0.9), kw_only=True)
+    extrapolate_nw_lags: Optional[int] = field(default=None, kw_only=True)
     # A16 (paper Section 4, Tables 8 and 9): the dependent variable of every stage is the compounded
     # ``horizon``-month return y_t .. y_{t+horizon-1} (column f"{y}_{horizon}m", built once by
     # engine.horizon_panel when the panel lacks it; the panel then needs firm ids).  1 = monthly
@@ -136,6 +152,10 @@ class PipelineResult:
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
     y_col: str = "retx"                                   # the dependent column (cfg.horizon > 1: f"{y}_{h}m")
+    # cfg.extrapolate (in front of the comparison's fields, which tests pin as the trailing three)
+    extrapolated: Optional[E.ForecastHorizon] = None      # [nsort, T, 6+nq], [nsort, T, 2], [nsort, T]
+    extrapolated_summary: Optional[E.Summary] = None      # [nsort, 6+nq]
+    extrapolated_problems: Optional[List[int]] = None     # the problem index (res.problems) of each sort
     forecast_compare: Optional[E.ForecastCompare] = None     # cfg.forecast_compare: [npair, T, 7], [npair, T, 2], [npair, T]
     forecast_compare_summary: Optional[E.Summary] = None     # [npair, 7]
     forecast_compare_pairs: Optional[List[tuple]] = None     # (problem_a, problem_b) of each pair: b regressed on a
@@ -253,6 +273,20 @@ def check_horizon(cfg: PipelineConfig):
                          "of month t - lag would be fitted on returns that end after month t)")
 
 
+def check_extrapolate(cfg: PipelineConfig):
+    """The rules of ``PipelineConfig.extrapolate`` that need no panel (no device work)."""
+    k, rho = cfg.extrapolate, cfg.extrapolate_decay
+    if k is None:
+        return
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or k < 2 or k > E.MAX_HORIZON:
+        raise ValueError(f"PipelineConfig: extrapolate must be an integer in 2..{E.MAX_HORIZON}, got {k!r}")
+    if isinstance(rho, bool) or not isinstance(rho, (int, float, np.integer, np.floating)) or not 0.0 < rho <= 1.0:
+        raise ValueError(f"PipelineConfig: extrapolate_decay must lie in (0, 1], got {rho!r}")
+    if cfg.horizon != 1:
+        raise ValueError(f"PipelineConfig: extrapolate={k} excludes horizon={cfg.horizon} (monthly forecasts scaled "
+                         "to k months and regressions refitted on k-month returns are alternatives)")
+
+
 def horizon_column(panel: E.DevicePanel, cfg: PipelineConfig, y="retx"):
     """The panel and dependent column of a run: (panel, y) at horizon 1; else the column
     f"{y}_{h}m", appended by engine.horizon_panel when the panel lacks it."""
@@ -271,13 +305,16 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     cfg = cfg or PipelineConfig()
     model_cols = model_cols or table2_models()
     check_horizon(cfg)
+    check_extrapolate(cfg)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
-                     (cfg.forecast_compare, "forecast_compare")):
+                     (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
         if on and cfg.standardize:
             raise ValueError(f"PipelineConfig: {what} excludes standardize (coefficients on z-scores "
                              "need the moment tables)")
         if on and not cfg.forecasts:
             raise ValueError(f"PipelineConfig: {what} needs forecasts=True (the lagged rolling coefficients)")
+    if cfg.extrapolate is not None and (panel.ids is None or panel.month_index is None):
+        raise ValueError("PipelineConfig: extrapolate needs a panel with firm ids (build it with ids=...)")
     panel, y = horizon_column(panel, cfg, y)
     res, names, cuts, level, bp, gpanel, models = _local_stage(panel, cfg, model_cols, y)
     ix, summ, roll, pred, pst = time_series_stage(res, cfg)
@@ -287,7 +324,8 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     ports = port_summ = port_probs = None
     dist = dist_summ = dist_probs = None
     comp = comp_summ = comp_pairs = None
-    if cfg.portfolios is not None or cfg.forecast_dist or cfg.forecast_compare:
+    extr = extr_summ = extr_probs = None
+    if cfg.portfolios is not None or cfg.forecast_dist or cfg.forecast_compare or cfg.extrapolate is not None:
         # Tables 5, 3 and 4: every Table-2 problem's forecast, sorted, summarized or compared in one launch each
         # on the panel the Gram read, with the pipeline's cuts and the coefficient rows the
         # predictive stage read
@@ -306,6 +344,16 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
         comp_pairs = [(probs[a], probs[b]) for a, b, _ in pairs]
         comp = E.forecast_compare(gpanel, coef, sel, pairs, cuts=cuts, ret=gpanel.col(y), level=level)
         comp_summ = E.forecast_compare_summary(comp, cfg.nw_lags)
+    if cfg.extrapolate is not None:
+        # the monthly forecasts scaled to k months, against the k-month return compounded over the firm links
+        k = int(cfg.extrapolate)
+        extr_probs = probs
+        ret_k = E.horizon_return(panel.seg_off, E.column_vector(panel, y), E.month_links(panel, 1), k)
+        extr = E.forecast_horizon(gpanel, coef, sel, ret_k, level_mult=k,
+                                  gain=E.extrapolation_gain(k, cfg.extrapolate_decay), cuts=cuts, level=level,
+                                  q=cfg.extrapolate_q)
+        extr_summ = E.forecast_horizon_summary(
+            extr, cfg.nw_lags if cfg.extrapolate_nw_lags is None else cfg.extrapolate_nw_lags)
     if cfg.portfolios is not None:
         port_probs = probs
         ports = E.forecast_portfolio_sort(gpanel, coef, sel, cuts=cuts, ret=gpanel.col(y), weight=gpanel.me,
@@ -318,7 +366,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                           portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
                           forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
                           forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
-                          y_col=y)
+                          y_col=y, extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

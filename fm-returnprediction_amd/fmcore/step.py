@@ -34,6 +34,9 @@ class ShardedStep:
             # a shard's last horizon - 1 months need the next shard's rows (no halo exchange)
             raise ValueError("ShardedStep: cfg.horizon must be 1 (multi-month returns need the following "
                              "months' rows, which a month shard does not hold)")
+        if cfg.extrapolate is not None:
+            raise ValueError("ShardedStep: cfg.extrapolate must be None (k-month returns need the following "
+                             "months' rows, which a month shard does not hold)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols
         self.world, self.rank, self.group = world, rank, group
         self.seg_lo = seg_lo

@@ -766,6 +766,63 @@ def _dist_frames(status, rec, cnt, mean, tstat, nobs, months, q, date_col="mthca
     return monthly, summary
 
 
+EXTRAPOLATION_COLUMNS = ["mean", "std", "slope", "intercept", "r2", "mean_1m"]
+
+
+def forecast_extrapolation(df: pd.DataFrame, forecast, horizon: int, decay: float = 0.9, return_col: str = "retx",
+                           universe: str = None, q=(0.1, 0.9), date_col: str = "mthcaldt", id_col: str = "permno",
+                           nw_lags: int = 4):
+    """A17 (the paper's Section 4, second approach): each month, the monthly ``forecast`` scaled to
+    ``horizon`` = k months, G = k * m + (1 + decay + ... + decay^(k-1)) (forecast - m) with m the
+    month's mean forecast over the rows with a finite forecast; G's cross-sectional mean, standard
+    deviation (ddof 1) and np.quantile levels ``q``; and the compounded k-month ``return_col`` (built
+    over the same firm links as ``horizon_returns``) regressed on G over the rows that have one
+    (slope, intercept, r2), on the device (fm_forecast_horizon).  ``universe`` in {None,
+    "all_but_tiny", "large"} keeps the rows of that get_subsets universe (from ``me`` and
+    ``primaryexch``).  ``date_col`` and ``id_col`` as ``horizon_returns`` needs them.
+    Returns (monthly, summary): ``monthly`` is indexed by month with columns mean, std, slope,
+    intercept, r2, mean_1m (m), one per level (p10, p90), n (rows with a forecast) and n_ret (those
+    with a k-month return), months without an eligible row absent; ``summary`` is indexed by those
+    columns (not n, n_ret) with columns mean / se / tstat / nobs: the time-series average, its
+    Newey-West(nw_lags) standard error and t-statistic."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    k = int(horizon)
+    if k < 1 or k > _E.MAX_HORIZON:
+        raise ValueError(f"forecast_extrapolation: horizon must be 1..{_E.MAX_HORIZON}, got {horizon!r}")
+    if not 0.0 < float(decay) <= 1.0:
+        raise ValueError(f"forecast_extrapolation: decay must lie in (0, 1], got {decay!r}")
+    f = np.asarray(forecast, dtype=np.float64)
+    if f.shape != (len(df),):
+        raise ValueError("forecast must hold one value per row of df")
+    ids = _firm_ids(df[id_col], df[date_col])
+    if ids is None:
+        raise ValueError(f"forecast_extrapolation: {id_col!r} must hold whole-number firm ids and {date_col!r} "
+                         "datetime64 or integer months")
+    dates = df[date_col].to_numpy()
+    order = np.lexsort((ids, dates))
+    d = df.iloc[order]
+    me = _api.as_f64(d["me"]) if universe is not None else None
+    nyse = (d["primaryexch"] == "N").to_numpy().astype(np.uint8) if universe is not None else None
+    panel = _E.panel_from_arrays([f[order], _api.as_f64(d[return_col])], ["forecast", return_col], dates[order],
+                                 me=me, nyse=nyse, ids=ids[order])
+    level = _E.universe(panel)[2] if universe is not None else None
+    ret_k = _E.horizon_return(panel.seg_off, panel.cols[1], _E.month_links(panel, 1), k)
+    h = _E.forecast_horizon_vector(panel.seg_off, panel.cols[0], ret_k, float(k), _E.extrapolation_gain(k, decay),
+                                   level=level, min_level=_UNIVERSE_LEVEL[universe], q=q,
+                                   max_seg_len=panel.max_seg_len)
+    s = _E.forecast_horizon_summary(h, nw_lags)
+    cols = EXTRAPOLATION_COLUMNS + _dist_columns(q)
+    ok = h.status[0].cpu().numpy() == 1
+    monthly = pd.DataFrame(h.rec[0].cpu().numpy()[ok], index=pd.Index(np.asarray(panel.months)[ok], name=date_col),
+                           columns=cols)
+    cnt = h.cnt[0].cpu().numpy()[ok].astype(np.int64)
+    monthly["n"], monthly["n_ret"] = cnt[:, 0], cnt[:, 1]
+    summary = pd.DataFrame({c: getattr(s, c)[0].cpu().numpy() for c in ("mean", "se", "tstat", "nobs")},
+                           index=pd.Index(cols, name="statistic"))
+    return monthly, summary
+
+
 COMPARISON_COLUMNS = ["corr", "slope", "intercept", "res_std", "pred_slope", "pred_intercept", "pred_r2"]
 
 
@@ -914,6 +971,32 @@ def build_table_3(crsp_comp: pd.DataFrame, variables_dict: dict = None, q=(0.1, 
         prob = out.res.problems[k]
         keys.append((out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level]))
         rows.append(list(dmean[j]) + [pmean[k, 0], pse[k, 0], pt[k, 0], pmean[k, 1]])
+    return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(keys, names=["model", "universe"]),
+                        columns=["Avg", "Std"] + _dist_columns(q) + ["Slope", "S.E.", "t-stat", "R2"])
+
+
+def build_table_3_extrapolated(crsp_comp: pd.DataFrame, horizon: int, variables_dict: dict = None, decay: float = 0.9,
+                               q=(0.1, 0.9), **cfg):
+    """The lower panels of the paper's Tables 9a / 9b (horizon 6 / 12) from ONE device pipeline run
+    (build-defined A17; no reference line): build_table_3's frame for the monthly forecasts
+    extrapolated to ``horizon`` months, F_ik = k * mean + (1 + decay + ... + decay^(k-1)) (F_i1 - mean)
+    with the mean taken over the universe each month -- the time-series averages of each month's
+    cross-sectional mean (``Avg``), standard deviation (``Std``) and ``q`` quantiles of F_ik, and the
+    Fama-MacBeth slope of the compounded ``horizon``-month return on F_ik with its Newey-West
+    standard error, t-statistic and the average R2.  The regressions and forecasts stay monthly
+    (``PipelineConfig(extrapolate=horizon)``).  ``cfg``: further PipelineConfig fields;
+    ``extrapolate_nw_lags`` is the caller's choice (the paper uses 10 lags for 6 and 16 for 12 months;
+    the default is ``nw_lags``).  Returns a DataFrame indexed by (model, universe)."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    pcfg = _LW.PipelineConfig(**dict(cfg, extrapolate=horizon, extrapolate_decay=decay, extrapolate_q=tuple(q)))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    s = out.extrapolated_summary
+    mean, se, t = s.mean.cpu().numpy(), s.se.cpu().numpy(), s.tstat.cpu().numpy()
+    keys, rows = [], []
+    for j, k in enumerate(out.extrapolated_problems):
+        prob = out.res.problems[k]
+        keys.append((out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level]))
+        rows.append([mean[j, 0], mean[j, 1]] + list(mean[j, _L.FM_FHOR_NREC:]) + [mean[j, 2], se[j, 2], t[j, 2], mean[j, 4]])
     return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(keys, names=["model", "universe"]),
                         columns=["Avg", "Std"] + _dist_columns(q) + ["Slope", "S.E.", "t-stat", "R2"])
 

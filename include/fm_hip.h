@@ -60,6 +60,10 @@
  *                      the compounded k-month return (1 + r_t) ... (1 + r_{t+k-1}) - 1 (the
  *                      dependent variable of the paper's Tables 8 and 9, "longer-horizon
  *                      expected returns"); no reference line
+ *   fm_forecast_horizon <- build-defined extension A17: per month, the monthly forecasts scaled
+ *                      to k months (geometric decay toward the cross-sectional mean) and the
+ *                      k-month return regressed on them (the paper's second long-horizon
+ *                      approach, lower panels of Tables 9a and 9b); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -215,7 +219,7 @@ const char* fm_last_error(void);
 #define FM_ARG_STRUCTS(X)                                                                     \
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
-    X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args)
+    X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -467,7 +471,7 @@ int fm_portfolio_sort(const fm_port_args* args, void* stream);
 
 /* fm_forecast_src: the fused forecast -- nsel forecasts of one panel, each row's value computed
  * in the consuming kernel's load phase from the panel's own layout instead of read from a vector.
- * It is embedded as the field `src` of fm_fport_args, fm_fdist_args and fm_fcmp_args; nseg, seg_off and
+ * It is embedded as the field `src` of fm_fport_args, fm_fdist_args, fm_fcmp_args and fm_fhor_args; nseg, seg_off and
  * max_seg_len are the embedding struct's.  Exactly one predictor source: FP64 columns (cols,
  * col_stride) or the split planes (hi_plane, lo_plane, plane_stride); both or neither: FM_EINVAL.
  * For sort j (K = sel_k[j] in 1..FM_MAX_SORT_K predictors, panel columns sel_cols[j][0..K) in
@@ -656,6 +660,74 @@ typedef struct fm_fcmp_args {
 } fm_fcmp_args;
 
 int fm_forecast_compare(const fm_fcmp_args* args, void* stream);
+
+/* fm_forecast_horizon: per month, nsel monthly expected-return forecasts scaled to a longer
+ * horizon and held against the return realised over it, in one launch, grid (month, sort)
+ * (build-defined extension A17; no reference line; the paper's Section 4, second approach, the
+ * lower panels of Tables 9a and 9b: F_ik = k * mean + (1 + .9 + ... + .9^(k-1)) (F_i1 - mean), the
+ * monthly forecast extrapolated to k months under a geometric decay toward the cross-sectional mean,
+ * then the k-month return regressed on it).  Rows sorted by (month, permno), months
+ * seg_off[nseg+1] of at most 16,384 rows (its siblings' limit and their three workgroup shapes;
+ * longer: FM_ETOOBIG before any launch, outputs untouched).  Exactly one forecast source, anything
+ * else FM_EINVAL:
+ *   forecast [nsel][nrows]: the caller's vectors (of `src` only nsel, nrows and sel_level are
+ *   then read; its cols, planes and forecast_out must be NULL), or
+ *   the panel of `src` (fm_forecast_src above): sort j's forecast is its F, fm_forecast_dist's bit
+ *   for bit; src.forecast_out, if set, receives every row's F.
+ * The realised return is always the vector ret [rows] (fm_horizon_return's output), whatever the
+ * forecast's source.  With a = level_mult (finite) and g = gain (finite, > 0), per (sort j, month
+ * t), all outputs with a leading [nsel] dimension:
+ *   set E: the rows with F finite and level >= sel_level[j] (level NULL: every row);
+ *   set R: the rows of E with a finite ret;
+ *   cnt[0] = nE, cnt[1] = nR;
+ *   nE < min_count: status = 0, rec[0..6+nq) NaN and the month's rows of scaled_out NaN;
+ *   otherwise status = 1 and
+ *   m = sum(F over E) / nE: fm_forecast_dist's rec[0] on the same input, bit for bit;
+ *   the scaled forecast of a row of E is G = a * m + g * (F - m), three operations rounded one by
+ *   one: base = a * m; d = F - m; G = base + g * d.  Rows outside E have G = NaN.  scaled_out, if
+ *   set, receives every row's G;
+ *   rec[0] = sum(G over E) / nE;
+ *   rec[1] = the ddof-1 standard deviation of G over E, two passes:
+ *            sqrt(sum((G - rec[0])^2) / (nE - 1)), NaN when nE == 1;
+ *   rec[5] = m;
+ *   rec[6+i] = numpy 'linear' quantile q[i] of G over E: G is non-decreasing in F, so the two
+ *            neighbouring order statistics of F (exact, fm_forecast_dist's) are mapped through the
+ *            three operations above and interpolated as there;
+ *   over R (nR < 2: rec[2..5) NaN): mg = sum(G) / nR, mr = sum(ret) / nR,
+ *   Sgg = sum((G - mg)^2), Sgr = sum((G - mg) * (ret - mr)), Srr = sum((ret - mr)^2);
+ *   rec[2] = the predictive slope Sgr / Sgg;
+ *   rec[3] = its intercept mr - rec[2] * mg;
+ *   rec[4] = its R2 (Sgr * Sgr) / (Sgg * Srr).
+ * Degenerate months have no special cases, IEEE arithmetic decides them, as in
+ * fm_forecast_compare: a constant forecast gives a NaN slope.  Every product, sum and quotient
+ * above is rounded on its own, in the order written, and each of the eight sums runs in
+ * fm_forecast_dist's fixed order (tiles of 64 rows in row order, rows outside the set or past the
+ * month's end as +0.0, the wave butterfly, lane l adding the tile sums l, l + 64, ... from +0.0,
+ * the butterfly again).  So a month's bits depend on that month's rows alone: not on the source,
+ * the panel's layout, the grid, the other months, the other sorts or max_seg_len; two calls, or a
+ * month-sharded call, give the same bits.  nsel == 0 or nseg == 0 is a valid empty call.
+ * Zero-initialize the struct (it grows at the end). */
+#define FM_FHOR_NREC 6
+typedef struct fm_fhor_args {
+    fm_forecast_src src;
+    const double* forecast;      /* [nsel][nrows] forecast vectors, or NULL (the panel of src) */
+    const double* ret;           /* [rows] the realised k-month return */
+    const uint8_t* level;        /* [rows] universe level or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int32_t nseg;
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t min_count;           /* >= 1 */
+    int32_t nq;                  /* 0 .. FM_MAX_DIST_Q */
+    double q[FM_MAX_DIST_Q];     /* [nq] levels, strictly ascending in (0, 1) */
+    double level_mult;           /* a: the multiple of the month's mean forecast; finite */
+    double gain;                 /* g: the factor on the deviation from it; finite, > 0 */
+    double* scaled_out;          /* [nsel][nrows] or NULL */
+    double* rec;                 /* [nsel][nseg][FM_FHOR_NREC + nq] */
+    int32_t* cnt;                /* [nsel][nseg][2] */
+    uint32_t* status;            /* [nsel][nseg] */
+} fm_fhor_args;
+
+int fm_forecast_horizon(const fm_fhor_args* args, void* stream);
 
 /* fm_rank_transform: every chosen column's cross-sectional rank within its month (build-defined
  * extension A13; no reference line).  It is pandas' groupby(month)[x].rank(method, pct) and is

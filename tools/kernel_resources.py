@@ -15,7 +15,7 @@ CS = os.path.join(ROOT, "fm-returnprediction_amd", "csrc")
 HOT = ("select_pair_hk_kernelILi40", "select_pair_kernelILi40", "select_fixup_universe_kernelILi20",
        "select_fixup_kernelILi20", "select_long_hk_kernelILi40", "universe_kernelILi20",
        "gram_kernelILi1ELi15ELi3ELb1", "gram_kernelILi1ELi15ELi3ELb0", "solve16_kernel", "ts_fused_kernel",
-       "rolling_std_kernel", "firm_chars_kernel", "split_planes_kernel", "port_kernelILi", "fdist_kernelILi", "fcmp_kernelILi", "rank_kernelILi",
+       "rolling_std_kernel", "firm_chars_kernel", "split_planes_kernel", "port_kernelILi", "fdist_kernelILi", "fcmp_kernelILi", "fhor_kernelILi", "rank_kernelILi",
        "rank_long_kernel")
 
 
