@@ -134,6 +134,12 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
     return ((uint64_t)hi << 32) | lo;
 }
+// 64-bit readfirstlane: a value the caller knows to be wave-uniform, into SGPRs
+__device__ __forceinline__ uint64_t readfirstlane_u64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
 
 // compile-time loop: f(std::integral_constant<int, i>) for i in [B, E)
 template <int B, int E, typename F>

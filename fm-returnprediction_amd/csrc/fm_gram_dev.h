@@ -19,8 +19,14 @@
 
 #include "fm_common.h"
 
+#ifndef FM_GRAM_CLIP_BW
+#define FM_GRAM_CLIP_BW 4
+#endif
+
 namespace fm {
 namespace {
+
+constexpr int CLIP_BW = FM_GRAM_CLIP_BW;   // month parameters read per batch of the clip (run)
 
 // nn = 2 * nn + (x is not NaN): one compare + one add-with-carry
 __device__ __forceinline__ uint32_t push_valid(uint32_t nn, double x) {
@@ -228,15 +234,31 @@ struct GramWave {
             if (valid) {
                 double* dst = wt + dest * RS;
                 dst[0] = 1.0;
-                if (scaled) {
+                // The month parameters are read in batches of CLIP_BW columns per kind: the
+                // batch's LDS reads in flight together, then its arithmetic in place on xv
+                // (dead after this).  Read at the point of use, every parameter was its own
+                // dependent LDS round trip (22 waits per tile for 15 columns).  Per element
+                // the operations and their order are max, min, - shift (, * inv_scale).
+                constexpr int NC = ZW - 1;
+                auto sweep = [&](int kind, auto op) {
 #pragma unroll
-                    for (int c = 0; c < ZW - 1; ++c)
-                        dst[1 + c] = (hw_min(hw_max(xv[c], prm[0][c]), prm[1][c]) - prm[2][c]) * prm[3][c];
-                } else {
+                    for (int c0 = 0; c0 < NC; c0 += CLIP_BW) {
+                        double p[CLIP_BW];
 #pragma unroll
-                    for (int c = 0; c < ZW - 1; ++c)
-                        dst[1 + c] = hw_min(hw_max(xv[c], prm[0][c]), prm[1][c]) - prm[2][c];
-                }
+                        for (int i = 0; i < CLIP_BW; ++i) p[i] = prm[kind][c0 + i < NC ? c0 + i : NC - 1];
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = 0; i < CLIP_BW; ++i)
+                            if (c0 + i < NC) xv[c0 + i] = op(xv[c0 + i], p[i]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+                sweep(0, [](double x, double p) { return hw_max(x, p); });
+                sweep(1, [](double x, double p) { return hw_min(x, p); });
+                sweep(2, [](double x, double p) { return x - p; });
+                if (scaled) sweep(3, [](double x, double p) { return x * p; });
+#pragma unroll
+                for (int c = 0; c < NC; ++c) dst[1 + c] = xv[c];
             }
             // this tile's values are consumed: the next tile's loads fly during the MFMAs
             if (tnext < ntile) load_row(tnext);

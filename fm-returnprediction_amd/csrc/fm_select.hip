@@ -1485,9 +1485,9 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
     uint32_t xk[VPH];
     // the unit's raw high words: one buffer descriptor per unit (its range check reads 0 past
     // the month end; masked after), the lane's byte offset the only VGPR
-    auto load = [&](int s, int c) -> int {
-        const int64_t r0 = a.seg_off[s];
-        const int L = (int)(a.seg_off[s + 1] - r0);
+    // r0 and L (the month's first row and length) must be wave-uniform: with a per-lane
+    // descriptor every one of the loads is wrapped in a readfirstlane retry loop
+    auto load = [&](int64_t r0, int L, int c) {
         const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.hp + (int64_t)c * a.pstride + r0), 0,
                                                           L > 0 ? L * 4 : 0, 0x00020000);
         uint32_t lb = (uint32_t)(h * WAVE + lane) * 4u;
@@ -1495,11 +1495,9 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
 #pragma unroll
         for (int v = 0; v < VPH; ++v)
             xk[v] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, lb + (uint32_t)(v * 2 * WAVE * 4), 0, 0);
-        return L;
     };
-    auto finite_range = [&](int s, int c, double& m1, double& m2) {
-        const PCols base = sel_col(a, c, a.seg_off[s]);
-        const int Lu = (int)(a.seg_off[s + 1] - a.seg_off[s]);
+    auto finite_range = [&](int64_t r0, int Lu, int c, double& m1, double& m2) {
+        const PCols base = sel_col(a, c, r0);
         m1 = NAN;
         m2 = NAN;
         for (int r = h * WAVE + lane; r < Lu; r += 2 * WAVE) {
@@ -1513,7 +1511,9 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             m2 = hw_max(m2, xor_lanes_f64(m2, o));
         }
     };
-    int L = load(s_cur, c_cur);
+    int64_t r0 = a.seg_off[s_cur];
+    int L = (int)(a.seg_off[s_cur + 1] - r0);
+    load(r0, L, c_cur);
     while (true) {
         const int64_t u = (int64_t)c_cur * a.nseg + s_cur;
         const int64_t kn = k + gridDim.x;
@@ -1523,6 +1523,15 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             c_nx -= ncols;
             ++s_nx;
         }
+        // the next unit's month bounds, requested here: the kernel has stored to global memory
+        // by now, so these are vector loads; they return behind this unit's value loads, whose
+        // waits in step 1 cover them, and are made scalar (readfirstlane) where they are used
+        const int s_rq = more ? s_nx : s_cur;
+        // (only the words that are used: a loaded register that is dead is reused at once, and
+        // the write-after-write hazard puts a vmcnt(0) wait right behind the load)
+        const int64_t on0 = a.seg_off[s_rq];
+        const uint32_t on1 = *(const uint32_t*)(a.seg_off + s_rq + 1);   // low word: L < 2^31
+        int64_t r0n = 0;
         int Ln = 0;
         const int row0 = h * WAVE + lane;
         // ---- 1. keys (rows past the month end -> HK_NONE), count, lane min / max keys
@@ -1554,6 +1563,12 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             asm volatile("" : "+v"(kmn), "+v"(kmx2));
         }
         const int nh = VPH * WAVE - wave_sum(nbad);
+        // every value load has returned, so the month bounds behind them have too (the
+        // scheduler otherwise moves these, and a vmcnt(0) wait with them, to the loop's top)
+        __builtin_amdgcn_sched_barrier(0);
+        r0n = (int64_t)readfirstlane_u64((uint64_t)on0);
+        Ln = __builtin_amdgcn_readfirstlane((int)(on1 - (uint32_t)on0));
+        auto load_next = [&]() { load(r0n, Ln, c_nx); };
         const bool tvalid = kmn <= HK_MAX;
         const uint32_t kmx = kmx2 - 0x1FFFFEu;
         const bool amb = tvalid && (kmn == 0u || kmx == HK_MAX);
@@ -1618,7 +1633,7 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
                 sm.ni[h][2] = chi;
             }
             // xk is dead from here on: the next unit's loads fly during the sorts and gathers
-            if (more) Ln = load(s_nx, c_nx);
+            if (more) load_next();
             prefetched = true;
             __syncthreads();
             // ---- 4. one tail per wave over both halves' candidates
@@ -1627,7 +1642,7 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             const int cc = c0 + c1;
             bool good = c0 <= WCAP && c1 <= WCAP && cc <= 4 * WAVE;
             if (good) {
-                const PCols col = sel_col(a, c_cur, a.seg_off[s_cur]);
+                const PCols col = sel_col(a, c_cur, r0);
                 const int ra = t == 0 ? i0 : n - 1 - j1, rb = t == 0 ? j0 : n - 1 - i1;
                 double va = NAN, vb = NAN;
                 if (cc <= WAVE) good = pick_hk<1>(sm.cand[0][t], c0, sm.cand[1][t], c1, ra, rb, t, col, va, vb);
@@ -1648,7 +1663,7 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             double cen = 0.5 * (lo + hi);
             if (!isfinite(cen)) {
                 double m1, m2;
-                finite_range(s_cur, c_cur, m1, m2);
+                finite_range(r0, L, c_cur, m1, m2);
                 if (lane == 0) sm.res[0] = m1, sm.res[1] = m2;
             }
             if (lane == 0) {
@@ -1660,10 +1675,10 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
             }
         } else if (!isfinite(0.5 * (lo + hi))) {
             double m1, m2;
-            finite_range(s_cur, c_cur, m1, m2);
+            finite_range(r0, L, c_cur, m1, m2);
             if (lane == 0) sm.fr[0] = m1, sm.fr[1] = m2;
         }
-        if (more && !prefetched) Ln = load(s_nx, c_nx);
+        if (more && !prefetched) load_next();
         __syncthreads();
         if ((ok || !apply) && a.center && !isfinite(0.5 * (lo + hi)) && threadIdx.x == 0) {
             const double m1 = hw_min(sm.res[0], sm.fr[0]), m2 = hw_max(sm.res[1], sm.fr[1]);
@@ -1675,6 +1690,7 @@ __global__ __launch_bounds__(2 * WAVE, pair_hk_wgs(VPH) / 2) void select_pair_hk
         k = kn;
         s_cur = s_nx;
         c_cur = c_nx;
+        r0 = r0n;
         L = Ln;
     }
 }
