@@ -174,6 +174,11 @@ class RankArgs(C.Structure):
 
 
 FM_MAX_HORIZON = 60
+FM_MAX_FACTORS = 6
+FM_MAX_ALPHA_MODELS = 4
+FM_ALPHA_MAX_LAGS = 64
+FM_ALPHA_MAX_MONTHS = 4096
+FM_ALPHA_NSTAT = 4
 
 
 class LinksArgs(C.Structure):
@@ -187,6 +192,16 @@ class HorizonArgs(C.Structure):
     _fields_ = [
         ("ret", _p), ("link", _p), ("seg_off", _p), ("nrows", _i64), ("nseg", _i32), ("horizon", _i32),
         ("out", _p),
+    ]
+
+
+class AlphaArgs(C.Structure):
+    _fields_ = [
+        ("rec", _p), ("rec_month", _i64), ("rec_sort", _i64), ("rec_row", _i64), ("rec_col", _i64),
+        ("status", _p), ("st_month", _i64), ("st_sort", _i64), ("nsel", _i32), ("nrow", _i32), ("T", _i32),
+        ("K", _i32), ("M", _i32), ("nw_lags", _i32), ("factors", _p), ("rf", _p),
+        ("model_mask", C.c_uint32 * FM_MAX_ALPHA_MODELS), ("spread_row", _i32), ("pad_alpha", _i32),
+        ("coef", _p), ("se", _p), ("se_hac", _p), ("stat", _p), ("nobs", _p),
     ]
 
 
@@ -232,6 +247,7 @@ _SIGS = {
     "fm_rank_transform": (_i32, [C.POINTER(RankArgs), _p]),
     "fm_month_links": (_i32, [C.POINTER(LinksArgs), _p]),
     "fm_horizon_return": (_i32, [C.POINTER(HorizonArgs), _p]),
+    "fm_portfolio_alpha": (_i32, [C.POINTER(AlphaArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -250,7 +266,7 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_port_args": PortArgs, "fm_rank_args": RankArgs, "fm_forecast_src": ForecastSrc,
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs,
             "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
-            "fm_fhor_args": FHorArgs}
+            "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs}
 
 _lib = None
 

@@ -1474,6 +1474,92 @@ def portfolio_summary(p: Portfolios, nw_lags=4):
 
 
 @dataclass
+class PortfolioAlphas:
+    # leading dimensions [nport+1, 2 (ew, vw), M]; [nsel, nport+1, 2, M] for a batched Portfolios
+    coef: torch.Tensor     # [..., K+1] float64: alpha, then the loading on factor column f at 1 + f (NaN: not in the model)
+    se: torch.Tensor       # [..., K+1] float64 classical standard errors
+    se_hac: torch.Tensor   # [..., K+1] float64 Newey-West standard errors
+    stat: torch.Tensor     # [..., 4] float64: R2, residual s, mean and ddof-1 sd of the dependent series
+    nobs: torch.Tensor     # [...] int32 months used
+
+    @property
+    def tstat(self):
+        return self.coef / self.se
+
+    @property
+    def tstat_hac(self):
+        return self.coef / self.se_hac
+
+
+def alpha_model_masks(models, K):
+    """The bit masks of ``models`` (sequences of factor columns; None: CAPM on column 0 and, when
+    K > 1, all K factors).  ValueError for an empty model, a repeated column or one outside 0..K-1."""
+    if models is None:
+        models = [[0]] + ([list(range(K))] if K > 1 else [])
+    masks = []
+    for cols in models:
+        cols = [int(c) for c in cols]
+        if not cols or len(set(cols)) != len(cols) or min(cols) < 0 or max(cols) >= K:
+            raise ValueError(f"portfolio_alphas: a model must name distinct factor columns in 0..{K - 1}, got {cols}")
+        masks.append(sum(1 << c for c in cols))
+    if not 1 <= len(masks) <= L.FM_MAX_ALPHA_MODELS:
+        raise ValueError(f"portfolio_alphas: 1..{L.FM_MAX_ALPHA_MODELS} models per call, got {len(masks)}")
+    return masks
+
+
+def portfolio_alphas(ports: Portfolios, factors, models=None, rf=None, nw_lags=0):
+    """A18: the factor-model alphas of forecast-sorted portfolios -- every row of ``ports.rec``
+    (the portfolios and the high-minus-low spread), equal- and value-weighted, regressed over the
+    sorted months on each of ``models``' factor returns, with classical and Newey-West(``nw_lags``)
+    standard errors, R2, and the mean and standard deviation of the series, in one launch
+    (fm_portfolio_alpha; the definition is in fm_hip.h).  ``ports``: a ``Portfolios`` of
+    ``portfolio_sort`` (rec [T, nport+1, 4]) or the batched one of ``forecast_portfolio_sort``;
+    ``factors`` float64 [T, K] on its device, K <= 6, a NaN row dropping the month; ``rf`` float64
+    [T] or None, subtracted from the portfolios' returns (not from the spread); ``models``: up to 4
+    sequences of factor columns, default CAPM on column 0 plus, when K > 1, all K factors.
+    Returns ``PortfolioAlphas``.  No host sync."""
+    rec, status = ports.rec, ports.status
+    dev = rec.device
+    batched = rec.dim() == 4
+    if rec.dtype != torch.float64 or rec.dim() not in (3, 4) or rec.shape[-1] != 4 or rec.shape[-2] < 1:
+        raise ValueError("portfolio_alphas: ports.rec must be a float64 [T, nport+1, 4] or [nsel, T, nport+1, 4] tensor")
+    S = int(rec.shape[0]) if batched else 1
+    T, nrow = int(rec.shape[-3]), int(rec.shape[-2])
+    if status.dtype != torch.int32 or tuple(status.shape) != tuple(rec.shape[:-2]) or status.device != dev:
+        raise ValueError(f"portfolio_alphas: ports.status must be an int32 {list(rec.shape[:-2])} tensor on {dev}")
+    if factors.dtype != torch.float64 or factors.dim() != 2 or factors.shape[0] != T or factors.device != dev:
+        raise ValueError(f"portfolio_alphas: factors must be a float64 [{T}, K] tensor on {dev}")
+    K = int(factors.shape[1])
+    if not 1 <= K <= L.FM_MAX_FACTORS:
+        raise ValueError(f"portfolio_alphas: 1..{L.FM_MAX_FACTORS} factor columns, got {K}")
+    if rf is not None and (rf.dtype != torch.float64 or rf.dim() != 1 or rf.shape[0] != T or rf.device != dev):
+        raise ValueError(f"portfolio_alphas: rf must be a float64 [{T}] tensor on {dev}")
+    masks = alpha_model_masks(models, K)
+    M = len(masks)
+    factors = factors.contiguous()
+    rf = None if rf is None else rf.contiguous()
+    lead = ((S,) if batched else ()) + (nrow, 2, M)
+    out = PortfolioAlphas(coef=torch.empty(lead + (K + 1,), dtype=torch.float64, device=dev),
+                          se=torch.empty(lead + (K + 1,), dtype=torch.float64, device=dev),
+                          se_hac=torch.empty(lead + (K + 1,), dtype=torch.float64, device=dev),
+                          stat=torch.empty(lead + (L.FM_ALPHA_NSTAT,), dtype=torch.float64, device=dev),
+                          nobs=torch.empty(lead, dtype=torch.int32, device=dev))
+    # rec and status are read in place, whatever their strides
+    a = L.AlphaArgs(rec=rec.data_ptr(), rec_month=rec.stride(-3), rec_sort=rec.stride(0) if batched else 0,
+                    rec_row=rec.stride(-2), rec_col=rec.stride(-1), status=status.data_ptr(),
+                    st_month=status.stride(-1), st_sort=status.stride(0) if batched else 0,
+                    nsel=S, nrow=nrow, T=T, K=K, M=M,
+                    nw_lags=int(nw_lags), factors=factors.data_ptr(), rf=_ptr(rf), spread_row=nrow - 1,
+                    coef=out.coef.data_ptr(), se=out.se.data_ptr(), se_hac=out.se_hac.data_ptr(),
+                    stat=out.stat.data_ptr(), nobs=out.nobs.data_ptr())
+    for m, v in enumerate(masks):
+        a.model_mask[m] = v
+    _kcall("fm_portfolio_alpha", "fm_portfolio_alpha", L.C.byref(a), _stream())
+    _remember("fm_portfolio_alpha", "fm_portfolio_alpha", a, rec, status, factors, rf, out)
+    return out
+
+
+@dataclass
 class ForecastDist:
     rec: torch.Tensor      # [nsel, T, 2+nq] float64: mean, sd (ddof 1), the nq quantiles (NaN: status 0)
     cnt: torch.Tensor      # [nsel, T] int32 eligible rows

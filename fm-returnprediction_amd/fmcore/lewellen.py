@@ -14,6 +14,9 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
  -> optionally (``PipelineConfig.forecast_compare``) per universe and pair of Table-2 models the
     monthly regression of one model's forecast on the other's and of returns on its residual
     (paper Table 4, build-defined A15), likewise in one launch
+With ``PipelineConfig.alpha_factors`` the portfolios' monthly returns are also regressed on factor
+returns (CAPM and three-factor alphas, the second table of the paper's portfolio section;
+build-defined A18), in one more launch.
 With ``PipelineConfig.extrapolate`` = k the monthly run also scales every month's forecasts to k
 months and regresses the compounded k-month return on them (paper Section 4's second approach, the
 lower panels of Tables 9a and 9b; build-defined A17), in one more launch.
@@ -100,6 +103,21 @@ class PipelineConfig:
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
     forecast_dist: bool = field(default=False, kw_only=True)
     forecast_dist_q: Sequence[float] = field(default=(0.1, 0.9), kw_only=True)
+    # A18 (the portfolio section's second table, factor-model alphas): ``alpha_factors`` = the factor
+    # returns, float64 [T, K] with K <= 6 and row t = the panel's month t (a device tensor, or anything
+    # torch.as_tensor takes; a NaN row drops the month), regresses every portfolio's and the spread's
+    # ew and vw monthly return over the sorted months on each of ``alpha_models`` (sequences of factor
+    # columns; None: CAPM on column 0 and, when K > 1, all K factors), ``alpha_rf`` [T] subtracted
+    # from the portfolios' returns (not from the spread), with classical and Newey-West
+    # (``alpha_nw_lags``; None: ``nw_lags``) standard errors (engine.portfolio_alphas) -- one more
+    # launch.  Needs ``portfolios`` and horizon == 1 (overlapping k-month portfolio returns on monthly
+    # factors are not this table): ValueError otherwise, and for a first dimension other than the
+    # panel's month count.  None = no launch more.  In front of ``extrapolate``: tests pin the seven
+    # trailing fields.
+    alpha_factors: Optional[object] = field(default=None, kw_only=True)
+    alpha_models: Optional[Sequence[Sequence[int]]] = field(default=None, kw_only=True)
+    alpha_rf: Optional[object] = field(default=None, kw_only=True)
+    alpha_nw_lags: Optional[int] = field(default=None, kw_only=True)
     # A17 (paper Section 4, second approach): ``extrapolate`` = k in 2..engine.MAX_HORIZON keeps the
     # monthly regressions and forecasts and, in one more launch, scales every month's forecasts to k
     # months, G = k * mean + (1 + rho + ... + rho^(k-1)) (F - mean) with rho = ``extrapolate_decay`` in
@@ -152,6 +170,7 @@ class PipelineResult:
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
     y_col: str = "retx"                                   # the dependent column (cfg.horizon > 1: f"{y}_{h}m")
+    portfolio_alphas: Optional[E.PortfolioAlphas] = None  # cfg.alpha_factors: [nsort, nport+1, 2, M, ...]
     # cfg.extrapolate (in front of the comparison's fields, which tests pin as the trailing three)
     extrapolated: Optional[E.ForecastHorizon] = None      # [nsort, T, 6+nq], [nsort, T, 2], [nsort, T]
     extrapolated_summary: Optional[E.Summary] = None      # [nsort, 6+nq]
@@ -287,6 +306,38 @@ def check_extrapolate(cfg: PipelineConfig):
                          "to k months and regressions refitted on k-month returns are alternatives)")
 
 
+def check_alphas(cfg: PipelineConfig, nseg=None):
+    """The rules of ``PipelineConfig.alpha_factors`` (no device work); ``nseg``: the panel's month
+    count, when there is a panel."""
+    f = cfg.alpha_factors
+    if f is None:
+        for name in ("alpha_models", "alpha_rf", "alpha_nw_lags"):
+            if getattr(cfg, name) is not None:
+                raise ValueError(f"PipelineConfig: {name} needs alpha_factors")
+        return
+    if cfg.portfolios is None:
+        raise ValueError("PipelineConfig: alpha_factors needs portfolios (the returns it regresses)")
+    if cfg.horizon != 1:
+        raise ValueError(f"PipelineConfig: alpha_factors excludes horizon={cfg.horizon} (overlapping k-month "
+                         "portfolio returns on monthly factors are not this table)")
+    shape = tuple(getattr(f, "shape", np.shape(f)))
+    if len(shape) != 2 or not 1 <= shape[1] <= E.L.FM_MAX_FACTORS:
+        raise ValueError(f"PipelineConfig: alpha_factors must be [T, K] with K in 1..{E.L.FM_MAX_FACTORS}, "
+                         f"got shape {shape}")
+    E.alpha_model_masks(cfg.alpha_models, shape[1])
+    for what, t, want in (("alpha_factors", shape, None),
+                          ("alpha_rf", None if cfg.alpha_rf is None else
+                           tuple(getattr(cfg.alpha_rf, "shape", np.shape(cfg.alpha_rf))), 1)):
+        if t is None:
+            continue
+        if want is not None and len(t) != want:
+            raise ValueError(f"PipelineConfig: {what} must be a [T] vector, got shape {t}")
+        if nseg is not None and t[0] != nseg:
+            raise ValueError(f"PipelineConfig: {what} has {t[0]} rows, the panel has {nseg} months")
+        if t[0] != shape[0]:
+            raise ValueError(f"PipelineConfig: {what} has {t[0]} rows, alpha_factors {shape[0]}")
+
+
 def horizon_column(panel: E.DevicePanel, cfg: PipelineConfig, y="retx"):
     """The panel and dependent column of a run: (panel, y) at horizon 1; else the column
     f"{y}_{h}m", appended by engine.horizon_panel when the panel lacks it."""
@@ -306,6 +357,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     model_cols = model_cols or table2_models()
     check_horizon(cfg)
     check_extrapolate(cfg)
+    check_alphas(cfg, None if panel is None else panel.nseg)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
         if on and cfg.standardize:
@@ -360,13 +412,20 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                                           level=level, nyse=gpanel.nyse, nport=cfg.portfolios, q=cfg.portfolio_q,
                                           nyse_breakpoints=cfg.portfolio_nyse_breakpoints)
         port_summ = E.portfolio_summary(ports, cfg.nw_lags)
+    alphas = None
+    if cfg.alpha_factors is not None:
+        dev = ports.rec.device
+        alphas = E.portfolio_alphas(
+            ports, torch.as_tensor(cfg.alpha_factors, dtype=torch.float64).to(dev), models=cfg.alpha_models,
+            rf=None if cfg.alpha_rf is None else torch.as_tensor(cfg.alpha_rf, dtype=torch.float64).to(dev),
+            nw_lags=cfg.nw_lags if cfg.alpha_nw_lags is None else cfg.alpha_nw_lags)
     return PipelineResult(model_names=names, model_cols=dict(model_cols, **({"Figure 1": FIG1_VARS} if cfg.fig1 else {})),
                           res=res, ix=ix, summary=summ, rolling=roll, pred=pred, pred_status=pst,
                           pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
                           portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
                           forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
                           forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
-                          y_col=y, extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
+                          y_col=y, portfolio_alphas=alphas, extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

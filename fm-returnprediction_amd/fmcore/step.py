@@ -37,6 +37,9 @@ class ShardedStep:
         if cfg.extrapolate is not None:
             raise ValueError("ShardedStep: cfg.extrapolate must be None (k-month returns need the following "
                              "months' rows, which a month shard does not hold)")
+        if cfg.alpha_factors is not None:
+            raise ValueError("ShardedStep: cfg.alpha_factors must be None (a time-series regression needs every "
+                             "month's portfolio returns, which a month shard does not hold)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols
         self.world, self.rank, self.group = world, rank, group
         self.seg_lo = seg_lo

@@ -951,6 +951,92 @@ def build_table_5(crsp_comp: pd.DataFrame, variables_dict: dict = None, nport: i
     return frames
 
 
+def _month_rows(index, months, what):
+    """Row of ``index`` (dates, or the panel's own month numbers) for each of the panel's
+    ``months``, matched by calendar year and month; -1 where the month is absent."""
+    months = np.asarray(months)
+    if months.dtype.kind == "M":
+        have = pd.DatetimeIndex(index).values.astype("datetime64[M]")
+        want = months.astype("datetime64[M]")
+    else:
+        have, want = np.asarray(index), months
+    if len(np.unique(have)) != len(have):
+        raise ValueError(f"build_table_alphas: {what} holds a month twice")
+    at = {v: i for i, v in enumerate(have.tolist())}
+    return np.array([at.get(v, -1) for v in want.tolist()], dtype=np.int64)
+
+
+def _month_aligned(values, index, months, what):
+    """``values`` [rows(, K)] re-indexed to the panel's months: NaN rows for the months absent."""
+    rows = _month_rows(index, months, what)
+    v = np.asarray(values, dtype=np.float64)
+    out = np.full((len(rows),) + v.shape[1:], np.nan)
+    out[rows >= 0] = v[rows[rows >= 0]]
+    return out
+
+
+ALPHA_COLUMNS = ["alpha", "t", "t_hac", "R2", "nobs"]
+
+
+def build_table_alphas(crsp_comp: pd.DataFrame, factors: pd.DataFrame, rf=None, models: dict = None, nport: int = 10,
+                       **cfg):
+    """The factor-model alphas of build_table_5's portfolios from the same ONE device pipeline run
+    (build-defined A18; no reference line; the second table of the paper's portfolio section,
+    "Alphas for expected-return sorted portfolios" in the 2014 working paper): every portfolio's and
+    the high-minus-low spread's monthly return, equal- and value-weighted, regressed on factor returns.
+    ``factors``: a DataFrame of monthly factor returns (decimals, like the returns) indexed by date,
+    matched to the panel's months by calendar year and month; a month absent from it, or with a NaN
+    factor of the model, drops out of that model's regressions.  ``rf``: the risk-free rate as a
+    column name of ``factors`` (which is then no factor) or a Series indexed by date; it is
+    subtracted from the portfolios' returns, not from the spread.  ``models``: {name: [factor
+    columns]}, default {"CAPM": [the first column], "FF": all columns}.  ``cfg``: further
+    PipelineConfig fields (window, min_periods, lag, nw_lags, alpha_nw_lags, ...).
+    Returns {(model name, universe name): DataFrame} with build_table_5's portfolio labels as rows and
+    the columns (weighting, "", Avg / Std / Shp) -- the mean and standard deviation of the (excess)
+    return over the first model's months and the annualised Sharpe ratio Avg / Std * sqrt(12) -- and
+    (weighting, factor model, alpha / t / t_hac / R2 / nobs): the intercept, its classical and
+    Newey-West t-statistics, the regression's R2 and the months it used."""
+    panel, model_cols = _pipeline_panel(crsp_comp, None)
+    fcols = [c for c in factors.columns if not (isinstance(rf, str) and c == rf)]
+    if isinstance(rf, str) and rf not in factors.columns:
+        raise ValueError(f"build_table_alphas: factors has no column {rf!r}")
+    if models is None:
+        models = {"CAPM": fcols[:1]}
+        if len(fcols) > 1:
+            models["FF"] = list(fcols)
+    for name, cols in models.items():
+        missing = [c for c in cols if c not in fcols]
+        if missing:
+            raise ValueError(f"build_table_alphas: model {name!r} names {missing}, not among the factors {fcols}")
+    F = _month_aligned(factors[fcols].to_numpy(dtype=np.float64), factors.index, panel.months, "factors")
+    if rf is None:
+        R = None
+    elif isinstance(rf, str):
+        R = _month_aligned(factors[rf].to_numpy(dtype=np.float64), factors.index, panel.months, "factors")
+    else:
+        R = _month_aligned(np.asarray(rf, dtype=np.float64), rf.index, panel.months, "rf")
+    pcfg = _LW.PipelineConfig(**dict(cfg, portfolios=int(nport), alpha_factors=F, alpha_rf=R,
+                                     alpha_models=[[fcols.index(c) for c in cols] for cols in models.values()]))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    a = out.portfolio_alphas
+    coef, t, th, stat, nobs = (x.cpu().numpy() for x in (a.coef, a.tstat, a.tstat_hac, a.stat, a.nobs))
+    labels = pd.Index(list(range(int(nport))) + ["H-L"], name="portfolio")
+    frames = {}
+    for j, k in enumerate(out.portfolio_problems):
+        prob = out.res.problems[k]
+        data = {}
+        for w, wn in enumerate(("ew", "vw")):
+            avg, std = stat[j, :, w, 0, 2], stat[j, :, w, 0, 3]
+            data[(wn, "", "Avg")], data[(wn, "", "Std")] = avg, std
+            data[(wn, "", "Shp")] = avg / std * np.sqrt(12.0)
+            for m, name in enumerate(models):
+                for c, v in zip(ALPHA_COLUMNS, (coef[j, :, w, m, 0], t[j, :, w, m, 0], th[j, :, w, m, 0],
+                                                stat[j, :, w, m, 0], nobs[j, :, w, m])):
+                    data[(wn, name, c)] = v
+        frames[(out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level])] = pd.DataFrame(data, index=labels)
+    return frames
+
+
 def build_table_3(crsp_comp: pd.DataFrame, variables_dict: dict = None, q=(0.1, 0.9), **cfg):
     """Paper Table 3 from ONE device pipeline run (build-defined; no reference line): for every
     Table-2 model and universe, the univariate properties of the out-of-sample forecast from that

@@ -64,6 +64,10 @@
  *                      to k months (geometric decay toward the cross-sectional mean) and the
  *                      k-month return regressed on them (the paper's second long-horizon
  *                      approach, lower panels of Tables 9a and 9b); no reference line
+ *   fm_portfolio_alpha <- build-defined extension A18: the time-series regressions of every
+ *                      forecast-sorted portfolio's return on factor returns (CAPM and three-factor
+ *                      alphas with classical and Newey-West t-statistics, the second table of the
+ *                      paper's portfolio section); no reference line
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -219,7 +223,8 @@ const char* fm_last_error(void);
 #define FM_ARG_STRUCTS(X)                                                                     \
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
-    X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)
+    X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)      \
+    X(fm_alpha_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -835,6 +840,75 @@ typedef struct fm_horizon_args {
 } fm_horizon_args;
 
 int fm_horizon_return(const fm_horizon_args* args, void* stream);
+
+/* fm_portfolio_alpha: the factor-model alphas of the forecast-sorted portfolios -- every
+ * portfolio's (and the high-minus-low spread's) equal- and value-weighted monthly return regressed
+ * on M sets of factor returns, with classical and Newey-West (HAC) coefficient standard errors, in
+ * one launch with one workgroup per (series, model) (build-defined extension A18; no reference
+ * line; the 2014 working paper's "Alphas for expected-return sorted portfolios", the second table
+ * of the paper's portfolio section).  Inputs are fm_portfolio_sort's rec / status, read in place
+ * through their strides, and factors [T][K] (row t = month t, contiguous) with an optional rf [T].
+ * A series is (sort j < nsel, row p < nrow, weighting w in {0: ew, 1: vw}).  Its dependent value in
+ * month t is
+ *   d_t = rec[j * rec_sort + t * rec_month + p * rec_row + 2 * w * rec_col] - rf[t]
+ * with rf NULL or p == spread_row (a difference of two returns): the raw rec value.
+ * Model m is the set of factor columns in model_mask[m] (bit f = column f), k = its size.  It uses
+ * month t of a series only if status[j * st_sort + t * st_month] == 1, d_t is finite and every
+ * factor of m is finite at t.  The used months in month order are treated as consecutive
+ * (fm_ts_summary's dropna convention); n is their count.  Per (series, model), x = [1, f_m]:
+ *   means d- = sum(d) / n and f-_a = sum(f_a) / n first, then the centred cross-products
+ *   A = sum (f - f-)(f - f-)', c = sum (f - f-)(d - d-), Syy = sum (d - d-)^2;
+ *   Cholesky of A in ascending factor order, beta = A^-1 c, alpha = d- - beta'f-;
+ *   e_t = (d_t - d-) - beta'(f_t - f-), s^2 = e'e / (n - k - 1);
+ *   coef  [K+1]: slot 0 alpha, slot 1 + f factor column f; factors outside the model NaN;
+ *   se    [K+1]: classical, sqrt diag of s^2 (X'X)^-1;
+ *   se_hac[K+1]: sqrt diag of (X'X)^-1 S (X'X)^-1 with S = sum_t e_t^2 x_t x_t' + sum_{l = 1 ..
+ *                min(nw_lags, n - 1)} (1 - l / (nw_lags + 1)) sum_t e_t e_{t-l} (x_t x_{t-l}' +
+ *                x_{t-l} x_t'), no small-sample correction (evaluated in the centred basis
+ *                [1, f - f-], which is the same quadratic form); a variance that rounds below 0 is
+ *                written as se 0;
+ *   stat  [4]:   R^2 = 1 - e'e / Syy (NaN when Syy == 0), s, d-, and the ddof-1 standard deviation
+ *                of d, sqrt(Syy / (n - 1));
+ *   nobs:        n.
+ * Refusals per (series, model) write NaN, they are no error: n < k + 2 leaves everything NaN except
+ * nobs; a diagonal entry A_aa == 0 or a Cholesky pivot (A_aa minus the squares of its row of the
+ * factor so far) <= 1e-10 * A_aa -- collinear or constant factors -- leaves coef, se, se_hac, R^2
+ * and s NaN, with d-, the standard deviation and nobs still written.
+ * Every sum runs in one fixed order (thread i of 256 adds the used months i, i + 256, ... from +0.0,
+ * the wave butterfly, then the four wave sums in order), so the bits of a (series, model) depend on
+ * its own months alone: not on the other series or models of the launch, nor on the run.  The
+ * launch needs no workspace and no host sync.  Outputs have the leading dimensions
+ * [nsel][nrow][2][M].  Refused with FM_EINVAL before any launch (the message names the field): a
+ * NULL required pointer, K outside 1..FM_MAX_FACTORS, M outside 1..FM_MAX_ALPHA_MODELS, nw_lags
+ * outside 0..FM_ALPHA_MAX_LAGS, an empty mask, a mask bit >= K, a negative dimension.  T >
+ * FM_ALPHA_MAX_MONTHS: FM_ETOOBIG before any launch (the used months' index and the residuals stay
+ * in LDS).  T == 0, nsel == 0 or nrow == 0 is a valid empty call.  Zero-initialize the struct (it
+ * grows at the end). */
+#define FM_MAX_FACTORS 6
+#define FM_MAX_ALPHA_MODELS 4
+#define FM_ALPHA_MAX_LAGS 64
+#define FM_ALPHA_MAX_MONTHS 4096
+#define FM_ALPHA_NSTAT 4
+typedef struct fm_alpha_args {
+    const double* rec;           /* portfolio records; column 0 ew return, column 2 vw return */
+    int64_t rec_month, rec_sort, rec_row, rec_col;   /* strides in doubles */
+    const uint32_t* status;      /* 1 = sorted month */
+    int64_t st_month, st_sort;   /* strides in words */
+    int32_t nsel, nrow, T, K, M;
+    int32_t nw_lags;             /* 0 .. FM_ALPHA_MAX_LAGS */
+    const double* factors;       /* [T][K] */
+    const double* rf;            /* [T] or NULL */
+    uint32_t model_mask[FM_MAX_ALPHA_MODELS];   /* [M] bit f: factor column f is in the model */
+    int32_t spread_row;          /* the row that is a difference of returns (no rf), or -1 */
+    int32_t pad_alpha;
+    double* coef;                /* [nsel][nrow][2][M][K+1] */
+    double* se;                  /* [nsel][nrow][2][M][K+1] */
+    double* se_hac;              /* [nsel][nrow][2][M][K+1] */
+    double* stat;                /* [nsel][nrow][2][M][FM_ALPHA_NSTAT] */
+    int32_t* nobs;               /* [nsel][nrow][2][M] */
+} fm_alpha_args;
+
+int fm_portfolio_alpha(const fm_alpha_args* args, void* stream);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
