@@ -205,6 +205,18 @@ class AlphaArgs(C.Structure):
     ]
 
 
+FM_MAX_HOLD = 36
+
+
+class HoldArgs(C.Structure):
+    _fields_ = [
+        ("seg_off", _p), ("month_index", _p), ("link_prev", _p), ("port", _p), ("status", _p), ("ret", _p),
+        ("weight", _p), ("sort_rec", _p), ("nrows", _i64), ("nseg", _i32), ("nsel", _i32), ("nport", _i32),
+        ("hold", _i32), ("members", _p), ("stay", _p), ("cohort_n", _p), ("cohort", _p), ("status_out", _p),
+        ("rec", _p), ("turnover", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -248,6 +260,7 @@ _SIGS = {
     "fm_month_links": (_i32, [C.POINTER(LinksArgs), _p]),
     "fm_horizon_return": (_i32, [C.POINTER(HorizonArgs), _p]),
     "fm_portfolio_alpha": (_i32, [C.POINTER(AlphaArgs), _p]),
+    "fm_portfolio_hold": (_i32, [C.POINTER(HoldArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -266,7 +279,8 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_port_args": PortArgs, "fm_rank_args": RankArgs, "fm_forecast_src": ForecastSrc,
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs,
             "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
-            "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs}
+            "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs,
+            "fm_hold_args": HoldArgs}
 
 _lib = None
 

@@ -2118,6 +2118,97 @@ def column_vector(panel: DevicePanel, col):
     return out
 
 
+MAX_HOLD = L.FM_MAX_HOLD
+
+
+@dataclass
+class HeldPortfolios:
+    # ``rec`` and ``status`` have ``Portfolios``' shapes and dtypes: portfolio_summary and
+    # portfolio_alphas read a HeldPortfolios as they read a Portfolios.  Every tensor carries a leading
+    # [nsel] dimension when the port bytes did.
+    rec: torch.Tensor        # [T, nport+1, 4] float64: the k-cohort average of ew ret, predicted, vw ret, predicted; last = H-L
+    status: torch.Tensor     # [T] int32: 1 = a complete month (k sorted consecutive months end here)
+    cohort: torch.Tensor     # [T, k, nport, 2] float64: month-t ew / vw return of the cohort formed a months earlier
+    cohort_n: torch.Tensor   # [T, k, nport, 2] int32: its rows with a finite return / also a finite weight > 0
+    members: torch.Tensor    # [T, k+1, nport] int32: rows whose age-a ancestor was in portfolio q
+    stay: torch.Tensor       # [T, k+1, nport] int32: those that are in portfolio q themselves
+    turnover: torch.Tensor   # [T, nport] float64: share of names replaced in month t
+    hold: int = 1
+
+
+def portfolio_hold(seg_off, month_index, link_prev, port, status, ret, weight=None, nport=10, hold=1, sort_rec=None):
+    """A19: the sorted portfolios held for ``hold`` = k months as overlapping cohorts -- in month t
+    the k cohorts formed in months t, t-1, .., t-k+1, each followed through the firm links -- as a
+    monthly record with ``Portfolios``' layout, plus the cohorts' returns and sizes, how many of a
+    cohort's names are still in the same portfolio at every age, and the monthly name turnover
+    (fm_portfolio_hold; the definition is in fm_hip.h).  Plain device tensors in, ``HeldPortfolios``
+    out: ``seg_off`` int64 [T+1], ``month_index`` int32 [T], ``link_prev`` int32 [rows]
+    (``month_links`` with step -1), ``port`` uint8 [rows] or [nsel, rows] and ``status`` int32 [T] or
+    [nsel, T] of a sort, ``ret`` and ``weight`` float64 [rows], ``sort_rec`` the sort's own ``rec``
+    (for the predicted columns; None: they are NaN).  One launch, no host sync."""
+    dev = ret.device
+    n = int(ret.shape[0])
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("portfolio_hold: seg_off must be an int64 [T+1] tensor on the returns' device")
+    seg_off = seg_off.contiguous()
+    T = int(seg_off.shape[0]) - 1
+    nport, hold = int(nport), int(hold)
+    if not 2 <= nport <= L.FM_MAX_PORTS:
+        raise ValueError(f"portfolio_hold: nport must be 2..{L.FM_MAX_PORTS}, got {nport}")
+    if not 1 <= hold <= L.FM_MAX_HOLD:
+        raise ValueError(f"portfolio_hold: hold must be 1..{L.FM_MAX_HOLD}, got {hold}")
+    batched = port.dim() == 2
+    S = int(port.shape[0]) if batched else 1
+    lead = (S,) if batched else ()
+    if S > L.FM_MAX_SORTS:
+        raise ValueError(f"portfolio_hold: at most {L.FM_MAX_SORTS} sorts per call, got {S}")
+    for t, dt, sh, what in ((month_index, torch.int32, (T,), "month_index"), (link_prev, torch.int32, (n,), "link_prev"),
+                            (port, torch.uint8, lead + (n,), "port"), (status, torch.int32, lead + (T,), "status"),
+                            (ret, torch.float64, (n,), "ret"), (weight, torch.float64, (n,), "weight"),
+                            (sort_rec, torch.float64, lead + (T, nport + 1, 4), "sort_rec")):
+        if t is None and what in ("weight", "sort_rec"):
+            continue
+        if t is None or t.dtype != dt or tuple(t.shape) != sh or t.device != dev:
+            raise ValueError(f"portfolio_hold: {what} must be a {dt} {list(sh)} tensor on {dev}")
+    month_index, link_prev, port, status, ret = (t.contiguous() for t in (month_index, link_prev, port, status, ret))
+    weight = None if weight is None else weight.contiguous()
+    sort_rec = None if sort_rec is None else sort_rec.contiguous()
+
+    def new(shape, dtype, fill):
+        # an empty call launches nothing: its outputs are then what a launch would have written
+        if n and T and S:
+            return torch.empty(lead + shape, dtype=dtype, device=dev)
+        return torch.full(lead + shape, fill, dtype=dtype, device=dev)
+
+    out = HeldPortfolios(rec=new((T, nport + 1, 4), torch.float64, float("nan")), status=new((T,), torch.int32, 0),
+                         cohort=new((T, hold, nport, 2), torch.float64, float("nan")),
+                         cohort_n=new((T, hold, nport, 2), torch.int32, 0),
+                         members=new((T, hold + 1, nport), torch.int32, 0), stay=new((T, hold + 1, nport), torch.int32, 0),
+                         turnover=new((T, nport), torch.float64, float("nan")), hold=hold)
+    a = L.HoldArgs(seg_off=seg_off.data_ptr(), month_index=month_index.data_ptr(), link_prev=link_prev.data_ptr(),
+                   port=port.data_ptr(), status=status.data_ptr(), ret=ret.data_ptr(), weight=_ptr(weight),
+                   sort_rec=_ptr(sort_rec), nrows=n, nseg=T, nsel=S, nport=nport, hold=hold,
+                   members=out.members.data_ptr(), stay=out.stay.data_ptr(), cohort_n=out.cohort_n.data_ptr(),
+                   cohort=out.cohort.data_ptr(), status_out=out.status.data_ptr(), rec=out.rec.data_ptr(),
+                   turnover=out.turnover.data_ptr())
+    _kcall("fm_portfolio_hold", "fm_portfolio_hold", L.C.byref(a), _stream())
+    _remember("fm_portfolio_hold", "fm_portfolio_hold", a, seg_off, month_index, link_prev, port, status, ret, weight,
+              sort_rec, out)
+    return out
+
+
+def held_portfolios(panel: DevicePanel, ports: Portfolios, hold, ret="retx", weight=None):
+    """A19 on a panel: ``portfolio_hold`` of the sorted ``ports`` (``portfolio_sort`` or the batched
+    ``forecast_portfolio_sort``) with the panel's segments, calendar and step -1 firm links
+    (``month_links``), the panel column ``ret`` and the sort's own records for the predicted columns.
+    The panel needs ``ids``: ValueError otherwise."""
+    if panel.ids is None or panel.month_index is None:
+        raise ValueError("held_portfolios: the panel carries no firm ids (build it with ids=...)")
+    nport = int(ports.rec.shape[-2]) - 1
+    return portfolio_hold(panel.seg_off, panel.month_index_device(), month_links(panel, -1), ports.port, ports.status,
+                          column_vector(panel, ret), weight=weight, nport=nport, hold=hold, sort_rec=ports.rec)
+
+
 def segment_moments(panel: DevicePanel, level=None, min_level=0, finite_only=True, cols=None):
     """Per (column, month) count, mean and ddof=1 std of the non-missing values."""
     src = panel.values() if cols is None else cols

@@ -17,6 +17,9 @@ winsorize (1/99, every column, reference src/calc_Lewellen_2014.py:505-529)
 With ``PipelineConfig.alpha_factors`` the portfolios' monthly returns are also regressed on factor
 returns (CAPM and three-factor alphas, the second table of the paper's portfolio section;
 build-defined A18), in one more launch.
+With ``PipelineConfig.portfolio_hold`` = k those portfolios are held for k months as overlapping
+cohorts (the calendar-time strategy; build-defined A19): its monthly record, summary, turnover and,
+with the factors, its alphas, in one more launch.
 With ``PipelineConfig.extrapolate`` = k the monthly run also scales every month's forecasts to k
 months and regresses the compounded k-month return on them (paper Section 4's second approach, the
 lower panels of Tables 9a and 9b; build-defined A17), in one more launch.
@@ -118,6 +121,15 @@ class PipelineConfig:
     alpha_models: Optional[Sequence[Sequence[int]]] = field(default=None, kw_only=True)
     alpha_rf: Optional[object] = field(default=None, kw_only=True)
     alpha_nw_lags: Optional[int] = field(default=None, kw_only=True)
+    # A19 (k-month holding of the Table-5 portfolios): ``portfolio_hold`` = k in 1..engine.MAX_HOLD
+    # follows every month's portfolios for k months over the firm links and reports the strategy that
+    # holds the k latest cohorts (engine.held_portfolios: its monthly record, FM summary, cohort sizes,
+    # persistence and name turnover) -- one more launch; with ``alpha_factors`` the held record is
+    # regressed on the factors too.  The held returns are monthly, so month t of the factor table is
+    # month t of the record.  Needs ``portfolios``, a panel with firm ids and horizon == 1 (held
+    # monthly returns are the alternative to k-month dependent returns): ValueError otherwise.  None =
+    # no launch more.  In front of ``extrapolate``: tests pin the seven trailing fields.
+    portfolio_hold: Optional[int] = field(default=None, kw_only=True)
     # A17 (paper Section 4, second approach): ``extrapolate`` = k in 2..engine.MAX_HORIZON keeps the
     # monthly regressions and forecasts and, in one more launch, scales every month's forecasts to k
     # months, G = k * mean + (1 + rho + ... + rho^(k-1)) (F - mean) with rho = ``extrapolate_decay`` in
@@ -170,6 +182,9 @@ class PipelineResult:
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
     y_col: str = "retx"                                   # the dependent column (cfg.horizon > 1: f"{y}_{h}m")
+    held: Optional[E.HeldPortfolios] = None               # cfg.portfolio_hold: tensors with a leading [nsort] dimension
+    held_summary: Optional[E.Summary] = None              # [nsort, nport+1, 4]
+    held_alphas: Optional[E.PortfolioAlphas] = None       # with cfg.alpha_factors: [nsort, nport+1, 2, M, ...]
     portfolio_alphas: Optional[E.PortfolioAlphas] = None  # cfg.alpha_factors: [nsort, nport+1, 2, M, ...]
     # cfg.extrapolate (in front of the comparison's fields, which tests pin as the trailing three)
     extrapolated: Optional[E.ForecastHorizon] = None      # [nsort, T, 6+nq], [nsort, T, 2], [nsort, T]
@@ -319,7 +334,8 @@ def check_alphas(cfg: PipelineConfig, nseg=None):
         raise ValueError("PipelineConfig: alpha_factors needs portfolios (the returns it regresses)")
     if cfg.horizon != 1:
         raise ValueError(f"PipelineConfig: alpha_factors excludes horizon={cfg.horizon} (overlapping k-month "
-                         "portfolio returns on monthly factors are not this table)")
+                         "portfolio returns on monthly factors are not this table; portfolio_hold=k regresses "
+                         "the monthly returns of the portfolios held for k months)")
     shape = tuple(getattr(f, "shape", np.shape(f)))
     if len(shape) != 2 or not 1 <= shape[1] <= E.L.FM_MAX_FACTORS:
         raise ValueError(f"PipelineConfig: alpha_factors must be [T, K] with K in 1..{E.L.FM_MAX_FACTORS}, "
@@ -336,6 +352,23 @@ def check_alphas(cfg: PipelineConfig, nseg=None):
             raise ValueError(f"PipelineConfig: {what} has {t[0]} rows, the panel has {nseg} months")
         if t[0] != shape[0]:
             raise ValueError(f"PipelineConfig: {what} has {t[0]} rows, alpha_factors {shape[0]}")
+
+
+def check_hold(cfg: PipelineConfig, panel=None):
+    """The rules of ``PipelineConfig.portfolio_hold`` (no device work); ``panel``: the run's panel,
+    when there is one."""
+    k = cfg.portfolio_hold
+    if k is None:
+        return
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or k < 1 or k > E.MAX_HOLD:
+        raise ValueError(f"PipelineConfig: portfolio_hold must be an integer in 1..{E.MAX_HOLD}, got {k!r}")
+    if cfg.portfolios is None:
+        raise ValueError("PipelineConfig: portfolio_hold needs portfolios (the sorts it holds)")
+    if cfg.horizon != 1:
+        raise ValueError(f"PipelineConfig: portfolio_hold={k} excludes horizon={cfg.horizon} (held monthly returns "
+                         "and k-month dependent returns are alternatives)")
+    if panel is not None and (panel.ids is None or panel.month_index is None):
+        raise ValueError("PipelineConfig: portfolio_hold needs a panel with firm ids (build it with ids=...)")
 
 
 def horizon_column(panel: E.DevicePanel, cfg: PipelineConfig, y="retx"):
@@ -358,6 +391,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     check_horizon(cfg)
     check_extrapolate(cfg)
     check_alphas(cfg, None if panel is None else panel.nseg)
+    check_hold(cfg, panel)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
         if on and cfg.standardize:
@@ -412,20 +446,29 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                                           level=level, nyse=gpanel.nyse, nport=cfg.portfolios, q=cfg.portfolio_q,
                                           nyse_breakpoints=cfg.portfolio_nyse_breakpoints)
         port_summ = E.portfolio_summary(ports, cfg.nw_lags)
-    alphas = None
+    held = held_summ = None
+    if cfg.portfolio_hold is not None:
+        # the sorts' port bytes followed for k months over the firm links of the panel the sort read
+        held = E.held_portfolios(gpanel, ports, int(cfg.portfolio_hold), ret=gpanel.col(y), weight=gpanel.me)
+        held_summ = E.portfolio_summary(held, cfg.nw_lags)
+    alphas = held_alphas = None
     if cfg.alpha_factors is not None:
         dev = ports.rec.device
-        alphas = E.portfolio_alphas(
-            ports, torch.as_tensor(cfg.alpha_factors, dtype=torch.float64).to(dev), models=cfg.alpha_models,
-            rf=None if cfg.alpha_rf is None else torch.as_tensor(cfg.alpha_rf, dtype=torch.float64).to(dev),
-            nw_lags=cfg.nw_lags if cfg.alpha_nw_lags is None else cfg.alpha_nw_lags)
+        akw = dict(models=cfg.alpha_models,
+                   rf=None if cfg.alpha_rf is None else torch.as_tensor(cfg.alpha_rf, dtype=torch.float64).to(dev),
+                   nw_lags=cfg.nw_lags if cfg.alpha_nw_lags is None else cfg.alpha_nw_lags)
+        factors = torch.as_tensor(cfg.alpha_factors, dtype=torch.float64).to(dev)
+        alphas = E.portfolio_alphas(ports, factors, **akw)
+        if held is not None:
+            held_alphas = E.portfolio_alphas(held, factors, **akw)
     return PipelineResult(model_names=names, model_cols=dict(model_cols, **({"Figure 1": FIG1_VARS} if cfg.fig1 else {})),
                           res=res, ix=ix, summary=summ, rolling=roll, pred=pred, pred_status=pst,
                           pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
                           portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
                           forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
                           forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
-                          y_col=y, portfolio_alphas=alphas, extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
+                          y_col=y, held=held, held_summary=held_summ, held_alphas=held_alphas, portfolio_alphas=alphas,
+                          extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

@@ -40,6 +40,9 @@ class ShardedStep:
         if cfg.alpha_factors is not None:
             raise ValueError("ShardedStep: cfg.alpha_factors must be None (a time-series regression needs every "
                              "month's portfolio returns, which a month shard does not hold)")
+        if cfg.portfolio_hold is not None:
+            raise ValueError("ShardedStep: cfg.portfolio_hold must be None (a cohort is followed through the earlier "
+                             "months' rows, which a month shard does not hold)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols
         self.world, self.rank, self.group = world, rank, group
         self.seg_lo = seg_lo

@@ -688,22 +688,33 @@ def forecast_sorted_portfolios(df: pd.DataFrame, forecast, return_col: str = "re
     f = np.asarray(forecast, dtype=np.float64)
     if f.shape != (len(df),):
         raise ValueError("forecast must hold one value per row of df")
-    order = np.lexsort((df["permno"].to_numpy(), df[date_col].to_numpy()))
+    panel, p = _sorted_panel(df, f, return_col, weight_col, nport, breakpoints, universe, nyse_breakpoints, date_col)
+    s = _E.portfolio_summary(p, nw_lags)
+    return _portfolio_frames(p.status.cpu().numpy(), p.rec.cpu().numpy(), p.cnt.cpu().numpy(), s.mean.cpu().numpy(),
+                             s.tstat.cpu().numpy(), s.nobs.cpu().numpy(), panel.months, nport, date_col)
+
+
+def _sorted_panel(df, f, return_col, weight_col, nport, breakpoints, universe, nyse_breakpoints, date_col, ids=None,
+                  id_col="permno"):
+    """forecast_sorted_portfolios' device work: the frame's panel (columns forecast, return and, with
+    ``weight_col``, weight; rows by (month, ``id_col``); ``ids``: the firm ids it carries) and its
+    ``Portfolios``."""
+    keys = df[id_col].to_numpy() if ids is None else ids
+    order = np.lexsort((keys, df[date_col].to_numpy()))
     d = df.iloc[order]
     names = ["forecast", return_col] + ([weight_col] if weight_col is not None else [])
     arrays = [f[order], _api.as_f64(d[return_col])] + ([_api.as_f64(d[weight_col])] if weight_col is not None else [])
     need_nyse = nyse_breakpoints or universe is not None
     me = _api.as_f64(d["me"]) if universe is not None else None
     nyse = (d["primaryexch"] == "N").to_numpy().astype(np.uint8) if need_nyse else None
-    panel = _E.panel_from_arrays(arrays, names, d[date_col].values, me=me, nyse=nyse)
+    panel = _E.panel_from_arrays(arrays, names, d[date_col].values, me=me, nyse=nyse,
+                                 ids=None if ids is None else ids[order])
     level = _E.universe(panel)[2] if universe is not None else None
     p = _E.portfolio_sort(panel.seg_off, panel.cols[0], panel.cols[1],
                           weight=panel.cols[2] if weight_col is not None else None, level=level, nyse=panel.nyse,
                           nport=nport, q=breakpoints, min_level=_UNIVERSE_LEVEL[universe],
                           nyse_breakpoints=nyse_breakpoints, max_seg_len=panel.max_seg_len)
-    s = _E.portfolio_summary(p, nw_lags)
-    return _portfolio_frames(p.status.cpu().numpy(), p.rec.cpu().numpy(), p.cnt.cpu().numpy(), s.mean.cpu().numpy(),
-                             s.tstat.cpu().numpy(), s.nobs.cpu().numpy(), panel.months, nport, date_col)
+    return panel, p
 
 
 def _portfolio_frames(status, rec, cnt, mean, tstat, nobs, months, nport, date_col="mthcaldt"):
@@ -720,6 +731,49 @@ def _portfolio_frames(status, rec, cnt, mean, tstat, nobs, months, nport, date_c
                             for stat, v in (("mean", mean), ("tstat", tstat), ("nobs", nobs))},
                            index=pd.Index(labels, name="portfolio"))
     return monthly, summary
+
+
+def _held_frames(status, rec, members, turnover, mean, tstat, nobs, months, nport, date_col="mthcaldt"):
+    """held_sorted_portfolios' (monthly, summary) frames of one sort's host arrays: _portfolio_frames'
+    with ``n`` = the month's own members and one more column, ``turnover`` (NaN for "H-L")."""
+    monthly, summary = _portfolio_frames(status, rec, members[:, 0, :], mean, tstat, nobs, months, nport, date_col)
+    tv = np.concatenate([turnover[status == 1], np.full((int((status == 1).sum()), 1), np.nan)], axis=1)
+    monthly["turnover"] = tv.reshape(-1)
+    return monthly, summary
+
+
+def held_sorted_portfolios(df: pd.DataFrame, forecast, hold: int, return_col: str = "retx", weight_col: str = None,
+                           nport: int = 10, breakpoints=None, universe: str = None, nyse_breakpoints: bool = False,
+                           date_col: str = "mthcaldt", nw_lags: int = 4, id_col: str = "permno"):
+    """A19: forecast_sorted_portfolios' sorts held for ``hold`` = k months as overlapping cohorts (the
+    calendar-time strategy of Jegadeesh and Titman): in month t the strategy holds, per portfolio,
+    the k cohorts formed in months t, .., t-k+1, each followed through the firm's rows of the months
+    between (a firm with a gap leaves its cohort), equal-weighted among a cohort's survivors or
+    weighted by their current ``weight_col``; the strategy's return is the plain average of the k
+    cohort returns (fm_portfolio_sort, fm_month_links, fm_portfolio_hold on the device).  The other
+    arguments are forecast_sorted_portfolios'; ``id_col`` holds whole-number firm ids and ``date_col``
+    datetime64 or integer months, one row per (month, firm): ValueError otherwise.
+    Returns (monthly, summary) in forecast_sorted_portfolios' frame format over the complete months
+    (k sorted consecutive calendar months end there): ``n`` is the month's own sorted rows of the
+    portfolio, ew_pred / vw_pred average the formation months' predicted returns, and one more
+    column, ``turnover``, is the share of the strategy's names replaced that month, (1 - the share of
+    the portfolio's names that were in it k months earlier) / k (NaN for "H-L", and where month t-k is
+    not a sorted neighbour)."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    f = np.asarray(forecast, dtype=np.float64)
+    if f.shape != (len(df),):
+        raise ValueError("forecast must hold one value per row of df")
+    ids = _firm_ids(df[id_col], df[date_col])
+    if ids is None:
+        raise ValueError(f"held_sorted_portfolios: {id_col!r} must hold whole-number firm ids and {date_col!r} "
+                         "datetime64 or integer months")
+    panel, p = _sorted_panel(df, f, return_col, weight_col, nport, breakpoints, universe, nyse_breakpoints, date_col,
+                             ids=ids, id_col=id_col)
+    h = _E.held_portfolios(panel, p, hold, ret=1, weight=panel.cols[2] if weight_col is not None else None)
+    s = _E.portfolio_summary(h, nw_lags)
+    return _held_frames(*(t.cpu().numpy() for t in (h.status, h.rec, h.members, h.turnover, s.mean, s.tstat, s.nobs)),
+                        panel.months, nport, date_col)
 
 
 def _dist_columns(q):
@@ -951,6 +1005,26 @@ def build_table_5(crsp_comp: pd.DataFrame, variables_dict: dict = None, nport: i
     return frames
 
 
+def build_table_5_held(crsp_comp: pd.DataFrame, hold: int, nport: int = 10, nyse_breakpoints: bool = False, **cfg):
+    """build_table_5's portfolios held for ``hold`` months (build-defined A19; no reference line), from
+    the same ONE device pipeline run plus one launch: for every Table-2 model and universe the
+    overlapping-cohort strategy of held_sorted_portfolios on that problem's sorts, value weights from
+    ``me``.  ``cfg``: further PipelineConfig fields.  Returns {(model name, universe name): (monthly,
+    summary)} in held_sorted_portfolios' frame format."""
+    panel, model_cols = _pipeline_panel(crsp_comp, None)
+    pcfg = _LW.PipelineConfig(**dict(cfg, portfolios=int(nport), portfolio_nyse_breakpoints=bool(nyse_breakpoints),
+                                     portfolio_hold=hold))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    h, s = out.held, out.held_summary
+    host = [t.cpu().numpy() for t in (h.status, h.rec, h.members, h.turnover, s.mean, s.tstat, s.nobs)]
+    frames = {}
+    for j, k in enumerate(out.portfolio_problems):
+        prob = out.res.problems[k]
+        key = (out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level])
+        frames[key] = _held_frames(*(x[j] for x in host), panel.months, int(nport))
+    return frames
+
+
 def _month_rows(index, months, what):
     """Row of ``index`` (dates, or the panel's own month numbers) for each of the panel's
     ``months``, matched by calendar year and month; -1 where the month is absent."""
@@ -990,7 +1064,9 @@ def build_table_alphas(crsp_comp: pd.DataFrame, factors: pd.DataFrame, rf=None, 
     column name of ``factors`` (which is then no factor) or a Series indexed by date; it is
     subtracted from the portfolios' returns, not from the spread.  ``models``: {name: [factor
     columns]}, default {"CAPM": [the first column], "FF": all columns}.  ``cfg``: further
-    PipelineConfig fields (window, min_periods, lag, nw_lags, alpha_nw_lags, ...).
+    PipelineConfig fields (window, min_periods, lag, nw_lags, alpha_nw_lags, ...); with
+    ``portfolio_hold=k`` among them the regressions are those of the portfolios held for k months
+    (build_table_5_held's monthly records) instead of the one-month portfolios.
     Returns {(model name, universe name): DataFrame} with build_table_5's portfolio labels as rows and
     the columns (weighting, "", Avg / Std / Shp) -- the mean and standard deviation of the (excess)
     return over the first model's months and the annualised Sharpe ratio Avg / Std * sqrt(12) -- and
@@ -1018,7 +1094,7 @@ def build_table_alphas(crsp_comp: pd.DataFrame, factors: pd.DataFrame, rf=None, 
     pcfg = _LW.PipelineConfig(**dict(cfg, portfolios=int(nport), alpha_factors=F, alpha_rf=R,
                                      alpha_models=[[fcols.index(c) for c in cols] for cols in models.values()]))
     out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
-    a = out.portfolio_alphas
+    a = out.portfolio_alphas if pcfg.portfolio_hold is None else out.held_alphas
     coef, t, th, stat, nobs = (x.cpu().numpy() for x in (a.coef, a.tstat, a.tstat_hac, a.stat, a.nobs))
     labels = pd.Index(list(range(int(nport))) + ["H-L"], name="portfolio")
     frames = {}

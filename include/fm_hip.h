@@ -68,6 +68,10 @@
  *                      forecast-sorted portfolio's return on factor returns (CAPM and three-factor
  *                      alphas with classical and Newey-West t-statistics, the second table of the
  *                      paper's portfolio section); no reference line
+ *   fm_portfolio_hold <- build-defined extension A19; no reference line: the forecast-sorted
+ *                      portfolios held for k months as overlapping cohorts (the calendar-time
+ *                      strategy of Jegadeesh and Titman), its monthly return record, the cohorts'
+ *                      sizes and persistence, and the monthly name turnover
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -224,7 +228,7 @@ const char* fm_last_error(void);
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
     X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)      \
-    X(fm_alpha_args)
+    X(fm_alpha_args) X(fm_hold_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -909,6 +913,84 @@ typedef struct fm_alpha_args {
 } fm_alpha_args;
 
 int fm_portfolio_alpha(const fm_alpha_args* args, void* stream);
+
+/* fm_portfolio_hold: the forecast-sorted portfolios held for `hold` = k months as overlapping
+ * cohorts (build-defined extension A19; no reference line; the calendar-time strategy of Jegadeesh
+ * and Titman 1993 applied to the paper's Table 5 sorts).  In month t the strategy holds, per sort
+ * and portfolio, the k cohorts formed in months t, t-1, .., t-k+1; its return is a monthly series
+ * with fm_portfolio_sort's record layout, so fm_ts_summary and fm_portfolio_alpha read it as they
+ * read the sort's own.  Inputs: the month-sorted panel's seg_off [nseg+1], month_index [nseg] and
+ * nrows = seg_off[nseg]; link_prev [nrows], fm_month_links with step -1; port [nsel][nrows], the
+ * sorts' portfolio bytes (a value >= nport: the row is in no portfolio); status [nsel][nseg] (1 = a
+ * sorted month); ret [nrows]; weight [nrows] or NULL; sort_rec [nsel][nseg][nport+1][4] or NULL, the
+ * sorts' own records, read for the predicted columns 1 and 3 only.
+ * Ancestors.  For row i of segment t: anc_0 = i, and for a = 1..k
+ *   anc_a = seg_off[t-a] + link_prev[anc_{a-1}];
+ *   a hop is missing when t - a < 0, or when the link is negative or not below the length of
+ *   segment t - a (a stale or foreign link array never causes a read outside [0, nrows)); all later
+ *   hops are then missing too.
+ * Membership.  Row i is a member of cohort (j, t, a, q) when anc_a exists and port[j][anc_a] == q <
+ * nport.  status is not consulted: fm_portfolio_sort writes 255 in unsorted months.
+ * Outputs per sort j and month t:
+ *   members [j][t][a][q], a = 0..k: the number of members;
+ *   stay    [j][t][a][q], a = 0..k: the members whose own port[j][i] == q (age 0: all of them);
+ *   cohort_n[j][t][a][q][2], a = 0..k-1: slot 0 the members with a finite ret[i], slot 1 those that
+ *            also have a finite weight[i] > 0 (weight NULL: 0);
+ *   cohort  [j][t][a][q][2], a = 0..k-1: slot 0 sum(ret) / n over the first set, slot 1
+ *            sum(w * ret) / sum(w) over the second, with the return and weight of the row in month
+ *            t -- the month-t return of the stocks chosen a months earlier, equal-weighted among
+ *            the cohort's survivors or weighted by their current weight; an empty set gives NaN;
+ *   status_out[j][t]: 1 when the month is complete, else 0.  Complete: t - k + 1 >= 0 and for every
+ *            a < k, status[j][t-a] == 1 and month_index[t-a] == month_index[t] - a;
+ *   rec     [j][t][nport+1][4]: for a complete month and q < nport, column 0 = (c_0 + c_1 + .. +
+ *            c_{k-1}) / k over the equal-weighted cohort values, added in age order from c_0, every
+ *            operation rounded on its own; column 2 the same over the value-weighted cohort values;
+ *            columns 1 and 3 the same average of sort_rec[j][t-a][q][1] and [3], the formation
+ *            months' predicted returns (NaN when sort_rec is NULL).  A NaN term makes the entry NaN.
+ *            Row nport = row nport-1 minus row 0, one rounding per column.  A month that is not
+ *            complete is all NaN;
+ *   turnover[j][t][q]: the share of names the strategy replaces in month t (the cohort formed in
+ *            t - k leaves, the new one enters): (1.0 - (double)stay[..][k][q] / (double)
+ *            members[..][0][q]) / k, every operation rounded on its own, when the month is
+ *            complete, t - k >= 0, status[j][t-k] == 1, month_index[t-k] == month_index[t] - k and
+ *            members[..][0][q] > 0; NaN otherwise.  k = 1: each portfolio's month-to-month name
+ *            turnover.
+ * Months may have any length (a wave takes 64 rows wherever they lie; none of the sorts' 16,384-row
+ * limit applies).  Every output of (j, t) depends on the rows of months t-k..t alone.  Every sum of
+ * (j, t, a, q) runs in one fixed order: wave w of four starts from +0.0 and adds the terms of the
+ * month's rows 64 (w + 4 i) .. 64 (w + 4 i) + 63, i = 0, 1, .., in ascending row order, then the
+ * four wave sums are added in wave order.  Two calls give the same bits, and so does a call with
+ * other sorts beside sort j.  No floating-point atomics, no workspace, no host sync; the launch is
+ * capture-safe.  Refused with FM_EINVAL before any launch (the message names the field): a NULL
+ * required pointer, nport outside 2..FM_MAX_PORTS, hold outside 1..FM_MAX_HOLD, nsel outside
+ * 0..FM_MAX_SORTS, a negative dimension, an output overlapping an input.  nseg == 0, nrows == 0 or
+ * nsel == 0 is a valid empty call: nothing is launched and nothing is written.  Zero-initialize the
+ * struct (it grows at the end). */
+#define FM_MAX_HOLD 36
+typedef struct fm_hold_args {
+    const int64_t* seg_off;      /* [nseg+1] */
+    const int32_t* month_index;  /* [nseg] calendar month number, strictly ascending */
+    const int32_t* link_prev;    /* [nrows] fm_month_links with step -1 */
+    const uint8_t* port;         /* [nsel][nrows] */
+    const uint32_t* status;      /* [nsel][nseg] 1 = sorted month */
+    const double* ret;           /* [nrows] */
+    const double* weight;        /* [nrows] or NULL */
+    const double* sort_rec;      /* [nsel][nseg][nport+1][4] or NULL */
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t nseg;
+    int32_t nsel;                /* 0 .. FM_MAX_SORTS */
+    int32_t nport;               /* 2 .. FM_MAX_PORTS */
+    int32_t hold;                /* 1 .. FM_MAX_HOLD */
+    int32_t* members;            /* [nsel][nseg][hold+1][nport] */
+    int32_t* stay;               /* [nsel][nseg][hold+1][nport] */
+    int32_t* cohort_n;           /* [nsel][nseg][hold][nport][2] */
+    double* cohort;              /* [nsel][nseg][hold][nport][2] */
+    uint32_t* status_out;        /* [nsel][nseg] */
+    double* rec;                 /* [nsel][nseg][nport+1][4] */
+    double* turnover;            /* [nsel][nseg][nport] */
+} fm_hold_args;
+
+int fm_portfolio_hold(const fm_hold_args* args, void* stream);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
