@@ -217,6 +217,18 @@ class HoldArgs(C.Structure):
     ]
 
 
+FM_MAX_GROUPS = 256
+FM_GADJ_DEMEAN, FM_GADJ_MEAN, FM_GADJ_ZSCORE = 0, 1, 2
+
+
+class GroupAdjArgs(C.Structure):
+    _fields_ = [
+        ("src", _p), ("src_stride", _i64), ("dst", _p), ("dst_stride", _i64), ("seg_off", _p), ("group", _p),
+        ("level", _p), ("nrows", _i64), ("ncols", _i32), ("nseg", _i32), ("ngroups", _i32), ("mode", _i32),
+        ("min_count", _i32), ("min_level", _i32), ("gcount", _p), ("gmean", _p), ("gsd", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -261,6 +273,8 @@ _SIGS = {
     "fm_horizon_return": (_i32, [C.POINTER(HorizonArgs), _p]),
     "fm_portfolio_alpha": (_i32, [C.POINTER(AlphaArgs), _p]),
     "fm_portfolio_hold": (_i32, [C.POINTER(HoldArgs), _p]),
+    "fm_group_adjust": (_i32, [C.POINTER(GroupAdjArgs), _p]),
+    "fm_group_adjust_batch": (_i32, [_i32]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -280,7 +294,7 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs,
             "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
             "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs,
-            "fm_hold_args": HoldArgs}
+            "fm_hold_args": HoldArgs, "fm_gadj_args": GroupAdjArgs}
 
 _lib = None
 

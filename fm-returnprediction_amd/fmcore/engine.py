@@ -7,10 +7,10 @@ functions raise.
 Layout in HBM (``DevicePanel``): the panel's C columns with rows sorted by (month, input
 order) -- month segments are CSR ``seg_off[T+1]`` -- as an FP64 SoA block ``cols[C, n]``
 and/or the split layout ``planes[2, C, n]`` (uint32 high / low words: the selects read the
-high plane, the Gram both), plus optional ``me`` (FP64) and ``nyse`` (uint8) rows and a
-uint8 universe ``level`` per row.  A panel built with ``layout="planes"`` holds no FP64
-columns at all (half the HBM): the whole Table-2 pass reads the planes, and consumers of
-FP64 columns (clip, forecasts, moments) get them from ``values()``.
+high plane, the Gram both), plus optional ``me`` (FP64), ``nyse`` (uint8) and ``group`` (int32
+group / industry code) rows and a uint8 universe ``level`` per row.  A panel built with
+``layout="planes"`` holds no FP64 columns at all (half the HBM): the whole Table-2 pass reads
+the planes, and consumers of FP64 columns (clip, forecasts, moments) get them from ``values()``.
 """
 from __future__ import annotations
 
@@ -132,6 +132,8 @@ class DevicePanel:
     chunk_policy: Optional[tuple] = None    # Gram plan of the GLOBAL panel (chunk_policy()), sharded runs
     row_origin: int = 0                     # global row of this panel's row 0 (balanced plans)
     planes_version: int = -1                # cols._version when the planes were made from cols
+    group: Optional[torch.Tensor] = None    # [n] int32: each row's group (industry) code, month-major; < 0: none
+    ngroups: int = 0                        # codes 0 .. ngroups-1 (at most MAX_GROUPS)
     ids: Optional[torch.Tensor] = None      # [n] int64: each row's firm id, month-major, ascending within a month
     month_index: Optional[np.ndarray] = None   # [T] int32 (host): each segment's calendar month number, ascending
 
@@ -274,14 +276,34 @@ def gather_layout(raw, perm, layout="f64"):
     return cols, planes
 
 
+def _check_group(who, group, ngroups, n_in):
+    """Host group codes of an ingest -> (int32 [n_in], ngroups); ``ngroups`` None: max code + 1."""
+    group = np.asarray(group)
+    if group.dtype.kind not in "iu" or group.shape != (n_in,):
+        raise ValueError(f"{who}: group must hold one integer code per input row")
+    if len(group) and (group.min() < -(2 ** 31) or group.max() >= 2 ** 31):
+        raise ValueError(f"{who}: group codes must fit 32 bits")
+    if ngroups is None:
+        ngroups = max(int(group.max()) + 1 if len(group) else 1, 1)
+    ngroups = int(ngroups)
+    if ngroups < 1 or ngroups > MAX_GROUPS:
+        raise ValueError(f"{who}: ngroups must be 1..{MAX_GROUPS}, got {ngroups}")
+    return group.astype(np.int32), ngroups
+
+
 def panel_from_arrays(arrays: Sequence[np.ndarray], names, labels, me=None, nyse=None,
-                      device=None, layout="f64", ids=None):
+                      device=None, layout="f64", ids=None, group=None, ngroups=None):
     """Upload host columns (original row order) and permute them month-major on device, into
     the panel's ``layout`` ("f64", "planes": the split layout only, "both").  ``ids``: each input
     row's integer firm id; the panel then carries firm identity (``ids``, ``month_index``), which
     the month links and the multi-month returns need: the labels must then be datetime64 or
     integer month numbers (``month_index``), and a month's rows must arrive in ascending id order
-    (``month_links`` checks it)."""
+    (``month_links`` checks it).  ``group``: one integer group (industry) code per input row
+    (``group_codes`` makes them from labels; a negative code: no group), permuted month-major like
+    ``nyse``, with ``ngroups`` (default: the largest code + 1; more than MAX_GROUPS: ValueError) --
+    what ``group_adjust`` reads."""
+    if group is not None:
+        group, ngroups = _check_group("panel_from_arrays", group, ngroups, len(labels))
     device = device or require_device()
     _, uniq, order, seg_off = month_segments(labels)
     if ids is not None:
@@ -305,6 +327,9 @@ def panel_from_arrays(arrays: Sequence[np.ndarray], names, labels, me=None, nyse
                     seg_off_h=seg_off, months=uniq, me=me_t, nyse=nyse_t, order=order, planes=planes)
     if cols is not None and planes is not None:
         p.planes_version = cols._version
+    if group is not None:
+        p.group = torch.from_numpy(group).to(device).index_select(0, perm)
+        p.ngroups = ngroups
     if ids is not None:
         _set_ids(p, torch.from_numpy(ids.astype(np.int64)).to(device).index_select(0, perm))
     return p
@@ -1994,7 +2019,8 @@ def rank_transform(panel: DevicePanel, cols=None, method="average", scale="pct",
     res = DevicePanel(cols=out, names=list(panel.names), seg_off=panel.seg_off, seg_off_h=panel.seg_off_h,
                       months=panel.months, me=panel.me, nyse=panel.nyse, order=panel.order,
                       chunk_rows=panel.chunk_rows, chunk_split=panel.chunk_split, chunk_policy=panel.chunk_policy,
-                      row_origin=panel.row_origin, ids=panel.ids, month_index=panel.month_index)
+                      row_origin=panel.row_origin, group=panel.group, ngroups=panel.ngroups, ids=panel.ids,
+                      month_index=panel.month_index)
     _share_links(panel, res)
     res.rank_nvalid = nvalid
     return res
@@ -2100,7 +2126,8 @@ def horizon_panel(panel: DevicePanel, h, ret="retx", name=None):
     res = DevicePanel(cols=out, names=list(panel.names) + [name], seg_off=panel.seg_off, seg_off_h=panel.seg_off_h,
                       months=panel.months, me=panel.me, nyse=panel.nyse, order=panel.order,
                       chunk_rows=panel.chunk_rows, chunk_split=panel.chunk_split, chunk_policy=panel.chunk_policy,
-                      row_origin=panel.row_origin, ids=panel.ids, month_index=panel.month_index)
+                      row_origin=panel.row_origin, group=panel.group, ngroups=panel.ngroups, ids=panel.ids,
+                      month_index=panel.month_index)
     _share_links(panel, res)
     return res
 
@@ -2207,6 +2234,145 @@ def held_portfolios(panel: DevicePanel, ports: Portfolios, hold, ret="retx", wei
     nport = int(ports.rec.shape[-2]) - 1
     return portfolio_hold(panel.seg_off, panel.month_index_device(), month_links(panel, -1), ports.port, ports.status,
                           column_vector(panel, ret), weight=weight, nport=nport, hold=hold, sort_rec=ports.rec)
+
+
+# ------------------------------------------------------------------------------------------
+# Within-group (industry) adjustment of the characteristics (A20)
+# ------------------------------------------------------------------------------------------
+MAX_GROUPS = L.FM_MAX_GROUPS
+GADJ_MODES = {"demean": L.FM_GADJ_DEMEAN, "mean": L.FM_GADJ_MEAN, "zscore": L.FM_GADJ_ZSCORE}
+
+
+@dataclass
+class GroupStats:
+    mean: torch.Tensor             # [C, T, ngroups] float64: the group mean, NaN where n < max(1, min_count)
+    sd: Optional[torch.Tensor]     # [C, T, ngroups] float64: the ddof-1 sd, NaN where n < 2 (mode "zscore" only)
+    count: torch.Tensor            # [C, T, ngroups] int32: the group's eligible rows
+
+
+def group_codes(labels):
+    """Group labels (integers such as SIC codes, or strings) -> (codes int32, uniques): a sorted
+    factorisation on the host, code k = the k-th smallest distinct label; a missing label (None,
+    NaN, NaT) becomes -1, "no group"."""
+    import pandas as pd
+    codes, uniq = pd.factorize(np.asarray(labels) if not hasattr(labels, "dtype") else labels, sort=True)
+    return np.asarray(codes).astype(np.int32), np.asarray(uniq)
+
+
+def group_adjust_columns(seg_off, x, group, ngroups, mode="demean", min_count=1, level=None, min_level=0, out=None,
+                         stats=False):
+    """A20 on plain device tensors: every row of ``x`` (float64 [C, rows], rows sorted by month,
+    months ``seg_off`` int64 [T+1]) adjusted within the groups ``group`` (int32 [rows], codes
+    0..ngroups-1, any other value: no group) of each month -- ``mode`` "demean" x - group mean,
+    "mean" the group mean, "zscore" (x - mean) / ddof-1 sd (fm_group_adjust; the definition is in
+    fm_hip.h).  Groups with fewer than ``min_count`` rows, rows without a group and, with ``level``
+    (uint8 [rows]), rows below ``min_level`` give NaN.  Returns (or fills ``out``) float64 [C, rows];
+    with ``stats`` returns (out, GroupStats).  One launch, no host sync."""
+    if mode not in GADJ_MODES:
+        raise ValueError(f"group_adjust: mode must be one of {sorted(GADJ_MODES)}, got {mode!r}")
+    ngroups = int(ngroups)
+    if ngroups < 1 or ngroups > MAX_GROUPS:
+        raise ValueError(f"group_adjust: ngroups must be 1..{MAX_GROUPS}, got {ngroups}")
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or min_count < 0:
+        raise ValueError(f"group_adjust: min_count must be an integer >= 0, got {min_count!r}")
+    if x.dtype != torch.float64 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("group_adjust: x must be a float64 [C, rows] tensor with contiguous rows")
+    dev = x.device
+    C, n = int(x.shape[0]), int(x.shape[1])
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError("group_adjust: seg_off must be an int64 [T+1] tensor on the values' device")
+    seg_off = seg_off.contiguous()
+    T = int(seg_off.shape[0]) - 1
+    for t, dt, what in ((group, torch.int32, "group"), (level, torch.uint8, "level")):
+        if t is None and what == "level":
+            continue
+        if t is None or t.dtype != dt or t.dim() != 1 or t.shape[0] != n or t.device != dev:
+            raise ValueError(f"group_adjust: {what} must be a {dt} [{n}] tensor on {dev}")
+    group = group.contiguous()
+    level = None if level is None else level.contiguous()
+    if out is None:
+        out = torch.empty((C, n), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (C, n) or out.device != dev or \
+            (n > 1 and out.stride(1) != 1):
+        raise ValueError(f"group_adjust: out must be a float64 [{C}, {n}] tensor on {dev} with contiguous rows")
+    if out.data_ptr() == x.data_ptr() and C * n:
+        raise ValueError("group_adjust: out must not be the input's own memory")
+    empty = not (C and n and T)
+    st = None
+    if stats:
+        def table(dtype, fill):
+            # an empty call launches nothing: its tables are then what a launch would have written
+            if empty:
+                return torch.full((C, T, ngroups), fill, dtype=dtype, device=dev)
+            return torch.empty((C, T, ngroups), dtype=dtype, device=dev)
+        st = GroupStats(mean=table(torch.float64, float("nan")),
+                        sd=table(torch.float64, float("nan")) if mode == "zscore" else None,
+                        count=table(torch.int32, 0))
+    a = L.GroupAdjArgs(src=x.data_ptr(), src_stride=x.stride(0) if C > 1 else max(n, 1), dst=out.data_ptr(),
+                       dst_stride=out.stride(0) if C > 1 else max(n, 1), seg_off=seg_off.data_ptr(),
+                       group=group.data_ptr(), level=_ptr(level), nrows=n, ncols=C, nseg=T, ngroups=ngroups,
+                       mode=GADJ_MODES[mode], min_count=int(min_count), min_level=int(min_level),
+                       gcount=None if st is None else st.count.data_ptr(),
+                       gmean=None if st is None else st.mean.data_ptr(),
+                       gsd=None if st is None or st.sd is None else st.sd.data_ptr())
+    _kcall("fm_group_adjust", "fm_group_adjust", L.C.byref(a), _stream())
+    _remember("fm_group_adjust", "fm_group_adjust", a, x, out, seg_off, group, level, st)
+    return (out, st) if stats else out
+
+
+def group_adjust(panel: DevicePanel, cols=None, mode="demean", min_count=1, level=None, min_level=0, out=None,
+                 stats=False):
+    """A20 on a panel: the chosen columns (names or indices; default all) adjusted within the panel's
+    groups (``panel.group``, ``panel.ngroups``) of each month (``group_adjust_columns``), every other
+    column copied unchanged.  Returns a new f64-layout ``DevicePanel`` that shares the input's
+    segments, ``me``, ``nyse``, ``months``, ``order``, ``group``, ``ids``, ``month_index`` and links
+    (``out``: its [C, n] float64 column block, not the input's), as ``rank_transform`` does; with
+    ``stats`` the chosen columns' ``GroupStats`` ([len(cols), T, ngroups]) is its ``group_stats``
+    attribute."""
+    if mode not in GADJ_MODES:
+        raise ValueError(f"group_adjust: mode must be one of {sorted(GADJ_MODES)}, got {mode!r}")
+    if panel.group is None:
+        raise ValueError("group_adjust: the panel carries no group codes (build it with group=...)")
+    src = panel.values()
+    C, n = panel.ncols, panel.nrows
+    idx = list(range(C)) if cols is None else [panel.col(c) if isinstance(c, str) else int(c) for c in cols]
+    if any(i < 0 or i >= C for i in idx) or len(set(idx)) != len(idx):
+        raise ValueError("group_adjust: cols must be distinct columns of the panel")
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.dtype != torch.float64 or out.shape != src.shape or out.device != src.device or out.stride(1) != 1:
+        raise ValueError("group_adjust: out must be a float64 tensor of the panel's [C, n] shape on its device")
+    if out.data_ptr() == src.data_ptr():
+        raise ValueError("group_adjust: out must not be the panel's own columns")
+    for i in sorted(set(range(C)) - set(idx)):
+        out[i].copy_(src[i])
+    # consecutive columns go in one launch (all 14 predictors of the pipeline: one)
+    runs, k = [], 0
+    while k < len(idx):
+        e = k + 1
+        while e < len(idx) and idx[e] == idx[e - 1] + 1:
+            e += 1
+        runs.append((k, e))
+        k = e
+    parts = []
+    for k, e in runs:
+        r = group_adjust_columns(panel.seg_off, src[idx[k]:idx[k] + e - k, :n], panel.group, panel.ngroups, mode=mode,
+                                 min_count=min_count, level=level, min_level=min_level,
+                                 out=out[idx[k]:idx[k] + e - k, :n], stats=stats)
+        if stats:
+            parts.append(r[1])
+    res = DevicePanel(cols=out, names=list(panel.names), seg_off=panel.seg_off, seg_off_h=panel.seg_off_h,
+                      months=panel.months, me=panel.me, nyse=panel.nyse, order=panel.order,
+                      chunk_rows=panel.chunk_rows, chunk_split=panel.chunk_split, chunk_policy=panel.chunk_policy,
+                      row_origin=panel.row_origin, group=panel.group, ngroups=panel.ngroups, ids=panel.ids,
+                      month_index=panel.month_index)
+    _share_links(panel, res)
+    if stats:
+        cat = (lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)) if parts else None
+        res.group_stats = None if not parts else GroupStats(
+            mean=cat([p.mean for p in parts]), sd=None if parts[0].sd is None else cat([p.sd for p in parts]),
+            count=cat([p.count for p in parts]))
+    return res
 
 
 def segment_moments(panel: DevicePanel, level=None, min_level=0, finite_only=True, cols=None):

@@ -85,15 +85,22 @@ def arrow_host_columns(source, value_cols: Sequence[str], date_col: str = "mthca
 
 def panel_from_arrow(source, value_cols: Sequence[str], date_col: str = "mthcaldt",
                      me_col: Optional[str] = None, exch_col: Optional[str] = None,
-                     exch_value: str = "N", device=None, layout="f64") -> "E.DevicePanel":
+                     exch_value: str = "N", device=None, layout="f64",
+                     group_col: Optional[str] = None) -> "E.DevicePanel":
     """A pyarrow Table or a Parquet path -> month-sorted DevicePanel (one pinned H2D copy),
     in ``layout`` ("f64"; "planes": the split high / low-word layout only, gathered from the
-    raw words on the device; "both")."""
+    raw words on the device; "both").  ``group_col``: an integer or string column of group
+    (industry) labels, factorised with sorted uniques (``engine.group_codes``; nulls: no group)
+    into the panel's ``group`` codes; the labels of the codes are its ``group_labels`` attribute."""
     import pyarrow.compute as pc
     import torch
     device = device or E.require_device()
-    need = list(value_cols) + [date_col] + [c for c in (me_col, exch_col) if c]
+    need = list(value_cols) + [date_col] + [c for c in (me_col, exch_col, group_col) if c]
     tab = _read(source, need)
+    group = glabels = None
+    if group_col:
+        group, glabels = E.group_codes(tab.column(group_col).to_pandas())
+        group, ngroups = E._check_group("panel_from_arrow", group, max(len(glabels), 1), tab.num_rows)
     _, uniq, order, seg_off = month_order(tab.column(date_col).to_numpy())
     n = tab.num_rows
     extra = 1 if me_col else 0
@@ -120,5 +127,9 @@ def panel_from_arrow(source, value_cols: Sequence[str], date_col: str = "mthcald
                           months=uniq, me=me_t, nyse=nyse_t, order=order, planes=planes)
     if cols is not None and planes is not None:
         panel.planes_version = cols._version
+    if group is not None:
+        panel.group = torch.from_numpy(group).to(device).index_select(0, perm)
+        panel.ngroups = ngroups
+        panel.group_labels = glabels
     torch.cuda.current_stream().synchronize()   # the pinned stage must outlive the copy
     return panel

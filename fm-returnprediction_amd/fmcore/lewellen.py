@@ -117,6 +117,17 @@ class PipelineConfig:
     # factors are not this table): ValueError otherwise, and for a first dimension other than the
     # panel's month count.  None = no launch more.  In front of ``extrapolate``: tests pin the seven
     # trailing fields.
+    # A20 (in front of ``alpha_factors``, whose place tests pin): ``group_adjust`` = "demean", "mean"
+    # or "zscore" replaces the predictor columns ``group_adjust_cols`` (names; None: every predictor
+    # of every model, never the dependent column) by their adjustment within the panel's groups
+    # (industries) of each month (engine.group_adjust: x minus the group mean, the group mean, the
+    # within-group z-score; groups below ``group_min_count`` rows give NaN) before anything else:
+    # the adjusted columns are winsorized like any others, ``rank`` ranks them, and every forecast
+    # stage reads them.  Needs a panel with group codes and excludes standardize: ValueError
+    # otherwise.  None = no launch more.
+    group_adjust: Optional[str] = field(default=None, kw_only=True)
+    group_adjust_cols: Optional[Sequence[str]] = field(default=None, kw_only=True)
+    group_min_count: int = field(default=1, kw_only=True)
     alpha_factors: Optional[object] = field(default=None, kw_only=True)
     alpha_models: Optional[Sequence[Sequence[int]]] = field(default=None, kw_only=True)
     alpha_rf: Optional[object] = field(default=None, kw_only=True)
@@ -182,6 +193,8 @@ class PipelineResult:
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
     y_col: str = "retx"                                   # the dependent column (cfg.horizon > 1: f"{y}_{h}m")
+    group_stats: Optional[E.GroupStats] = None            # cfg.group_adjust: [len(group_adjusted), T, ngroups]
+    group_adjusted: Optional[List[str]] = None            # the adjusted columns' names, in panel order
     held: Optional[E.HeldPortfolios] = None               # cfg.portfolio_hold: tensors with a leading [nsort] dimension
     held_summary: Optional[E.Summary] = None              # [nsort, nport+1, 4]
     held_alphas: Optional[E.PortfolioAlphas] = None       # with cfg.alpha_factors: [nsort, nport+1, 2, M, ...]
@@ -230,13 +243,25 @@ def local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx")
 
 
 def _local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx"):
-    """local_stage, plus the panel the Gram read (the ranked one under cfg.rank) and the models."""
+    """local_stage, plus the panel the Gram read (the group-adjusted one under cfg.group_adjust, the
+    ranked one under cfg.rank), the models and, under cfg.group_adjust, (GroupStats, adjusted names)."""
     cuts = None
     shift = None
     inv_scale = None
     level, bp = None, None
     nlevels = 1
     models, names = build_models(panel, model_cols, y=y, fig1=cfg.fig1, universes=cfg.universes)
+    gadj = None
+    if cfg.group_adjust is not None:
+        # A20 (build-defined): the raw predictor columns (never y) adjusted within the month's groups,
+        # before the cuts: the adjusted columns are winsorized (and ranked) like any others
+        check_group_adjust(cfg, panel, model_cols, y)
+        adjusted = sorted({i for m in models for i in m.xs} - {panel.col(y)})
+        if cfg.group_adjust_cols is not None:
+            adjusted = sorted({panel.col(c) for c in cfg.group_adjust_cols})
+        panel = E.group_adjust(panel, cols=adjusted, mode=cfg.group_adjust, min_count=cfg.group_min_count,
+                               stats=True)
+        gadj = (panel.group_stats, [panel.names[i] for i in adjusted])
     ranked = None
     if cfg.rank is not None:
         # A13 (build-defined): every predictor column (never y) becomes its average-tie rank
@@ -281,7 +306,7 @@ def _local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx"
                     moments=cfg.forecasts)
     if cfg.standardize:
         E.drop_degenerate_months(res, models, cuts.sd)
-    return res, names, cuts, level, bp, panel, models
+    return res, names, cuts, level, bp, panel, models, gadj
 
 
 def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo=0, seg_hi=None,
@@ -371,6 +396,33 @@ def check_hold(cfg: PipelineConfig, panel=None):
         raise ValueError("PipelineConfig: portfolio_hold needs a panel with firm ids (build it with ids=...)")
 
 
+def check_group_adjust(cfg: PipelineConfig, panel=None, model_cols=None, y="retx"):
+    """The rules of ``PipelineConfig.group_adjust`` (no device work); ``panel``: the run's panel, when
+    there is one (touched only when group_adjust is set)."""
+    mode = cfg.group_adjust
+    if mode is None:
+        if cfg.group_adjust_cols is not None:
+            raise ValueError("PipelineConfig: group_adjust_cols needs group_adjust")
+        return
+    if mode not in E.GADJ_MODES:
+        raise ValueError(f"PipelineConfig: group_adjust must be one of {sorted(E.GADJ_MODES)}, got {mode!r}")
+    k = cfg.group_min_count
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+        raise ValueError(f"PipelineConfig: group_min_count must be an integer >= 0, got {k!r}")
+    if cfg.standardize:
+        raise ValueError("PipelineConfig: group_adjust excludes standardize (z-scores of the month on top of "
+                         "an adjustment within its groups; use group_adjust='zscore')")
+    if cfg.group_adjust_cols is not None:
+        model_cols = model_cols or table2_models()
+        predictors = {c for cols in model_cols.values() for c in cols} | (set(FIG1_VARS) if cfg.fig1 else set())
+        predictors.discard(y)
+        unknown = [c for c in cfg.group_adjust_cols if c not in predictors]
+        if isinstance(cfg.group_adjust_cols, str) or unknown:
+            raise ValueError(f"PipelineConfig: group_adjust_cols must name predictors of the models, not {unknown}")
+    if panel is not None and panel.group is None:
+        raise ValueError("PipelineConfig: group_adjust needs a panel with group codes (build it with group=...)")
+
+
 def horizon_column(panel: E.DevicePanel, cfg: PipelineConfig, y="retx"):
     """The panel and dependent column of a run: (panel, y) at horizon 1; else the column
     f"{y}_{h}m", appended by engine.horizon_panel when the panel lacks it."""
@@ -392,6 +444,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     check_extrapolate(cfg)
     check_alphas(cfg, None if panel is None else panel.nseg)
     check_hold(cfg, panel)
+    check_group_adjust(cfg, panel, model_cols, y)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
         if on and cfg.standardize:
@@ -402,7 +455,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     if cfg.extrapolate is not None and (panel.ids is None or panel.month_index is None):
         raise ValueError("PipelineConfig: extrapolate needs a panel with firm ids (build it with ids=...)")
     panel, y = horizon_column(panel, cfg, y)
-    res, names, cuts, level, bp, gpanel, models = _local_stage(panel, cfg, model_cols, y)
+    res, names, cuts, level, bp, gpanel, models, gadj = _local_stage(panel, cfg, model_cols, y)
     ix, summ, roll, pred, pst = time_series_stage(res, cfg)
     psumm = None
     if cfg.forecasts:
@@ -467,7 +520,8 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                           portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
                           forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
                           forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
-                          y_col=y, held=held, held_summary=held_summ, held_alphas=held_alphas, portfolio_alphas=alphas,
+                          y_col=y, group_stats=None if gadj is None else gadj[0],
+                          group_adjusted=None if gadj is None else gadj[1], held=held, held_summary=held_summ, held_alphas=held_alphas, portfolio_alphas=alphas,
                           extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
 
 

@@ -8,7 +8,8 @@ Mirrored (same names, signatures, return types and row/column/index order):
   build_table_2    reference :674-868   9 FM passes batched into one Gram pass on device
   create_figure_1  reference :871-957   F1 OLS + 120-month rolling means on device
 Extensions the north star names (not in the reference; parity unpinned):
-  standardize, rank_transform, monthly_coefficients, rolling_coefficients, expected_return_forecasts,
+  standardize, rank_transform, group_adjust (within-industry adjustment; every lewellen_pipeline /
+  build_table_* **cfg also takes group_col=...), monthly_coefficients, rolling_coefficients, expected_return_forecasts,
   predictive_slope_regressions, forecast_sorted_portfolios, forecast_distribution,
   forecast_comparison, lewellen_pipeline, build_table_5, build_table_3, build_table_4,
   horizon_returns, build_table_2_horizon (multi-month returns: paper Tables 8 and 9; every
@@ -164,6 +165,46 @@ def rank_transform(crsp_comp: pd.DataFrame, varlist: list, date_col: str = "mthc
         level = _E.universe(panel)[2]
     r = _E.rank_transform(panel, method=method, scale=scale, level=level,
                           min_level=_UNIVERSE_LEVEL[universe]).cols.cpu().numpy()
+    for i, v in enumerate(varlist):
+        col = np.full(len(df), np.nan)
+        col[panel.order] = r[i]
+        df[v] = col
+    return df
+
+
+def group_adjust(crsp_comp: pd.DataFrame, varlist: list, group_col: str = "siccd", date_col: str = "mthcaldt",
+                 mode: str = "demean", min_count: int = 1, universe: str = None) -> pd.DataFrame:
+    """Each variable adjusted within the groups (industries) ``group_col`` of its month over its
+    non-NaN values (extension A20; the reference has no such transform): pandas'
+    ``groupby([date_col, group_col])[v].transform`` of x - mean for ``mode`` "demean" (the
+    industry-relative characteristic), of the mean for "mean" and of (x - mean) / std(ddof=1) for
+    "zscore", on the device (fm_group_adjust; sums in a fixed order, so a repeat gives the same
+    bits).  ``group_col`` holds integers or strings (at most 256 distinct values); a row with a
+    missing label, or in a group of fewer than ``min_count`` rows, gets NaN.  ``universe`` in {None,
+    "all_but_tiny", "large"} takes the groups within that get_subsets universe (from ``me`` and
+    ``primaryexch``) and gives NaN outside it.  Works on any column, a materialised forecast
+    included.  Returns a copy of the frame in the caller's row order; rows with a missing month
+    label get NaN."""
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    if mode not in _E.GADJ_MODES:
+        raise ValueError(f"group_adjust: mode must be one of {sorted(_E.GADJ_MODES)}, got {mode!r}")
+    df = crsp_comp.copy()
+    varlist = list(varlist)
+    if not varlist:
+        return df
+    arrays = [_api.as_f64(df[v]) for v in varlist]
+    codes, uniq = _E.group_codes(df[group_col])
+    me = nyse = level = None
+    if universe is not None:
+        me = _api.as_f64(df["me"])
+        nyse = (df["primaryexch"] == "N").to_numpy().astype(np.uint8)
+    panel = _E.panel_from_arrays(arrays, varlist, df[date_col].values, me=me, nyse=nyse, group=codes,
+                                 ngroups=max(len(uniq), 1))
+    if universe is not None:
+        level = _E.universe(panel)[2]
+    r = _E.group_adjust(panel, mode=mode, min_count=min_count, level=level,
+                        min_level=_UNIVERSE_LEVEL[universe]).cols.cpu().numpy()
     for i, v in enumerate(varlist):
         col = np.full(len(df), np.nan)
         col[panel.order] = r[i]
@@ -917,16 +958,23 @@ def forecast_comparison(df: pd.DataFrame, forecast_a, forecast_b, return_col: st
     return monthly, summary
 
 
-def _pipeline_panel(crsp_comp: pd.DataFrame, variables_dict: dict = None):
-    """The device panel and the Table-2 models of a crsp_comp frame (rows by (month, permno))."""
+def _pipeline_panel(crsp_comp: pd.DataFrame, variables_dict: dict = None, group_col: str = None):
+    """The device panel and the Table-2 models of a crsp_comp frame (rows by (month, permno));
+    ``group_col``: the frame's column of group (industry) labels, whose sorted factorisation becomes
+    the panel's group codes (what ``group_adjust=...`` in a ``**cfg`` reads)."""
     vd = variables_dict or _LW.VARIABLES_DICT
     model_cols = _LW.table2_models(vd)
     cols = list(dict.fromkeys(["retx"] + [c for xs in model_cols.values() for c in xs] + _LW.FIG1_VARS))
     df = crsp_comp.sort_values(["mthcaldt", "permno"])
     me = _api.as_f64(df["me"])
     nyse = (df["primaryexch"] == "N").to_numpy().astype(np.uint8)
+    group = ngroups = None
+    if group_col is not None:
+        group, uniq = _E.group_codes(df[group_col])
+        ngroups = max(len(uniq), 1)
     panel = _E.panel_from_arrays([_api.as_f64(df[c]) for c in cols], cols, df["mthcaldt"].values,
-                                 me=me, nyse=nyse, ids=_firm_ids(df["permno"], df["mthcaldt"]))
+                                 me=me, nyse=nyse, ids=_firm_ids(df["permno"], df["mthcaldt"]),
+                                 group=group, ngroups=ngroups)
     return panel, model_cols
 
 
@@ -978,7 +1026,7 @@ def lewellen_pipeline(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cf
     Table-2 problem; with ``horizon=k, lag>=k`` on compounded k-month returns, the paper's
     Section 4, ``nw_lags`` being the caller's choice: the paper takes 10 for 6 and 16 for 12
     months).  Returns fmcore.lewellen.PipelineResult (device tensors)."""
-    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
     return _LW.run_pipeline(panel, _LW.PipelineConfig(**cfg), model_cols=model_cols)
 
 
@@ -992,7 +1040,7 @@ def build_table_5(crsp_comp: pd.DataFrame, variables_dict: dict = None, nport: i
     (model, universe), without their uploads and refits.  ``cfg``: further PipelineConfig
     fields (window, min_periods, lag, nw_lags, ...).  Returns {(model name, universe name):
     (monthly, summary)} in forecast_sorted_portfolios' frame format."""
-    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
     pcfg = _LW.PipelineConfig(**dict(cfg, portfolios=int(nport), portfolio_nyse_breakpoints=bool(nyse_breakpoints)))
     out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
     p, s = out.portfolios, out.portfolio_summary
@@ -1011,7 +1059,7 @@ def build_table_5_held(crsp_comp: pd.DataFrame, hold: int, nport: int = 10, nyse
     overlapping-cohort strategy of held_sorted_portfolios on that problem's sorts, value weights from
     ``me``.  ``cfg``: further PipelineConfig fields.  Returns {(model name, universe name): (monthly,
     summary)} in held_sorted_portfolios' frame format."""
-    panel, model_cols = _pipeline_panel(crsp_comp, None)
+    panel, model_cols = _pipeline_panel(crsp_comp, None, cfg.pop("group_col", None))
     pcfg = _LW.PipelineConfig(**dict(cfg, portfolios=int(nport), portfolio_nyse_breakpoints=bool(nyse_breakpoints),
                                      portfolio_hold=hold))
     out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
@@ -1072,7 +1120,7 @@ def build_table_alphas(crsp_comp: pd.DataFrame, factors: pd.DataFrame, rf=None, 
     return over the first model's months and the annualised Sharpe ratio Avg / Std * sqrt(12) -- and
     (weighting, factor model, alpha / t / t_hac / R2 / nobs): the intercept, its classical and
     Newey-West t-statistics, the regression's R2 and the months it used."""
-    panel, model_cols = _pipeline_panel(crsp_comp, None)
+    panel, model_cols = _pipeline_panel(crsp_comp, None, cfg.pop("group_col", None))
     fcols = [c for c in factors.columns if not (isinstance(rf, str) and c == rf)]
     if isinstance(rf, str) and rf not in factors.columns:
         raise ValueError(f"build_table_alphas: factors has no column {rf!r}")
@@ -1122,7 +1170,7 @@ def build_table_3(crsp_comp: pd.DataFrame, variables_dict: dict = None, q=(0.1, 
     returns on the forecast, its Newey-West standard error and t-statistic and the average R2
     (``PipelineResult.pred_summary`` as it stands).  ``cfg``: further PipelineConfig fields
     (window, min_periods, lag, nw_lags, ...).  Returns a DataFrame indexed by (model, universe)."""
-    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
     pcfg = _LW.PipelineConfig(**dict(cfg, forecast_dist=True, forecast_dist_q=tuple(q)))
     out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
     dmean = out.forecast_dist_summary.mean.cpu().numpy()
@@ -1149,7 +1197,7 @@ def build_table_3_extrapolated(crsp_comp: pd.DataFrame, horizon: int, variables_
     (``PipelineConfig(extrapolate=horizon)``).  ``cfg``: further PipelineConfig fields;
     ``extrapolate_nw_lags`` is the caller's choice (the paper uses 10 lags for 6 and 16 for 12 months;
     the default is ``nw_lags``).  Returns a DataFrame indexed by (model, universe)."""
-    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
     pcfg = _LW.PipelineConfig(**dict(cfg, extrapolate=horizon, extrapolate_decay=decay, extrapolate_q=tuple(q)))
     out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
     s = out.extrapolated_summary
@@ -1172,7 +1220,7 @@ def build_table_4(crsp_comp: pd.DataFrame, variables_dict: dict = None, **cfg):
     slope of returns on that residual (``Pred. slope``) with its Newey-West standard error and
     t-statistic.  ``cfg``: further PipelineConfig fields (window, min_periods, lag, nw_lags, ...).
     Returns a DataFrame indexed by (universe, "Model j on Model i")."""
-    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
     out = _LW.run_pipeline(panel, _LW.PipelineConfig(**dict(cfg, forecast_compare=True)), model_cols=model_cols)
     s = out.forecast_compare_summary
     mean, se, t = s.mean.cpu().numpy(), s.se.cpu().numpy(), s.tstat.cpu().numpy()
@@ -1194,7 +1242,7 @@ def build_table_2_horizon(crsp_comp: pd.DataFrame, horizon: int, variables_dict:
     caller's choice (the paper uses 10 lags for 6-month and 16 for 12-month returns; the default is
     PipelineConfig's 4) and ``lag`` defaults to the horizon.  Returns are decimals, so the slopes are
     1/100 of the paper's, which regresses percent returns."""
-    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict)
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
     pcfg = _LW.PipelineConfig(**dict({"lag": max(int(horizon), 1)}, **cfg, horizon=horizon))
     out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
     res, s = out.res, out.summary

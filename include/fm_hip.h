@@ -72,6 +72,10 @@
  *                      portfolios held for k months as overlapping cohorts (the calendar-time
  *                      strategy of Jegadeesh and Titman), its monthly return record, the cohorts'
  *                      sizes and persistence, and the monthly name turnover
+ *   fm_group_adjust <- build-defined extension A20; no reference line: each characteristic
+ *                      adjusted within a group of firms (an industry) per month -- the value minus
+ *                      its group's mean, the group mean, or the within-group z-score (pandas
+ *                      groupby([month, industry]).transform; Asness, Porter and Stevens 2000)
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -228,7 +232,7 @@ const char* fm_last_error(void);
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
     X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)      \
-    X(fm_alpha_args) X(fm_hold_args)
+    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -991,6 +995,73 @@ typedef struct fm_hold_args {
 } fm_hold_args;
 
 int fm_portfolio_hold(const fm_hold_args* args, void* stream);
+
+/* fm_group_adjust: every chosen column adjusted within a group of firms, per month (build-defined
+ * extension A20; no reference line).  It is pandas' groupby([month, group])[x].transform: the
+ * industry-relative characteristic x - mean, the industry mean, or the within-industry z-score
+ * (Asness, Porter and Stevens 2000).  Rows sorted by (month, permno), months seg_off[nseg+1] of any
+ * length, nrows = seg_off[nseg]; group[nrows] is an int32 code per row.  For every column c and
+ * month t taken separately:
+ *   eligible rows: the value is not NaN, 0 <= group < ngroups and, with level given, level >=
+ *                  min_level.  Any other code (-1, ngroups, INT32_MIN, ...) means "no group".  +-inf
+ *                  are ordinary values and propagate by the IEEE rules: a group with a +inf gives
+ *                  -inf to its finite rows and NaN to the +inf row, a group with both infinities is
+ *                  all NaN;
+ *   statistics of group g: n = its eligible rows, S = their sum, m = S / (double)n (one division),
+ *                  ss = the sum of (x - m)^2 over the same rows, sd = sqrt(ss / (double)(n - 1));
+ *   output:        FM_GADJ_DEMEAN x - m, FM_GADJ_MEAN m, FM_GADJ_ZSCORE (x - m) / sd; every operation
+ *                  is rounded on its own (none is contracted into an FMA);
+ *   NaN output:    ineligible rows; the rows of a group with n < max(1, min_count); under
+ *                  FM_GADJ_ZSCORE also the groups with n < 2 and those whose sd is not finite and
+ *                  positive (a constant group, a group with an infinity);
+ *   optional tables, each [ncols][nseg][ngroups]: gcount = n, always; gmean = m, NaN where n <
+ *                  max(1, min_count); gsd = sd, NaN where n < 2, with FM_GADJ_ZSCORE only (FM_EINVAL
+ *                  otherwise).  Every element of a given table is written, those of groups without
+ *                  rows and of empty months too.
+ * Order of summation.  S and ss are each added in one fixed order: wave w of four starts from +0.0
+ * and adds the group's eligible values among the month's rows 64 (w + 4 i) .. 64 (w + 4 i) + 63,
+ * i = 0, 1, .., in ascending row order, then the four wave sums are added in wave order.  The order
+ * depends on the month's own rows and codes alone: not on the run, the other months or columns of
+ * the call, how the launch batches the columns, nor on ngroups beyond the codes that occur.  So a
+ * repeat call gives the same bits, and so does a call on a sub-range of the months or on a subset
+ * of the columns.  No floating-point atomics, no workspace, no host sync; the launch is
+ * capture-safe.
+ * Limits: ngroups <= FM_MAX_GROUPS = 256 (SIC-2, the 48 / 49 Fama-French and the GICS industries);
+ * none on the month length or on ncols (the launch batches the columns: fm_group_adjust_batch
+ * (ngroups) columns share a workgroup's LDS bins: 8 while those fit, 4 at 256 groups).  Refused with
+ * FM_EINVAL before any launch, outputs untouched (the message names the field): ngroups outside
+ * 1..FM_MAX_GROUPS, an unknown mode, min_count < 0, a negative dimension, gsd without
+ * FM_GADJ_ZSCORE, a stride below nrows, a NULL src, dst, seg_off or group, dst or a table
+ * overlapping src, seg_off, group or level.  nseg == 0, nrows == 0 or ncols == 0 is a valid empty
+ * call: nothing is launched and nothing is written.  A foreign seg_off reads nothing outside
+ * [0, nrows).  Zero-initialize the struct (it grows at the end). */
+#define FM_MAX_GROUPS 256
+#define FM_GADJ_DEMEAN 0
+#define FM_GADJ_MEAN 1
+#define FM_GADJ_ZSCORE 2
+typedef struct fm_gadj_args {
+    const double* src;           /* [ncols][src_stride], rows sorted by (month, permno) */
+    int64_t src_stride;
+    double* dst;                 /* [ncols][dst_stride] */
+    int64_t dst_stride;
+    const int64_t* seg_off;      /* [nseg+1] */
+    const int32_t* group;        /* [nrows] group code of each row */
+    const uint8_t* level;        /* [nrows] universe level or NULL (every row) */
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t ncols;
+    int32_t nseg;
+    int32_t ngroups;             /* 1 .. FM_MAX_GROUPS */
+    int32_t mode;                /* FM_GADJ_DEMEAN / MEAN / ZSCORE */
+    int32_t min_count;           /* >= 0 */
+    int32_t min_level;
+    int32_t* gcount;             /* [ncols][nseg][ngroups] or NULL */
+    double* gmean;               /* [ncols][nseg][ngroups] or NULL */
+    double* gsd;                 /* [ncols][nseg][ngroups] or NULL; FM_GADJ_ZSCORE only */
+} fm_gadj_args;
+
+int fm_group_adjust(const fm_gadj_args* args, void* stream);
+/* the columns that share a workgroup at `ngroups` groups (0 for ngroups outside 1..FM_MAX_GROUPS) */
+int fm_group_adjust_batch(int32_t ngroups);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
