@@ -229,6 +229,20 @@ class GroupAdjArgs(C.Structure):
     ]
 
 
+FM_MAX_DSORT = 10
+
+
+class DsortArgs(C.Structure):
+    _fields_ = [
+        ("a", _p), ("b", _p), ("a_sort_stride", _i64), ("b_sort_stride", _i64), ("ret", _p), ("weight", _p),
+        ("level", _p), ("nyse", _p), ("seg_off", _p), ("nrows", _i64), ("nseg", _i32), ("nsel", _i32),
+        ("max_seg_len", _i32), ("na", _i32), ("nb", _i32), ("conditional", _i32), ("min_level", _i32),
+        ("nyse_breakpoints", _i32), ("min_count", _i32), ("min_count_bin", _i32),
+        ("qa", _f64 * (FM_MAX_DSORT - 1)), ("qb", _f64 * (FM_MAX_DSORT - 1)), ("rec_b", _p), ("rec_a", _p),
+        ("cnt", _p), ("cell", _p), ("bpa", _p), ("bpb", _p), ("status", _p),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -275,6 +289,7 @@ _SIGS = {
     "fm_portfolio_hold": (_i32, [C.POINTER(HoldArgs), _p]),
     "fm_group_adjust": (_i32, [C.POINTER(GroupAdjArgs), _p]),
     "fm_group_adjust_batch": (_i32, [_i32]),
+    "fm_portfolio_double_sort": (_i32, [C.POINTER(DsortArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -294,7 +309,8 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_fport_args": FPortArgs, "fm_fdist_args": FDistArgs,
             "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
             "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs,
-            "fm_hold_args": HoldArgs, "fm_gadj_args": GroupAdjArgs}
+            "fm_hold_args": HoldArgs, "fm_gadj_args": GroupAdjArgs,
+            "fm_dsort_args": DsortArgs}
 
 _lib = None
 

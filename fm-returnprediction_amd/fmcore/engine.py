@@ -2237,6 +2237,176 @@ def held_portfolios(panel: DevicePanel, ports: Portfolios, hold, ret="retx", wei
 
 
 # ------------------------------------------------------------------------------------------
+# Double-sorted portfolios and the factor returns built from them (A21)
+# ------------------------------------------------------------------------------------------
+MAX_DSORT = L.FM_MAX_DSORT
+
+
+@dataclass
+class DoubleSort:
+    # nsel sorts of na x nb cells; ``batched`` False: the call had one [n] signal pair (nsel = 1)
+    rec_b: torch.Tensor    # [nsel, na+1, T, nb+1, 4] float64: per a-bin (last slab: a-neutral) the b portfolios'
+    #                        ew ret, ew mean b, vw ret, vw mean b; last row = H-L
+    rec_a: torch.Tensor    # [nsel, nb+1, T, na+1, 4] float64: the same with the roles swapped (ew / vw mean a)
+    cnt: torch.Tensor      # [nsel, T, na, nb] int32 rows with a finite return
+    cell: torch.Tensor     # [nsel, rows] uint8: pa * nb + pb, 255 = none
+    bpa: torch.Tensor      # [nsel, T, na-1] float64 breakpoints of a (NaN: unsorted month)
+    bpb: torch.Tensor      # [nsel, T, na, nb-1] float64 breakpoints of b per a-bin (independent: the same row)
+    status: torch.Tensor   # [nsel, T] int32: 1 = sorted month
+    na: int = 5
+    nb: int = 5
+    conditional: bool = False
+
+    def _view(self, rec, nslab):
+        S, T = int(self.status.shape[0]), int(self.status.shape[1])
+        status = self.status[:, None, :].repeat(1, nslab, 1).view(S * nslab, T)   # (a copy: consumers read it by stride)
+        return Portfolios(bp=None, port=None, rec=rec.view(S * nslab, T, rec.shape[-2], 4), cnt=None, status=status)
+
+    @property
+    def by_b(self):
+        """The b portfolios within every a-bin and a-neutral, as a batched ``Portfolios`` whose sort axis
+        is nsel * (na+1) (sort s, slab i at s * (na+1) + i), for ``portfolio_summary`` / ``portfolio_alphas``."""
+        return self._view(self.rec_b, self.na + 1)
+
+    @property
+    def by_a(self):
+        """The a portfolios within every b-bin and b-neutral: sort axis nsel * (nb+1)."""
+        return self._view(self.rec_a, self.nb + 1)
+
+
+def _dsort_levels(who, name, nbin, q):
+    if not 2 <= nbin <= L.FM_MAX_DSORT:
+        raise ValueError(f"{who}: n{name} must be 2..{L.FM_MAX_DSORT}, got {nbin}")
+    qs = [float(v) for v in q] if q is not None else [k / nbin for k in range(1, nbin)]
+    if len(qs) != nbin - 1:
+        raise ValueError(f"{who}: q{name} must hold n{name} - 1 = {nbin - 1} levels, got {len(qs)}")
+    if any(not (lo < v < 1.0) for lo, v in zip([0.0] + qs[:-1], qs)):
+        raise ValueError(f"{who}: q{name} must be strictly ascending in (0, 1), got {qs}")
+    return qs
+
+
+def double_sort(seg_off, a, b, ret, weight=None, level=None, nyse=None, na=5, nb=5, qa=None, qb=None,
+                conditional=False, min_level=0, nyse_breakpoints=False, min_count=None, min_count_bin=None,
+                max_seg_len=None):
+    """A21: per month (``seg_off`` int64 [T+1], rows sorted by month) sort the rows two ways, on ``a``
+    into ``na`` bins and on ``b`` into ``nb`` -- independently, or with ``conditional`` b within each
+    a-bin -- and average every cell's ``ret``, a and b, equal- and ``weight``-weighted, with each
+    row's and column's high-minus-low spread and the a-neutral / b-neutral averages across the
+    rows / columns (fm_portfolio_double_sort; the definition is in fm_hip.h).  ``a`` and ``b``: float64
+    [n], or [nsel, n] for nsel sorts in one call ([n] beside [nsel, n] is shared by all of them).
+    ``qa`` / ``qb``: the breakpoint levels (default k / na, k / nb); ``min_count`` (default na * nb):
+    breakpoint rows a month needs; ``min_count_bin`` (default nb): those an a-bin needs, conditional
+    only; ``max_seg_len``: the longest month if the caller knows it (else one host sync).  Plain
+    device tensors in, ``DoubleSort`` out."""
+    who = "double_sort"
+    for t, what in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() not in (1, 2):
+            raise ValueError(f"{who}: {what} must be a float64 [n] or [nsel, n] tensor")
+    dev = a.device
+    n = int(a.shape[-1])
+    if int(b.shape[-1]) != n or b.device != dev:
+        raise ValueError(f"{who}: a and b must have the same rows on one device, got {list(a.shape)} and {list(b.shape)}")
+    batched = a.dim() == 2 or b.dim() == 2
+    S = max(int(a.shape[0]) if a.dim() == 2 else 1, int(b.shape[0]) if b.dim() == 2 else 1)
+    for t, what in ((a, "a"), (b, "b")):
+        if t.dim() == 2 and int(t.shape[0]) != S:
+            raise ValueError(f"{who}: {what} holds {int(t.shape[0])} sorts, the other signal {S}")
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError(f"{who}: seg_off must be an int64 [T+1] tensor on the signals' device")
+    T = int(seg_off.shape[0]) - 1
+    for t, dt, what in ((ret, torch.float64, "ret"), (weight, torch.float64, "weight"), (level, torch.uint8, "level"),
+                        (nyse, torch.uint8, "nyse")):
+        if t is None and what != "ret":
+            continue
+        if t is None or t.dtype != dt or t.dim() != 1 or t.shape[0] != n or t.device != dev:
+            raise ValueError(f"{who}: {what} must be a {dt} [{n}] tensor on {dev}")
+    na, nb = int(na), int(nb)
+    qa = _dsort_levels(who, "a", na, qa)
+    qb = _dsort_levels(who, "b", nb, qb)
+    min_count = na * nb if min_count is None else int(min_count)
+    min_count_bin = nb if min_count_bin is None else int(min_count_bin)
+    if min_count < 1 or min_count_bin < 1:
+        raise ValueError(f"{who}: min_count and min_count_bin must be >= 1, got {min_count} and {min_count_bin}")
+    if not 0 <= int(min_level) <= 255:
+        raise ValueError(f"{who}: min_level must be 0..255, got {min_level}")
+    if nyse_breakpoints and nyse is None:
+        raise ValueError(f"{who}: nyse_breakpoints needs nyse")
+    if S > 65535:
+        raise ValueError(f"{who}: at most 65535 sorts per call, got {S}")
+    seg_off, a, b, ret = seg_off.contiguous(), a.contiguous(), b.contiguous(), ret.contiguous()
+    weight, level, nyse = (None if t is None else t.contiguous() for t in (weight, level, nyse))
+    if max_seg_len is None:
+        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+
+    def new(shape, dtype, fill):
+        # an empty call launches nothing: its outputs are then what a launch would have written
+        if T and S:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        return torch.full(shape, fill, dtype=dtype, device=dev)
+
+    nan = float("nan")
+    out = DoubleSort(rec_b=new((S, na + 1, T, nb + 1, 4), torch.float64, nan),
+                     rec_a=new((S, nb + 1, T, na + 1, 4), torch.float64, nan),
+                     cnt=new((S, T, na, nb), torch.int32, 0), cell=new((S, n), torch.uint8, 255),
+                     bpa=new((S, T, na - 1), torch.float64, nan), bpb=new((S, T, na, nb - 1), torch.float64, nan),
+                     status=new((S, T), torch.int32, 0), na=na, nb=nb, conditional=bool(conditional))
+    args = L.DsortArgs(a=a.data_ptr(), b=b.data_ptr(), a_sort_stride=n if a.dim() == 2 else 0,
+                       b_sort_stride=n if b.dim() == 2 else 0, ret=ret.data_ptr(), weight=_ptr(weight),
+                       level=_ptr(level), nyse=_ptr(nyse), seg_off=seg_off.data_ptr(), nrows=n, nseg=T, nsel=S,
+                       max_seg_len=int(max_seg_len), na=na, nb=nb, conditional=int(bool(conditional)),
+                       min_level=int(min_level), nyse_breakpoints=int(bool(nyse_breakpoints)), min_count=min_count,
+                       min_count_bin=min_count_bin, rec_b=out.rec_b.data_ptr(), rec_a=out.rec_a.data_ptr(),
+                       cnt=out.cnt.data_ptr(), cell=out.cell.data_ptr(), bpa=out.bpa.data_ptr(),
+                       bpb=out.bpb.data_ptr(), status=out.status.data_ptr())
+    for j, v in enumerate(qa):
+        args.qa[j] = v
+    for j, v in enumerate(qb):
+        args.qb[j] = v
+    _kcall("fm_portfolio_double_sort", "fm_portfolio_double_sort", L.C.byref(args), _stream())
+    _remember("fm_portfolio_double_sort", "fm_portfolio_double_sort", args, seg_off, a, b, ret, weight, level, nyse, out)
+    return out
+
+
+def double_sort_panel(panel: DevicePanel, a_col, b_cols, ret="retx", weight=None, level=None, nyse=None, **kw):
+    """A21 on a panel: ``double_sort`` of the panel column ``a_col`` against every column of
+    ``b_cols`` (a name or index, or a sequence of them: one sort each, in one launch, sharing a) with
+    the panel column ``ret`` as the realised return.  ``weight``: a float64 [rows] vector, or "me" for
+    the panel's market equity; ``nyse``: a uint8 [rows] vector, default the panel's own NYSE byte
+    when ``nyse_breakpoints`` is asked for.  Further keywords are ``double_sort``'s."""
+    single = isinstance(b_cols, (str, int))
+    names = [b_cols] if single else list(b_cols)
+    if not names:
+        raise ValueError("double_sort_panel: b_cols is empty")
+    if isinstance(weight, str):
+        if weight != "me" or panel.me is None:
+            raise ValueError("double_sort_panel: weight names the panel's 'me', which this panel must carry")
+        weight = panel.me
+    if nyse is None and kw.get("nyse_breakpoints"):
+        nyse = panel.nyse
+    a = column_vector(panel, a_col)
+    if single:
+        b = column_vector(panel, names[0])
+    elif panel.cols is not None and all(isinstance(c, (str, int)) for c in names):
+        idx = [panel.col(c) if isinstance(c, str) else int(c) for c in names]
+        b = panel.cols[idx, :panel.nrows]
+    else:
+        b = torch.stack([column_vector(panel, c) for c in names])
+    return double_sort(panel.seg_off, a, b, column_vector(panel, ret), weight=weight, level=level, nyse=nyse,
+                       max_seg_len=kw.pop("max_seg_len", panel.max_seg_len), **kw)
+
+
+def sort_factors(ds: DoubleSort, axis="b", weighted=True):
+    """The neutral high-minus-low return series of every sort of ``ds`` as float64 [T, nsel], NaN in
+    unsorted months: ``axis`` "b" the a-neutral spread of the b portfolios, "a" the b-neutral spread
+    of the a portfolios; value- (``weighted``) or equal-weighted.  A view of the records (no kernel),
+    in the shape ``portfolio_alphas`` takes as ``factors``."""
+    if axis not in ("a", "b"):
+        raise ValueError(f"sort_factors: axis must be 'a' or 'b', got {axis!r}")
+    rec = ds.rec_b if axis == "b" else ds.rec_a
+    return rec[:, -1, :, -1, 2 if weighted else 0].transpose(0, 1)
+
+
+# ------------------------------------------------------------------------------------------
 # Within-group (industry) adjustment of the characteristics (A20)
 # ------------------------------------------------------------------------------------------
 MAX_GROUPS = L.FM_MAX_GROUPS

@@ -20,6 +20,9 @@ build-defined A18), in one more launch.
 With ``PipelineConfig.portfolio_hold`` = k those portfolios are held for k months as overlapping
 cohorts (the calendar-time strategy; build-defined A19): its monthly record, summary, turnover and,
 with the factors, its alphas, in one more launch.
+With ``PipelineConfig.double_sort`` = a panel column those forecasts are also sorted two ways, against
+that column (size, say), into na x nb cells: each row's spread and the column-neutral spread
+(build-defined A21).
 With ``PipelineConfig.extrapolate`` = k the monthly run also scales every month's forecasts to k
 months and regresses the compounded k-month return on them (paper Section 4's second approach, the
 lower panels of Tables 9a and 9b; build-defined A17), in one more launch.
@@ -101,6 +104,18 @@ class PipelineConfig:
     portfolios: Optional[int] = field(default=None, kw_only=True)
     portfolio_q: Optional[Sequence[float]] = field(default=None, kw_only=True)   # nport - 1 levels (None: k / nport)
     portfolio_nyse_breakpoints: bool = field(default=False, kw_only=True)        # breakpoints from the NYSE rows only
+    # A21 (the Table-5 spread controlled for a second variable): ``double_sort`` = a panel column (by
+    # name, e.g. "log_size") sorts every month's stocks into ``double_sort_shape`` = (na, nb) cells, na
+    # bins of that column by nb bins of each Table-2 problem's forecast, independently or
+    # (``double_sort_conditional``) the forecast within each bin of the column, over the problem's
+    # universe and with ``portfolio_nyse_breakpoints`` (engine.double_sort): every row's H-L and the
+    # column-neutral H-L.  The portfolio launch is asked for its forecasts, which the double sort
+    # reads as vectors; one more launch per universe level.  Needs ``portfolios``; excludes horizon > 1,
+    # ``extrapolate`` and ``portfolio_hold`` (not wired): ValueError otherwise.  None = no launch more.
+    # Here, in front of every field whose place tests pin.
+    double_sort: Optional[str] = field(default=None, kw_only=True)
+    double_sort_shape: Sequence[int] = field(default=(5, 5), kw_only=True)
+    double_sort_conditional: bool = field(default=False, kw_only=True)
     # A14 inside the pipeline (paper Table 3's univariate properties): each month's cross-sectional
     # mean, standard deviation and ``forecast_dist_q`` quantiles of the same forecasts, over the same
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
@@ -189,6 +204,8 @@ class PipelineResult:
     portfolios: Optional[E.Portfolios] = None        # cfg.portfolios: tensors with a leading [nsort] dimension
     portfolio_summary: Optional[E.Summary] = None    # [nsort, nport+1, 4]
     portfolio_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
+    double_sort: Optional[E.DoubleSort] = None        # cfg.double_sort: tensors with a leading [nsort] dimension
+    double_sort_summary: Optional[tuple] = None       # (Summary of by_b [nsort, na+1, nb+1, 4], of by_a [nsort, nb+1, na+1, 4])
     forecast_dist: Optional[E.ForecastDist] = None       # cfg.forecast_dist: [nsort, T, 2+nq] and [nsort, T]
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
@@ -396,6 +413,52 @@ def check_hold(cfg: PipelineConfig, panel=None):
         raise ValueError("PipelineConfig: portfolio_hold needs a panel with firm ids (build it with ids=...)")
 
 
+def check_double_sort(cfg: PipelineConfig, panel=None):
+    """The rules of ``PipelineConfig.double_sort`` (no device work); ``panel``: the run's panel, when
+    there is one."""
+    col = cfg.double_sort
+    if col is None:
+        return
+    if not isinstance(col, str):
+        raise ValueError(f"PipelineConfig: double_sort must name a panel column, got {col!r}")
+    shape = cfg.double_sort_shape
+    ok = not isinstance(shape, str) and len(tuple(shape)) == 2 and all(
+        isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 2 <= v <= E.MAX_DSORT for v in shape)
+    if not ok:
+        raise ValueError(f"PipelineConfig: double_sort_shape must be (na, nb) with both in 2..{E.MAX_DSORT}, "
+                         f"got {shape!r}")
+    if cfg.portfolios is None:
+        raise ValueError("PipelineConfig: double_sort needs portfolios (the launch that makes the forecasts)")
+    for on, what in ((cfg.horizon != 1, f"horizon={cfg.horizon}"), (cfg.extrapolate is not None, "extrapolate"),
+                     (cfg.portfolio_hold is not None, "portfolio_hold")):
+        if on:
+            raise ValueError(f"PipelineConfig: double_sort excludes {what} (the combination is not wired)")
+    if panel is not None and col not in panel.names:
+        raise ValueError(f"PipelineConfig: double_sort names column {col!r}, which the panel lacks")
+
+
+def double_sort_forecasts(panel: E.DevicePanel, cfg: PipelineConfig, forecast, levels, level, y="retx"):
+    """A21 of the pipeline: the panel column ``cfg.double_sort`` against every forecast vector
+    (``forecast`` [nsort, rows], sort j over the universe ``levels[j]``), one ``engine.double_sort``
+    launch per distinct level, gathered back in sort order."""
+    na, nb = (int(v) for v in cfg.double_sort_shape)
+    a = E.column_vector(panel, cfg.double_sort)
+    ret = E.column_vector(panel, y)
+    parts, order = [], []
+    for lv in sorted(set(levels)):
+        js = [j for j, l in enumerate(levels) if l == lv]
+        order += js
+        parts.append(E.double_sort(panel.seg_off, a, forecast[js], ret, weight=panel.me, level=level, nyse=panel.nyse,
+                                   na=na, nb=nb, conditional=cfg.double_sort_conditional, min_level=lv,
+                                   nyse_breakpoints=cfg.portfolio_nyse_breakpoints, max_seg_len=panel.max_seg_len))
+    if len(parts) == 1:
+        return parts[0]
+    inv = torch.as_tensor(np.argsort(np.asarray(order)), device=forecast.device)
+    cat = {k: torch.cat([getattr(p, k) for p in parts])[inv]
+           for k in ("rec_b", "rec_a", "cnt", "cell", "bpa", "bpb", "status")}
+    return E.DoubleSort(na=na, nb=nb, conditional=bool(cfg.double_sort_conditional), **cat)
+
+
 def check_group_adjust(cfg: PipelineConfig, panel=None, model_cols=None, y="retx"):
     """The rules of ``PipelineConfig.group_adjust`` (no device work); ``panel``: the run's panel, when
     there is one (touched only when group_adjust is set)."""
@@ -444,6 +507,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     check_extrapolate(cfg)
     check_alphas(cfg, None if panel is None else panel.nseg)
     check_hold(cfg, panel)
+    check_double_sort(cfg, panel)
     check_group_adjust(cfg, panel, model_cols, y)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
@@ -497,8 +561,17 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
         port_probs = probs
         ports = E.forecast_portfolio_sort(gpanel, coef, sel, cuts=cuts, ret=gpanel.col(y), weight=gpanel.me,
                                           level=level, nyse=gpanel.nyse, nport=cfg.portfolios, q=cfg.portfolio_q,
-                                          nyse_breakpoints=cfg.portfolio_nyse_breakpoints)
+                                          nyse_breakpoints=cfg.portfolio_nyse_breakpoints,
+                                          forecast_out=cfg.double_sort is not None)
         port_summ = E.portfolio_summary(ports, cfg.nw_lags)
+    dsort = dsort_summ = None
+    if cfg.double_sort is not None:
+        # the sort's own forecasts, as vectors (the fused sorts never write them), against the column
+        dsort = double_sort_forecasts(gpanel, cfg, ports.forecast, [lv for _, lv in sel], level, y)
+        S, na, nb = len(sel), dsort.na, dsort.nb
+        sb, sa = E.portfolio_summary(dsort.by_b, cfg.nw_lags), E.portfolio_summary(dsort.by_a, cfg.nw_lags)
+        dsort_summ = (E.Summary(*(t.view(S, na + 1, nb + 1, 4) for t in (sb.mean, sb.se, sb.tstat, sb.nobs))),
+                      E.Summary(*(t.view(S, nb + 1, na + 1, 4) for t in (sa.mean, sa.se, sa.tstat, sa.nobs))))
     held = held_summ = None
     if cfg.portfolio_hold is not None:
         # the sorts' port bytes followed for k months over the firm links of the panel the sort read
@@ -517,7 +590,8 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     return PipelineResult(model_names=names, model_cols=dict(model_cols, **({"Figure 1": FIG1_VARS} if cfg.fig1 else {})),
                           res=res, ix=ix, summary=summ, rolling=roll, pred=pred, pred_status=pst,
                           pred_summary=psumm, cuts=cuts, level=level, breakpoints=bp, portfolios=ports,
-                          portfolio_summary=port_summ, portfolio_problems=port_probs, forecast_dist=dist,
+                          portfolio_summary=port_summ, portfolio_problems=port_probs, double_sort=dsort,
+                          double_sort_summary=dsort_summ, forecast_dist=dist,
                           forecast_dist_summary=dist_summ, forecast_dist_problems=dist_probs,
                           forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
                           y_col=y, group_stats=None if gadj is None else gadj[0],

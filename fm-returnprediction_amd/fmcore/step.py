@@ -43,6 +43,9 @@ class ShardedStep:
         if cfg.portfolio_hold is not None:
             raise ValueError("ShardedStep: cfg.portfolio_hold must be None (a cohort is followed through the earlier "
                              "months' rows, which a month shard does not hold)")
+        if cfg.double_sort is not None:
+            raise ValueError("ShardedStep: cfg.double_sort must be None (the step runs no portfolio stage, whose "
+                             "forecasts the double sort reads)")
         if cfg.group_adjust is not None:
             raise ValueError("ShardedStep: cfg.group_adjust must be None (the sharded ingest carries no group codes)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols

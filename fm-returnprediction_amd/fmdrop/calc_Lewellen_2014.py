@@ -1161,6 +1161,176 @@ def build_table_alphas(crsp_comp: pd.DataFrame, factors: pd.DataFrame, rf=None, 
     return frames
 
 
+DOUBLE_SORT_COLUMNS = ["ew_ret", "vw_ret", "ew_a", "ew_b"]
+
+
+def _dsort_grid(rb, ra, na, nb):
+    """The two record views of one double sort, rb [..., na+1, nb+1, 4] (slab, row) and ra [..., nb+1,
+    na+1, 4], as one grid [..., na+2, nb+2, 4] over the labels (0..na-1, "H-L", "avg") x (0..nb-1,
+    "H-L", "avg") with DOUBLE_SORT_COLUMNS; NaN where the device holds no such number: a margin has
+    the mean of the signal its view sorts on only, and the corners ("H-L", "H-L") and ("avg", "avg")
+    are not defined."""
+    ra = np.swapaxes(ra, -3, -2)    # [..., i <= na, j <= nb, 4]: i = na the H-L of a, j = nb the b-neutral slab
+    g = np.full(rb.shape[:-3] + (na + 2, nb + 2, 4), np.nan)
+    g[..., :na, :nb + 1, 0], g[..., :na, :nb + 1, 1], g[..., :na, :nb + 1, 3] = (rb[..., :na, :, c] for c in (0, 2, 1))
+    g[..., :na, :nb, 2] = ra[..., :na, :nb, 1]
+    g[..., na + 1, :nb + 1, 0], g[..., na + 1, :nb + 1, 1], g[..., na + 1, :nb + 1, 3] = (rb[..., na, :, c] for c in (0, 2, 1))
+    g[..., na, :nb, 0], g[..., na, :nb, 1], g[..., na, :nb, 2] = (ra[..., na, :nb, c] for c in (0, 2, 1))
+    g[..., :na + 1, nb + 1, 0], g[..., :na + 1, nb + 1, 1], g[..., :na + 1, nb + 1, 2] = (ra[..., :, nb, c] for c in (0, 2, 1))
+    return g
+
+
+def _dsort_counts(cnt):
+    """cnt [T, na, nb] -> [T, na+2, nb+2]: the rows behind every entry of _dsort_grid (both ends of a
+    spread, all cells of an average; 0 in the two undefined corners)."""
+    T, na, nb = cnt.shape
+    n = np.zeros((T, na + 2, nb + 2), dtype=np.int64)
+    n[:, :na, :nb] = cnt
+    n[:, :na, nb] = cnt[:, :, 0] + cnt[:, :, -1]
+    n[:, na, :nb] = cnt[:, 0, :] + cnt[:, -1, :]
+    n[:, :na, nb + 1] = cnt.sum(axis=2)
+    n[:, na + 1, :nb] = cnt.sum(axis=1)
+    n[:, na + 1, nb] = n[:, :na, nb].sum(axis=1)
+    n[:, na, nb + 1] = n[:, na, :nb].sum(axis=1)
+    return n
+
+
+def _dsort_frames(status, rec_b, rec_a, cnt, sb, sa, months, na, nb, date_col="mthcaldt"):
+    """double_sorted_portfolios' (monthly, summary) frames of one sort's host arrays: rec_b [na+1, T,
+    nb+1, 4], rec_a [nb+1, T, na+1, 4], cnt [T, na, nb], sb / sa = (mean, tstat, nobs) of the two views."""
+    la, lb = list(range(na)) + ["H-L", "avg"], list(range(nb)) + ["H-L", "avg"]
+    srt = status == 1
+    g = _dsort_grid(np.moveaxis(rec_b, 1, 0)[srt], np.moveaxis(rec_a, 1, 0)[srt], na, nb)
+    index = pd.MultiIndex.from_product([np.asarray(months)[srt], la, lb], names=[date_col, "a_bin", "b_bin"])
+    monthly = pd.DataFrame(g.reshape(-1, 4), index=index, columns=DOUBLE_SORT_COLUMNS)
+    monthly["n"] = _dsort_counts(cnt[srt].astype(np.int64)).reshape(-1)
+    stats = [_dsort_grid(b, a, na, nb) for b, a in zip(sb, sa)]   # mean, tstat, nobs: [na+2, nb+2, 4]
+    summary = pd.DataFrame({(c, stat): v[..., j].reshape(-1) for j, c in enumerate(DOUBLE_SORT_COLUMNS)
+                            for stat, v in zip(("mean", "tstat", "nobs"), stats)},
+                           index=pd.MultiIndex.from_product([la, lb], names=["a_bin", "b_bin"]))
+    return monthly, summary
+
+
+def _signal(df, x, what):
+    """A column name or one value per row -> float64 [rows]."""
+    v = _api.as_f64(df[x]) if isinstance(x, str) else np.asarray(x, dtype=np.float64)
+    if v.shape != (len(df),):
+        raise ValueError(f"{what} must be a column name or hold one value per row of df")
+    return v
+
+
+def _double_sort_frame(df, a, bs, return_col, weight_col, universe, nyse_breakpoints, date_col, **kw):
+    """The device work of the two functions below: the frame's panel (rows by (month, input order))
+    and the ``DoubleSort`` of signal ``a`` against every signal of ``bs``, in one launch."""
+    import torch
+    if universe not in _UNIVERSE_LEVEL:
+        raise ValueError(f"universe must be one of {list(_UNIVERSE_LEVEL)}")
+    names = ["a"] + [f"b{j}" for j in range(len(bs))] + ["ret"] + (["weight"] if weight_col is not None else [])
+    arrays = [a] + list(bs) + [_api.as_f64(df[return_col])] + ([_api.as_f64(df[weight_col])] if weight_col is not None else [])
+    me = _api.as_f64(df["me"]) if universe is not None else None
+    nyse = (df["primaryexch"] == "N").to_numpy().astype(np.uint8) if (nyse_breakpoints or universe is not None) else None
+    panel = _E.panel_from_arrays(arrays, names, df[date_col].values, me=me, nyse=nyse)
+    level = _E.universe(panel)[2] if universe is not None else None
+    nb_ = len(bs)
+    ds = _E.double_sort(panel.seg_off, panel.cols[0], panel.cols[1:1 + nb_], panel.cols[1 + nb_],
+                        weight=panel.cols[2 + nb_] if weight_col is not None else None, level=level, nyse=panel.nyse,
+                        min_level=_UNIVERSE_LEVEL[universe], nyse_breakpoints=nyse_breakpoints,
+                        max_seg_len=panel.max_seg_len, **kw)
+    torch.cuda.synchronize()
+    return panel, ds
+
+
+def double_sorted_portfolios(df: pd.DataFrame, a, b, return_col: str = "retx", weight_col: str = None, na: int = 5,
+                             nb: int = 5, breakpoints_a=None, breakpoints_b=None, conditional: bool = False,
+                             universe: str = None, nyse_breakpoints: bool = False, date_col: str = "mthcaldt",
+                             nw_lags: int = 4):
+    """A21: each month, sort the stocks two ways -- on ``a`` into ``na`` bins and on ``b`` into ``nb``
+    (column names or one value per row), independently or, with ``conditional``, b within each a-bin
+    -- at the np.quantile levels ``breakpoints_a`` / ``breakpoints_b`` (default k / na, k / nb; with
+    ``nyse_breakpoints`` from the NYSE rows only), and average each cell's realised return and its two
+    signals, equal- and ``weight_col``-weighted, on the device (fm_portfolio_double_sort).
+    ``universe`` as in forecast_sorted_portfolios.
+    Returns (monthly, summary): ``monthly`` is indexed by (month, a_bin, b_bin), the bins 0..n-1 plus
+    the margins "H-L" (last bin minus first along that axis) and "avg" (the average across that
+    axis' bins: ("avg", "H-L") is the a-neutral spread of b), with columns ew_ret, vw_ret, ew_a,
+    ew_b and n (rows with a return), sorted months only; a margin carries the mean of the signal it
+    is sorted on, NaN for the other, and the corners ("H-L", "H-L") and ("avg", "avg") are NaN.
+    ``summary`` is indexed by (a_bin, b_bin) with columns (column, mean / tstat / nobs): the FM mean
+    and its Newey-West(nw_lags) t-statistic."""
+    panel, ds = _double_sort_frame(df, _signal(df, a, "a"), [_signal(df, b, "b")], return_col, weight_col, universe,
+                                   nyse_breakpoints, date_col, na=na, nb=nb, qa=breakpoints_a, qb=breakpoints_b,
+                                   conditional=conditional)
+    sb, sa = _E.portfolio_summary(ds.by_b, nw_lags), _E.portfolio_summary(ds.by_a, nw_lags)
+    host = lambda s: [t.cpu().numpy() for t in (s.mean, s.tstat, s.nobs)]
+    return _dsort_frames(ds.status[0].cpu().numpy(), ds.rec_b[0].cpu().numpy(), ds.rec_a[0].cpu().numpy(),
+                         ds.cnt[0].cpu().numpy(), host(sb), host(sa), panel.months, int(na), int(nb), date_col)
+
+
+def characteristic_factors(df: pd.DataFrame, char_cols, size_col: str = "me", weight_col: str = "me",
+                           breakpoints_size=(0.5,), breakpoints_char=(0.3, 0.7), nyse_breakpoints: bool = True,
+                           universe: str = None, return_col: str = "retx", date_col: str = "mthcaldt") -> pd.DataFrame:
+    """A21: factor returns built from the panel itself.  Each month the stocks are sorted
+    independently on ``size_col`` (breakpoints ``breakpoints_size``, the median) and on every column of
+    ``char_cols`` (``breakpoints_char``, 30 / 70 per cent), at NYSE breakpoints, all characteristics
+    in one batched launch; the cells' returns are ``weight_col``-weighted (None: equal-weighted).
+    Returns a DataFrame indexed by month with one column per characteristic -- the size-neutral
+    high-minus-low return, i.e. the average over the size groups of (top minus bottom characteristic
+    group) -- and "SMB": minus the mean over the characteristics of the characteristic-neutral
+    size spread (small minus big).  NaN in months that could not be sorted.  ``build_table_alphas``
+    takes the frame as ``factors``.
+    What this is not: the Fama-French factors.  The sorts are rebalanced every month on the rows' own
+    values of that month: there is no June formation, no six-month accounting lag, and nothing is
+    held between rebalancing dates.  Lagging the weight (last month's market equity) is the caller's
+    job, through ``weight_col``."""
+    char_cols = list(char_cols)
+    if not char_cols:
+        raise ValueError("characteristic_factors: char_cols is empty")
+    bs = [_signal(df, c, c) for c in char_cols]
+    panel, ds = _double_sort_frame(df, _signal(df, size_col, "size_col"), bs, return_col, weight_col, universe,
+                                   nyse_breakpoints, date_col, na=len(breakpoints_size) + 1,
+                                   nb=len(breakpoints_char) + 1, qa=breakpoints_size, qb=breakpoints_char)
+    weighted = weight_col is not None
+    hml = _E.sort_factors(ds, "b", weighted).cpu().numpy()           # [T, nchar]
+    smb = -_E.sort_factors(ds, "a", weighted).cpu().numpy().mean(axis=1)
+    out = pd.DataFrame(hml, index=pd.Index(np.asarray(panel.months), name=date_col), columns=char_cols)
+    out["SMB"] = smb
+    return out
+
+
+def build_table_double_sort(crsp_comp: pd.DataFrame, by: str = "log_size", variables_dict: dict = None, shape=(5, 5),
+                            **cfg):
+    """build_table_5's spread controlled for ``by`` (build-defined A21; no reference line), from ONE
+    device pipeline run: for every Table-2 model and universe the stocks are sorted each month into
+    ``shape`` = (na, nb) cells, na bins of the panel column ``by`` (size) by nb bins of the
+    out-of-sample forecast (``conditional=True``: the forecast within each bin of ``by``).  ``cfg``:
+    further PipelineConfig fields (portfolios: the single sort's nport, default 10;
+    portfolio_nyse_breakpoints; window, min_periods, lag, nw_lags, ...).
+    Returns {(model name, universe name): DataFrame} with the rows 0..na-1 (the bins of ``by``) and
+    "avg" (the ``by``-neutral portfolios) and the columns (weighting, 0..nb-1): the mean realised
+    return of the cell, (weighting, "H-L"): the row's high-minus-low forecast spread and (weighting,
+    "t(H-L)"): its Newey-West t-statistic."""
+    panel, model_cols = _pipeline_panel(crsp_comp, variables_dict, cfg.pop("group_col", None))
+    na, nb = (int(v) for v in shape)
+    conditional = bool(cfg.pop("conditional", False))
+    cfg.setdefault("portfolios", 10)
+    pcfg = _LW.PipelineConfig(**dict(cfg, double_sort=by, double_sort_shape=(na, nb), double_sort_conditional=conditional))
+    out = _LW.run_pipeline(panel, pcfg, model_cols=model_cols)
+    sb = out.double_sort_summary[0]
+    mean, tstat = sb.mean.cpu().numpy(), sb.tstat.cpu().numpy()   # [nsort, na+1, nb+1, 4]
+    rows = pd.Index(list(range(na)) + ["avg"], name=by)
+    frames = {}
+    for j, k in enumerate(out.portfolio_problems):
+        prob = out.res.problems[k]
+        data = {}
+        for wn, c in (("ew", 0), ("vw", 2)):
+            for jj in range(nb):
+                data[(wn, jj)] = mean[j, :, jj, c]
+            data[(wn, "H-L")] = mean[j, :, nb, c]
+            data[(wn, "t(H-L)")] = tstat[j, :, nb, c]
+        frames[(out.model_names[prob.model], _LW.SUBSET_NAMES[prob.level])] = pd.DataFrame(data, index=rows)
+    return frames
+
+
 def build_table_3(crsp_comp: pd.DataFrame, variables_dict: dict = None, q=(0.1, 0.9), **cfg):
     """Paper Table 3 from ONE device pipeline run (build-defined; no reference line): for every
     Table-2 model and universe, the univariate properties of the out-of-sample forecast from that

@@ -232,7 +232,7 @@ const char* fm_last_error(void);
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
     X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)      \
-    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args)
+    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args) X(fm_dsort_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -1062,6 +1062,88 @@ typedef struct fm_gadj_args {
 int fm_group_adjust(const fm_gadj_args* args, void* stream);
 /* the columns that share a workgroup at `ngroups` groups (0 for ngroups outside 1..FM_MAX_GROUPS) */
 int fm_group_adjust_batch(int32_t ngroups);
+
+/* fm_portfolio_double_sort: per month, sort the stocks two ways, on signals a and b, into na x nb
+ * cells, and average each cell's realised return and signals (build-defined extension A21; no
+ * reference line): the 5 x 5 control of one sort for a second variable, and the 2 x 3 sorts that
+ * size, value and characteristic factors are built from.  Rows sorted by (month, permno), months
+ * seg_off[nseg+1] of at most 16,384 rows (longer: FM_ETOOBIG before any launch, outputs
+ * untouched), nrows = seg_off[nseg].  nsel sorts share one launch (grid (month, sort)): sort s
+ * reads a + s * a_sort_stride and b + s * b_sort_stride (elements; a stride of 0 shares that
+ * signal across the sorts), and writes row vectors at [s][row] and month records at [s][t].
+ * Per month t of sort s:
+ *   eligible rows:   isfinite(a) and isfinite(b) and level >= min_level (level NULL: every row);
+ *   breakpoint rows: the eligible rows; with nyse_breakpoints those with nyse != 0;
+ *   fewer than min_count breakpoint rows: status = 0, bpa and bpb NaN, every cell byte 255, every
+ *     record NaN, every count 0; otherwise status = 1 and
+ *   bpa[i]     = numpy 'linear' quantile qa[i] of the breakpoint rows' a (exact order statistics;
+ *                the sign of an exactly-zero breakpoint is not specified);
+ *   pa         = #{ i : a > bpa[i] } (right-closed bins);
+ *   bpb[i'][j] = conditional == 0: the quantile qb[j] of all breakpoint rows' b, the same row
+ *                written for every i' < na; conditional != 0: the quantile over the breakpoint
+ *                rows with pa == i'.  An a-bin with fewer than min_count_bin such rows has NaN
+ *                bpb, its rows get cell byte 255, its cells count 0 and NaN records;
+ *   pb         = #{ j : b > bpb[pa][j] };
+ *   cell[row]  = pa * nb + pb for the eligible rows of a sorted a-bin, else 255;
+ *   cnt[pa][pb] = the cell's rows with a finite return.  Over those rows the cell has six sums:
+ *                ret, a, b, and w ret, w a, w b over the rows that also have a finite weight > 0
+ *                (weight NULL: none); the means are sum / count and sum / sum(w), an empty set
+ *                gives NaN.
+ * Records, in two views that each have fm_portfolio_sort's record layout:
+ *   rec_b[s][i][t][j] (i < na, j < nb) = { ew ret, ew mean b, vw ret, vw mean b } of cell (i, j);
+ *   rec_b[s][i][t][nb] = row nb-1 minus row 0 (NaN if either end is);
+ *   rec_b[s][na][t][j][c] = (x_0 + x_1 + ... + x_{na-1}) / na over the na slabs' entries
+ *                (j, c), added in that order (NaN if any term is): the a-neutral b portfolios;
+ *                the slab's row nb is its own row nb-1 minus its row 0;
+ *   rec_a[s][j][t][i] = { ew ret, ew mean a, vw ret, vw mean a } of cell (i, j), with the roles
+ *                swapped throughout: row na = row na-1 minus row 0, slab nb the b-neutral a
+ *                portfolios (x_0 + ... + x_{nb-1}) / nb and their spread.
+ * Every output of a month depends on that month's rows alone and every sum runs in one fixed
+ * order (the cell's rows in row order, lane l of a wave taking the list's entries l, l + 64, ...,
+ * then the wave butterfly): a repeat call, a sub-range of the months, a sort alone or in a batch
+ * and any workgroup form give the same bits.  No floating-point atomics, no workspace, no host
+ * sync: three launches on the stream (a's breakpoints, b's breakpoints with the a-bins of a
+ * conditional sort side by side, then cells and sums), the breakpoints waiting in the month's own
+ * records in between.
+ * Refused with FM_EINVAL before any launch: na or nb outside 2..FM_MAX_DSORT, qa / qb not strictly
+ * ascending in (0, 1), min_count or min_count_bin < 1, min_level outside 0..255, nyse_breakpoints
+ * without nyse, nsel outside 0..65,535, a negative size or stride, a NULL required pointer.
+ * nsel == 0 or nseg == 0 is a valid empty call.  Zero-initialize the struct (it grows at the
+ * end). */
+#define FM_MAX_DSORT 10
+typedef struct fm_dsort_args {
+    const double* a;             /* [nsel or 1][nrows] first signal */
+    const double* b;             /* [nsel or 1][nrows] second signal */
+    int64_t a_sort_stride;       /* elements between the sorts' a vectors; 0: shared */
+    int64_t b_sort_stride;       /* elements between the sorts' b vectors; 0: shared */
+    const double* ret;           /* [nrows] */
+    const double* weight;        /* [nrows] or NULL */
+    const uint8_t* level;        /* [nrows] universe level or NULL */
+    const uint8_t* nyse;         /* [nrows] nonzero = NYSE row, or NULL */
+    const int64_t* seg_off;      /* [nseg+1] */
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t nseg;
+    int32_t nsel;                /* 0 .. 65,535 (the grid's second dimension) */
+    int32_t max_seg_len;         /* >= every month's rows, <= 16,384 */
+    int32_t na;                  /* 2 .. FM_MAX_DSORT */
+    int32_t nb;                  /* 2 .. FM_MAX_DSORT */
+    int32_t conditional;         /* 0: independent; nonzero: b within the a-bins */
+    int32_t min_level;
+    int32_t nyse_breakpoints;    /* nonzero: breakpoints from the NYSE rows only */
+    int32_t min_count;           /* >= 1 */
+    int32_t min_count_bin;       /* >= 1; read in conditional mode only */
+    double qa[FM_MAX_DSORT - 1]; /* [na-1] levels, strictly ascending in (0, 1) */
+    double qb[FM_MAX_DSORT - 1]; /* [nb-1] */
+    double* rec_b;               /* [nsel][na+1][nseg][nb+1][4] */
+    double* rec_a;               /* [nsel][nb+1][nseg][na+1][4] */
+    int32_t* cnt;                /* [nsel][nseg][na][nb] */
+    uint8_t* cell;               /* [nsel][nrows] or NULL */
+    double* bpa;                 /* [nsel][nseg][na-1] or NULL */
+    double* bpb;                 /* [nsel][nseg][na][nb-1] or NULL */
+    uint32_t* status;            /* [nsel][nseg] */
+} fm_dsort_args;
+
+int fm_portfolio_double_sort(const fm_dsort_args* args, void* stream);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
