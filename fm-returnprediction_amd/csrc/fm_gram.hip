@@ -38,7 +38,8 @@ __device__ uint32_t g_wgtime[4 * WGT_MAX];   // the probe's own buffer, bounds-c
 // One workgroup per chunk (normally a whole month: the chunk plan makes chunks as large as
 // the chip's resident workgroup slots allow, so the prologue and the cross-wave epilogue run
 // once per month and every wave streams ~20 tiles back to back).  MINW = waves per SIMD.
-template <int NT, int NB, int MINW, bool PL, bool FULLC>
+// SC: with inv_scale (the standardize pass), set at launch.
+template <int NT, int NB, int MINW, bool PL, bool FULLC, bool SC>
 __global__ __launch_bounds__(GT, MINW) void gram_kernel(fm_gram_args a) {
     using S = GramShape<NT>;
     __shared__ double tile[GNW * S::WT];
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(GT, MINW) void gram_kernel(fm_gram_args a) {
         }
         if (tid < 128) prm[tid >> 5][tid & 31] = pv;   // the previous chunk's epilogue ended in a barrier
         __syncthreads();
-        g.run(prm, lut, a.inv_scale != nullptr, tile, zblk);
+        g.template run<SC>(prm, lut, tile, zblk);
         g.epilogue(tile, a.partial + (int64_t)chunk * nbr * S::PK, nbr);
     }
 #if FM_GRAM_WGTIME
@@ -108,6 +109,12 @@ __global__ __launch_bounds__(GT, MINW) void gram_kernel(fm_gram_args a) {
 #endif
 }
 
+template <int NT, int NB, int MINW, bool PL, bool FULLC>
+void launch_gram_sc(const fm_gram_args& a, int grid, hipStream_t st) {
+    if (a.inv_scale != nullptr) hipLaunchKernelGGL((gram_kernel<NT, NB, MINW, PL, FULLC, true>), dim3(grid), dim3(GT), 0, st, a);
+    else hipLaunchKernelGGL((gram_kernel<NT, NB, MINW, PL, FULLC, false>), dim3(grid), dim3(GT), 0, st, a);
+}
+
 template <int NT, int NB, int MINW>
 void launch_gram(const fm_gram_args& a, hipStream_t st) {
     const int grid = a.wg_chunk_off != nullptr ? a.nwg : a.nchunks;
@@ -116,11 +123,11 @@ void launch_gram(const fm_gram_args& a, hipStream_t st) {
     // and plane for it)
     const bool full = a.ncols == 16 * NT - 1;
     if (a.hi_plane != nullptr) {
-        if (full) hipLaunchKernelGGL((gram_kernel<NT, NB, MINW, true, true>), dim3(grid), dim3(GT), 0, st, a);
-        else hipLaunchKernelGGL((gram_kernel<NT, NB, MINW, true, false>), dim3(grid), dim3(GT), 0, st, a);
+        if (full) launch_gram_sc<NT, NB, MINW, true, true>(a, grid, st);
+        else launch_gram_sc<NT, NB, MINW, true, false>(a, grid, st);
     } else {
-        if (full) hipLaunchKernelGGL((gram_kernel<NT, NB, MINW, false, true>), dim3(grid), dim3(GT), 0, st, a);
-        else hipLaunchKernelGGL((gram_kernel<NT, NB, MINW, false, false>), dim3(grid), dim3(GT), 0, st, a);
+        if (full) launch_gram_sc<NT, NB, MINW, false, true>(a, grid, st);
+        else launch_gram_sc<NT, NB, MINW, false, false>(a, grid, st);
     }
 }
 

@@ -2,8 +2,11 @@
 //
 // Per wave, 64-row tiles (one row per lane):
 //   1. ncols coalesced FP64 loads per row (SoA; the next tile's loads are in flight while
-//      this one is processed), clip to the month's winsorize cuts, shift by the month's
-//      pivot (optional standardize scale), z = [1, x..., y];
+//      this one is processed); z = [1, x..., y] with x clipped to the month's winsorize cuts,
+//      shifted by the month's pivot (optional standardize scale).  16 columns: the sorted tile
+//      holds the raw x and the clip is applied to the MFMA operand in step 3, from parameters
+//      each lane reads once per chunk for its own operand column (no parameter read in the
+//      tile loop).  32 columns: clipped before the scatter, parameters read from LDS per tile;
 //   2. the row's validity pattern (bit m: every column model m needs is non-NaN) and its
 //      universe level give a bucket id; per bucket one wave ballot gives the bucket's row
 //      count (SGPR) and the lane's rank, so the counting sort needs no LDS counters; each
@@ -26,7 +29,7 @@
 namespace fm {
 namespace {
 
-constexpr int CLIP_BW = FM_GRAM_CLIP_BW;   // month parameters read per batch of the clip (run)
+constexpr int CLIP_BW = FM_GRAM_CLIP_BW;   // month parameters read per batch of the clip (run, NT 2)
 
 // nn = 2 * nn + (x is not NaN): one compare + one add-with-carry
 __device__ __forceinline__ uint32_t push_valid(uint32_t nn, double x) {
@@ -87,7 +90,7 @@ struct GramShape {
 // One wave's share of the Gram of rows [r0, r1) (tiles w, w + NWV, ...).  Usage:
 //   GramWave g(a, r0, r1, w);  g.prefetch();   (first tile's loads in flight)
 //   ... fill the month parameters (prm) / pattern table (lut) / zero rows, barrier ...
-//   g.run(prm, lut, scaled, tile, zblk);  barrier-free per wave
+//   g.run<scaled>(prm, lut, tile, zblk);  barrier-free per wave
 //   g.epilogue(tile, outp);   (all waves: cross-wave sum + packed store, barriers inside)
 template <int NT, int NB, int NWV, bool PL = false, bool FULLC = false>
 struct GramWave {
@@ -160,8 +163,11 @@ struct GramWave {
     }
 
     // prm: LDS [4][32] = lo, hi, shift, inv_scale per column; lut: LDS pattern table.
-    __device__ __forceinline__ void run(const double (*prm)[32], const uint8_t* lut, bool scaled,
-                                        double* tile, const double* zblk) {
+    // SC: the scaled clip (* inv_scale), chosen at launch: each way has its own kernel, so the
+    // unscaled one carries neither the multiply nor the scale's registers.
+    template <bool SC>
+    __device__ __forceinline__ void run(const double (*prm)[32], const uint8_t* lut, double* tile,
+                                        const double* zblk) {
         constexpr BlockPairs<4 * NT> BP{};
         const int nmodels = a.nmodels, nlevels = a.nlevels;
         const int lvand = a.level ? 0xFF : 0;
@@ -187,6 +193,15 @@ struct GramWave {
 #pragma unroll
         for (int m = 0; m < FM_MAX_MODELS; ++m)
             mm[m] = (uint32_t)__builtin_amdgcn_readlane(mmv, m < nmodels ? m : 0);
+
+        // NT 1: the clip parameters of this lane's operand column q = lane & 15 (z column q is
+        // panel column q - 1), read once per chunk: a lane only ever holds values of that one
+        // column (see `group`), so the tile loop reads no parameter at all.  Lane q == 0 holds
+        // the constant column: slot 31 of prm is past every ncols (FM_MAX_COLS) and keeps the
+        // defaults (NaN bounds, shift 0.0, scale 1.0), under which the stored 1.0 passes through
+        // unchanged; so do the slots of the columns past ncols.
+        const int pc = ((lane & 15) - 1) & 31;
+        const double plo = prm[0][pc], phi = prm[1][pc], psh = prm[2][pc], pis = SC ? prm[3][pc] : 1.0;
 
         auto tile_step = [&](int t, int tnext) {
             const int64_t row = r0 + (int64_t)t * TR + lane;
@@ -230,33 +245,37 @@ struct GramWave {
             // column that is NaN in a row belongs to no model of the row's pattern, so the
             // Gram entries it pollutes are never read by fm_solve.  clip = hardware max/min:
             // a NaN bound is ignored, a NaN x gives a don't-care value.  Dropped rows are not
-            // stored.
+            // stored.  Per element the operations and their order are max, min, - shift
+            // (, * inv_scale).
+            //  NT 1: the tile holds [1, raw x ...]; the clip is applied to the MFMA operand
+            //        (`group`), from the lane's own column parameters.
+            //  NT 2: A and B operands come from different columns per lane, so the clip stays
+            //        here: the month parameters are read from prm in batches of CLIP_BW columns
+            //        per kind (the batch's LDS reads in flight together, then its arithmetic
+            //        in place on xv, dead after this).
             if (valid) {
                 double* dst = wt + dest * RS;
                 dst[0] = 1.0;
-                // The month parameters are read in batches of CLIP_BW columns per kind: the
-                // batch's LDS reads in flight together, then its arithmetic in place on xv
-                // (dead after this).  Read at the point of use, every parameter was its own
-                // dependent LDS round trip (22 waits per tile for 15 columns).  Per element
-                // the operations and their order are max, min, - shift (, * inv_scale).
                 constexpr int NC = ZW - 1;
-                auto sweep = [&](int kind, auto op) {
+                if constexpr (NT != 1) {
+                    auto sweep = [&](int kind, auto op) {
 #pragma unroll
-                    for (int c0 = 0; c0 < NC; c0 += CLIP_BW) {
-                        double p[CLIP_BW];
+                        for (int c0 = 0; c0 < NC; c0 += CLIP_BW) {
+                            double p[CLIP_BW];
 #pragma unroll
-                        for (int i = 0; i < CLIP_BW; ++i) p[i] = prm[kind][c0 + i < NC ? c0 + i : NC - 1];
-                        __builtin_amdgcn_sched_barrier(0);
+                            for (int i = 0; i < CLIP_BW; ++i) p[i] = prm[kind][c0 + i < NC ? c0 + i : NC - 1];
+                            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                        for (int i = 0; i < CLIP_BW; ++i)
-                            if (c0 + i < NC) xv[c0 + i] = op(xv[c0 + i], p[i]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                };
-                sweep(0, [](double x, double p) { return hw_max(x, p); });
-                sweep(1, [](double x, double p) { return hw_min(x, p); });
-                sweep(2, [](double x, double p) { return x - p; });
-                if (scaled) sweep(3, [](double x, double p) { return x * p; });
+                            for (int i = 0; i < CLIP_BW; ++i)
+                                if (c0 + i < NC) xv[c0 + i] = op(xv[c0 + i], p[i]);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    };
+                    sweep(0, [](double x, double p) { return hw_max(x, p); });
+                    sweep(1, [](double x, double p) { return hw_min(x, p); });
+                    sweep(2, [](double x, double p) { return x - p; });
+                    if (SC) sweep(3, [](double x, double p) { return x * p; });
+                }
 #pragma unroll
                 for (int c = 0; c < NC; ++c) dst[1 + c] = xv[c];
             }
@@ -290,11 +309,16 @@ struct GramWave {
                     // one 4-row group: operand `cur` (read one group ahead), the next group's
                     // read into `nxt`.  Rows past the tile end (rn + kr <= TR + 3: lanes of rows
                     // past a bucket's count) read this wave's own TPAD pad rows, never another
-                    // wave's tile; their (unwritten) values are masked here
+                    // wave's tile; their (unwritten, then clipped: arbitrary) values are masked
+                    // here, after the clip and before the rotations
                     auto group = [&](int g, const double cur, double& nxt) {
                         const int rn = g + 4 < n ? off + g + 4 : off + n;
                         nxt = rd[rn * RS];
-                        const double A = kr < n - g ? cur : 0.0;
+                        // the clip, on the operand: every lane of a rotation source holds its
+                        // own column's value, so B1 / B2 arrive clipped
+                        double z = hw_min(hw_max(cur, plo), phi) - psh;
+                        if (SC) z = z * pis;
+                        const double A = kr < n - g ? z : 0.0;
                         const double B1 = dpp_f64<0x12C>(A), B2 = dpp_f64<0x128>(A);
                         acc[b][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(A, A, acc[b][0], 0, 0, 0);
                         acc[b][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(A, B1, acc[b][1], 0, 0, 0);
