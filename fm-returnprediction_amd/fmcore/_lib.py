@@ -243,6 +243,18 @@ class DsortArgs(C.Structure):
     ]
 
 
+FM_WLS_MAX_COLS = 15
+
+
+class WlsArgs(C.Structure):
+    _fields_ = [
+        ("cols", _p), ("col_stride", _i64), ("nrows", _i64), ("ncols", _i32), ("nseg", _i32), ("seg_off", _p),
+        ("lo", _p), ("hi", _p), ("shift", _p), ("level", _p), ("weight", _p), ("nprob", _i32), ("pmax", _i32),
+        ("prob_level", _p), ("prob_z", _p), ("prob_nz", _p), ("rec", _p), ("status", _p), ("moments", _p),
+        ("mom_stride", _i32), ("pad_wls", _i32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -290,6 +302,7 @@ _SIGS = {
     "fm_group_adjust": (_i32, [C.POINTER(GroupAdjArgs), _p]),
     "fm_group_adjust_batch": (_i32, [_i32]),
     "fm_portfolio_double_sort": (_i32, [C.POINTER(DsortArgs), _p]),
+    "fm_wls": (_i32, [C.POINTER(WlsArgs), _p]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -310,7 +323,7 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
             "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs,
             "fm_hold_args": HoldArgs, "fm_gadj_args": GroupAdjArgs,
-            "fm_dsort_args": DsortArgs}
+            "fm_dsort_args": DsortArgs, "fm_wls_args": WlsArgs}
 
 _lib = None
 

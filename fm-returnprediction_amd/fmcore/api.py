@@ -39,6 +39,13 @@ def raise_like_reference(status, K, what="exog"):
     raise IndexError(f"index {K - 1} is out of bounds for axis 0 with size {K - 1}")
 
 
+def raise_like_reference_wls(status, what="exog"):
+    """The weighted cross-sections' (fm_wls) counterpart: a month with an inf regressor is flagged
+    FM_ST_INF_IN_X (and is not fitted); sm.WLS would raise the same MissingDataError there."""
+    if (np.asarray(status) & L.FM_ST_INF_IN_X).any():
+        raise MissingDataError(f"{what} contains inf or nans")
+
+
 def cs_frame(months, rec, status, pmax, predictor_cols, date_col):
     """Monthly results frame with the reference's columns: date, N, R2, slope_<x>...
     (src/regressions.py:68-75)."""

@@ -1064,6 +1064,74 @@ def fm_pass(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, 
                     mom_stride=mom_stride)
 
 
+def wls_weight(panel: DevicePanel, weight):
+    """The [rows] FP64 weight vector ``fm_pass_wls`` reads: None or "me" the panel's market equity,
+    another string a panel column by name, anything else a float64 [rows] tensor on the panel's device."""
+    if weight is None or (isinstance(weight, str) and weight == "me"):
+        if panel.me is None:
+            raise ValueError("fm_pass_wls: the panel has no market equity (me) to weight by")
+        return panel.me
+    if isinstance(weight, str):
+        if weight not in panel.names:
+            raise ValueError(f"fm_pass_wls: the panel has no column {weight!r} to weight by")
+        return column_vector(panel, weight)
+    return _row_vector(weight, torch.float64, panel.nrows, panel.device, "weight")
+
+
+def _wls_tables(panel, models, problems, dev):
+    """The problem tables fm_wls reads (fm_solve's prob_level / prob_z / prob_nz), made once per
+    model set and kept with the panel."""
+    key = (tuple((m.y, tuple(m.xs)) for m in models), tuple((p.model, p.level) for p in problems), str(dev))
+    cache = panel.__dict__.setdefault("_wls_cache", {})
+    if key not in cache:
+        pz = np.zeros((len(problems), 32), dtype=np.int32)
+        pnz = np.zeros(len(problems), dtype=np.int32)
+        for j, p in enumerate(problems):
+            m = models[p.model]
+            z = [0] + [1 + x for x in m.xs] + [1 + m.y]
+            pz[j, :len(z)] = z
+            pnz[j] = len(z)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        cache[key] = (t(np.array([p.level for p in problems], dtype=np.int32)), t(pz), t(pnz))
+    return cache[key]
+
+
+def fm_pass_wls(panel: DevicePanel, models: Sequence[Model], weight=None, level=None, nlevels=1, cuts: Cuts = None,
+                shift=None, moments=False):
+    """The weighted counterpart of fm_pass (A22, fm_wls): per month and (model, universe level)
+    problem the weighted least-squares fit of y on [1, x], the weights ``weight`` (see wls_weight;
+    usually market equity), in one launch.  Rows of NaN, +-inf, zero or negative weight are dropped.
+    Returns an FMResult laid out as fm_pass lays it out, so every later stage runs on it unchanged.
+    FP64 columns, at most 15 of them; ``shift`` [C, T] is only the pivot of the kernel's first pass."""
+    if panel.cols is None:
+        raise ValueError("fm_pass_wls: a planes-only panel is not supported (fm_wls reads FP64 columns)")
+    src = panel.cols
+    dev = src.device
+    T = panel.nseg
+    if src.shape[0] > L.FM_WLS_MAX_COLS:
+        raise ValueError(f"fm_pass_wls: at most {L.FM_WLS_MAX_COLS} columns per pass")
+    wv = wls_weight(panel, weight)
+    problems = _problems(models, nlevels)
+    pmax = max(2, max(p.K + 1 for p in problems))
+    nprob = len(problems)
+    mom_stride = 1 + (pmax + 1) + (pmax + 1) ** 2
+    rec = torch.empty((T, nprob, pmax + 2), dtype=torch.float64, device=dev)
+    status = torch.empty((T, nprob), dtype=torch.int32, device=dev)   # the kernel writes every entry
+    mom = torch.empty((T, nprob, mom_stride), dtype=torch.float64, device=dev) if moments else None
+    lo = cuts.lo if cuts is not None else None
+    hi = cuts.hi if cuts is not None else None
+    pl, pz, pnz = _wls_tables(panel, models, problems, dev)
+    wa = L.WlsArgs(
+        cols=src.data_ptr(), col_stride=src.stride(0), nrows=panel.nrows, ncols=src.shape[0], nseg=T,
+        seg_off=panel.seg_off.data_ptr(), lo=_ptr(lo), hi=_ptr(hi), shift=_ptr(shift), level=_ptr(level),
+        weight=wv.data_ptr(), nprob=nprob, pmax=pmax, prob_level=pl.data_ptr(), prob_z=pz.data_ptr(),
+        prob_nz=pnz.data_ptr(), rec=rec.data_ptr(), status=status.data_ptr(), moments=_ptr(mom),
+        mom_stride=mom_stride)
+    _kcall("fm_wls", "fm_wls", L.C.byref(wa), _stream())
+    _remember("fm_wls", "fm_wls", wa, src, wv, lo, hi, shift, level, pl, pz, pnz, rec, status, mom)
+    return FMResult(problems=problems, rec=rec, status=status, pmax=pmax, moments=mom, mom_stride=mom_stride)
+
+
 def drop_degenerate_months(res: FMResult, models: Sequence[Model], sd):
     """Standardized passes (A9): a month in which a regressor has fewer than two values or
     zero dispersion has an all-NaN z-score column, so every row drops out and the month is

@@ -23,6 +23,8 @@ with the factors, its alphas, in one more launch.
 With ``PipelineConfig.double_sort`` = a panel column those forecasts are also sorted two ways, against
 that column (size, say), into na x nb cells: each row's spread and the column-neutral spread
 (build-defined A21).
+With ``PipelineConfig.wls_weights`` (e.g. "me") every monthly cross-section is a weighted
+least-squares fit (engine.fm_pass_wls) and every later stage runs on the weighted slopes.
 With ``PipelineConfig.extrapolate`` = k the monthly run also scales every month's forecasts to k
 months and regresses the compounded k-month return on them (paper Section 4's second approach, the
 lower panels of Tables 9a and 9b; build-defined A17), in one more launch.
@@ -116,6 +118,14 @@ class PipelineConfig:
     double_sort: Optional[str] = field(default=None, kw_only=True)
     double_sort_shape: Sequence[int] = field(default=(5, 5), kw_only=True)
     double_sort_conditional: bool = field(default=False, kw_only=True)
+    # A22 (the value-weighted regressions): ``wls_weights`` = "me" (the panel's market equity), a panel
+    # column by name or a [rows] tensor makes every monthly cross-section a weighted least-squares fit
+    # (engine.fm_pass_wls in place of fm_pass: rows of NaN, infinite, zero or negative weight drop
+    # out); group adjustment, ranks, cuts and universes run in front of it as they are, the
+    # time-series stage and every forecast stage behind it, on the weighted slopes.  Excludes
+    # standardize and a planes-only panel: ValueError.  None = exactly the launches of before.  Here,
+    # in front of every field whose place tests pin.
+    wls_weights: Optional[object] = field(default=None, kw_only=True)
     # A14 inside the pipeline (paper Table 3's univariate properties): each month's cross-sectional
     # mean, standard deviation and ``forecast_dist_q`` quantiles of the same forecasts, over the same
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
@@ -267,6 +277,7 @@ def _local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx"
     inv_scale = None
     level, bp = None, None
     nlevels = 1
+    check_wls(cfg, panel)
     models, names = build_models(panel, model_cols, y=y, fig1=cfg.fig1, universes=cfg.universes)
     gadj = None
     if cfg.group_adjust is not None:
@@ -318,6 +329,11 @@ def _local_stage(panel: E.DevicePanel, cfg: PipelineConfig, model_cols, y="retx"
         if not cfg.winsorize:
             cuts = E.Cuts(torch.full_like(cuts.lo, float("nan")), torch.full_like(cuts.hi, float("nan")),
                           cuts.nvalid, cuts.mean, cuts.sd, cuts.center)
+    if cfg.wls_weights is not None:
+        # A22: the weighted cross-sections; the cuts' centre is only the pivot of its first pass
+        res = E.fm_pass_wls(panel, models, weight=cfg.wls_weights, level=level, nlevels=nlevels, cuts=cuts,
+                            shift=shift, moments=cfg.forecasts)
+        return res, names, cuts, level, bp, panel, models, gadj
     res = E.fm_pass(panel, models, level=level, nlevels=nlevels, cuts=cuts, shift=shift,
                     inv_scale=inv_scale, add_back=add_back if cfg.standardize else shift,
                     moments=cfg.forecasts)
@@ -337,6 +353,24 @@ def time_series_stage(res: E.FMResult, cfg: PipelineConfig, moments=None, seg_lo
         res, cfg.nw_lags, cfg.window, cfg.min_periods, cfg.lag, seg_lo=seg_lo, seg_hi=seg_hi,
         moments=moments, rolling=cfg.forecasts or cfg.fig1, predictive=cfg.forecasts,
         sum_range=sum_range, roll_own=roll_own)
+
+
+def check_wls(cfg: PipelineConfig, panel=None, y="retx"):
+    """The rules of ``PipelineConfig.wls_weights`` (no device work); ``panel``: the run's panel, when
+    there is one; ``y``: the dependent column's name before ``horizon`` renames it."""
+    if cfg.wls_weights is None:
+        return
+    if cfg.standardize:
+        raise ValueError("PipelineConfig: wls_weights excludes standardize (weighted z-scores are not wired)")
+    if panel is not None and panel.cols is None:
+        raise ValueError("PipelineConfig: wls_weights needs a panel with FP64 columns, not a planes-only one")
+    if panel is not None:
+        # fm_wls takes a panel of at most 15 columns; horizon > 1 appends the k-month return to it
+        extra = int(cfg.horizon > 1 and f"{y}_{cfg.horizon}m" not in panel.names)
+        if panel.ncols + extra > E.L.FM_WLS_MAX_COLS:
+            raise ValueError(f"PipelineConfig: wls_weights takes a panel of at most {E.L.FM_WLS_MAX_COLS} columns, this "
+                             f"one has {panel.ncols}" + (f" and horizon={cfg.horizon} adds the k-month return" if extra
+                                                         else ""))
 
 
 def check_horizon(cfg: PipelineConfig):
@@ -509,6 +543,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     check_hold(cfg, panel)
     check_double_sort(cfg, panel)
     check_group_adjust(cfg, panel, model_cols, y)
+    check_wls(cfg, panel, y)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
         if on and cfg.standardize:

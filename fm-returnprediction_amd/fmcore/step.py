@@ -48,6 +48,9 @@ class ShardedStep:
                              "forecasts the double sort reads)")
         if cfg.group_adjust is not None:
             raise ValueError("ShardedStep: cfg.group_adjust must be None (the sharded ingest carries no group codes)")
+        if cfg.wls_weights is not None:
+            raise ValueError("ShardedStep: cfg.wls_weights must be None (the step's Gram exchange carries fm_gram's "
+                             "partials, which hold no weights)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols
         self.world, self.rank, self.group = world, rank, group
         self.seg_lo = seg_lo

@@ -471,8 +471,9 @@ def _batched_subsets(subsets):
     return a, abt.astype(np.uint8) + lg.astype(np.uint8)
 
 
-def _fm_summaries(df, model_cols, level=None, nlevels=1, fig1=False, moments=False):
-    """Device FM pass of several models over one frame (optionally levelled)."""
+def _fm_summaries(df, model_cols, level=None, nlevels=1, fig1=False, moments=False, weight_col=None):
+    """Device FM pass of several models over one frame (optionally levelled); ``weight_col``: the
+    weighted cross-sections (fm_wls) with that column of the frame as row weights."""
     cols = []
     for xs in model_cols.values():
         for c in ["retx"] + list(xs):
@@ -483,7 +484,8 @@ def _fm_summaries(df, model_cols, level=None, nlevels=1, fig1=False, moments=Fal
             if c not in cols:
                 cols.append(c)
     arrays = [_api.as_f64(df[c]) for c in cols]
-    panel = _E.panel_from_arrays(arrays, cols, df["mthcaldt"].values)
+    panel = _E.panel_from_arrays(arrays, cols, df["mthcaldt"].values,
+                                 me=None if weight_col is None else _api.as_f64(df[weight_col]))
     lvl_t = None
     if level is not None:
         import torch
@@ -491,7 +493,10 @@ def _fm_summaries(df, model_cols, level=None, nlevels=1, fig1=False, moments=Fal
     levels = tuple(range(nlevels))
     models = [_E.Model(n, y=panel.col("retx"), xs=[panel.col(c) for c in xs], levels=levels)
               for n, xs in model_cols.items()]
-    res = _E.fm_pass(panel, models, level=lvl_t, nlevels=nlevels, moments=moments)
+    if weight_col is not None:
+        res = _E.fm_pass_wls(panel, models, weight="me", level=lvl_t, nlevels=nlevels, moments=moments)
+    else:
+        res = _E.fm_pass(panel, models, level=lvl_t, nlevels=nlevels, moments=moments)
     return panel, models, res
 
 
@@ -543,9 +548,11 @@ def _format_table_2(stats, subset_names):
     return pd.DataFrame(rows, index=idx, columns=cols, dtype=object)
 
 
-def build_table_2(subsets_comp_crsp: dict, variables_dict: dict) -> pd.DataFrame:
+def build_table_2(subsets_comp_crsp: dict, variables_dict: dict, weight_col: str = None) -> pd.DataFrame:
     """Lewellen Table 2: Fama-MacBeth slopes, NW(4) t-stats, mean R^2 and mean N for
-    Models 1-3 on each universe (reference src/calc_Lewellen_2014.py:674-868)."""
+    Models 1-3 on each universe (reference src/calc_Lewellen_2014.py:674-868).  ``weight_col``
+    (build-defined, A22; no reference line), e.g. "me": the same table from weighted cross-sections
+    (run_monthly_cs_regressions' ``weight_col``)."""
     model_cols = _LW.table2_models(variables_dict)
     stats = {}
     batched = _batched_subsets(subsets_comp_crsp)
@@ -557,12 +564,15 @@ def build_table_2(subsets_comp_crsp: dict, variables_dict: dict) -> pd.DataFrame
         for s, frame in subsets_comp_crsp.items():
             jobs.append((frame, None, 1, {0: s}))
     for frame, level, nlevels, level_names in jobs:
-        panel, models, res = _fm_summaries(frame, model_cols, level, nlevels)
+        panel, models, res = _fm_summaries(frame, model_cols, level, nlevels, weight_col=weight_col)
         status_h = res.status.cpu().numpy()
         # the reference loop order is model-major, subset-minor: raise on the first failure
         order = sorted(range(len(res.problems)), key=lambda k: (res.problems[k].model, res.problems[k].level))
         for k in order:
-            _api.raise_like_reference(status_h[:, k], res.problems[k].K)
+            if weight_col is not None:
+                _api.raise_like_reference_wls(status_h[:, k])
+            else:
+                _api.raise_like_reference(status_h[:, k], res.problems[k].K)
         summ, _ = _E.summarize_result(res)
         mean, se, t, nobs = (summ.mean.cpu().numpy(), summ.se.cpu().numpy(), summ.tstat.cpu().numpy(),
                              summ.nobs.cpu().numpy())

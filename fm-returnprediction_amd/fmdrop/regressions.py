@@ -16,24 +16,37 @@ MissingDataError = _api.MissingDataError
 
 
 def run_monthly_cs_regressions(df: pd.DataFrame, return_col: str, predictor_cols: list,
-                               date_col: str = "mthcaldt") -> pd.DataFrame:
+                               date_col: str = "mthcaldt", weight_col: str = None) -> pd.DataFrame:
     """Per-month cross-sectional OLS of ``return_col`` on an intercept and
     ``predictor_cols`` (reference src/regressions.py:9-76).
 
     Rows with NaN in any of [return_col, date_col] + predictor_cols are dropped; months
     with fewer than K+1 rows are skipped; returns one row per fitted month with columns
     [date_col, 'N', 'R2', 'slope_<col>'...] in ascending month order.
+
+    ``weight_col`` (build-defined, A22; no reference line): the frame's column of row weights, e.g.
+    "me": every month is then a weighted least-squares fit (statsmodels' WLS; fm_wls), R2 its
+    weighted R2 and N the rows used -- rows whose weight is NaN, infinite, zero or negative drop out
+    too.  The same frame and columns; months whose regressors are collinear or constant
+    (FM_ST_RANK_DEF) are absent like skipped months, an inf regressor raises MissingDataError.
     """
     predictor_cols = list(predictor_cols)
     sub = df[[return_col, date_col] + predictor_cols]
     names = predictor_cols + [return_col]
     arrays = [_api.as_f64(sub[c]) for c in names]
-    panel = _E.panel_from_arrays(arrays, names, sub[date_col].values)
     K = len(predictor_cols)
-    res = _E.fm_pass(panel, [_E.Model("m", y=K, xs=list(range(K)))])
+    if weight_col is not None:
+        panel = _E.panel_from_arrays(arrays, names, sub[date_col].values, me=_api.as_f64(df[weight_col]))
+        res = _E.fm_pass_wls(panel, [_E.Model("m", y=K, xs=list(range(K)))], weight="me")
+    else:
+        panel = _E.panel_from_arrays(arrays, names, sub[date_col].values)
+        res = _E.fm_pass(panel, [_E.Model("m", y=K, xs=list(range(K)))])
     status = res.status[:, 0].cpu().numpy()
     rec = res.rec[:, 0, :].cpu().numpy()
-    _api.raise_like_reference(status, K)
+    if weight_col is not None:
+        _api.raise_like_reference_wls(status)
+    else:
+        _api.raise_like_reference(status, K)
     return _api.cs_frame(panel.months, rec, status, res.pmax, predictor_cols, date_col)
 
 

@@ -76,6 +76,9 @@
  *                      adjusted within a group of firms (an industry) per month -- the value minus
  *                      its group's mean, the group mean, or the within-group z-score (pandas
  *                      groupby([month, industry]).transform; Asness, Porter and Stevens 2000)
+ *   fm_wls          <- build-defined extension A22; no reference line: the weighted (value-weighted)
+ *                      monthly cross-sections, statsmodels' WLS per month, written as fm_solve
+ *                      writes the OLS ones
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -232,7 +235,7 @@ const char* fm_last_error(void);
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
     X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)      \
-    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args) X(fm_dsort_args)
+    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args) X(fm_dsort_args) X(fm_wls_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -1144,6 +1147,81 @@ typedef struct fm_dsort_args {
 } fm_dsort_args;
 
 int fm_portfolio_double_sort(const fm_dsort_args* args, void* stream);
+
+/* fm_wls: the weighted (value-weighted) monthly cross-sections: for every month and every problem
+ * (model x universe level) the weighted least-squares fit of y on [1, x], in one launch, grid
+ * (month, problem) (build-defined extension A22; the reference has no WLS, so no reference line:
+ * the definition is statsmodels' WLS(y, add_constant(x), weights=w) on the rows used).  It writes
+ * what fm_solve writes for OLS -- rec, status and the optional moments in the same layouts -- so the
+ * time-series and forecast stages run on it unchanged.  FP64 columns, at most FM_WLS_MAX_COLS of
+ * them (z = [1, x.., y] is at most 16 wide); rows sorted by (month, permno), months
+ * seg_off[nseg+1] of any length.  Problem p reads the z list prob_z[p][0..prob_nz[p]) = 0 (the
+ * intercept), 1 + the panel columns of x_1 .. x_K, 1 + the panel column of y (fm_solve_args'
+ * tables; K = prob_nz[p] - 2 <= pmax - 1): the model's columns are exactly that list, so there is no
+ * mask table.  Per (month t, problem p):
+ *   a row is used when every column of the list (y included) is non-NaN, level >= prob_level[p]
+ *     (level NULL: every row) and its weight is finite and > 0: fm_gram's rule plus the weight's.
+ *     Rows of NaN, +-inf, zero or negative weight are dropped and do not count;
+ *   values are clipped first, as fm_gram clips: max with lo, then min with hi, both [ncols][nseg];
+ *     a NaN bound is ignored; lo == hi == NULL: no clipping;
+ *   N = the number of rows used.  N < K + 1: status FM_ST_SKIPPED alone, rec NaN but rec[pmax+1] = N;
+ *   a used row with +-inf after clipping in x / in y: status FM_ST_INF_IN_X / FM_ST_INF_IN_Y (or
+ *     both) alone -- not FITTED -- and rec as for a skipped month;
+ *   with W = sum(w), the weighted means m = sum(w z) / W and w~ = w N / W (the weights scaled to
+ *     sum to N), the centred moments S = sum(w~ (z - m)(z - m)') over (x_1 .. x_K, y);
+ *   a predictor whose S_kk is not above 1e-20 (S_kk + N m_k^2) -- rounding beside its raw second
+ *     moment: a constant, or all-zero, column -- or a Cholesky pivot of Sxx that is not above 1e-6
+ *     (fm_solve's REFIT_REL) of its diagonal entry S_kk: status FM_ST_RANK_DEF alone, rec as for a
+ *     skipped month.  There is no CONST_COL / CONST_SUSPECT logic and no pinv re-solve;
+ *   otherwise status FM_ST_FITTED and b = Sxx^-1 Sxy (the minimiser of sum(w (y - a - b'x)^2)),
+ *     rec[0] = a = m_y - b'm_x, rec[1..K] = b, rec[K+1..pmax) NaN,
+ *     rec[pmax] = R2 = 1 - (Syy - b'Sxy) / Syy = 1 - SSR_w / sum(w (y - m_y)^2) (statsmodels'
+ *     WLS.rsquared), rec[pmax+1] = N.  N == K + 1 is fitted.  A constant y is no special case, as in
+ *     fm_solve: Syy = 0 gives slopes of 0 and R2 = 0 / 0 = NaN under FM_ST_FITTED (statsmodels
+ *     divides by the same zero); the time-series summaries skip a NaN R2 as they skip any NaN;
+ *   moments (optional; written where N >= K + 1 and no value is +-inf): [0] = N, [1 + i] = m_i in
+ *     raw units, [1 + K1 + i K1 + j] = S_ij with K1 = K + 1 and i, j over (x_1 .. x_K, y): fm_solve's
+ *     index layout and its centred block, so fm_predictive / fm_ts_fused give the weighted
+ *     predictive slope and R2 from it (fm_solve's means are about its pivot; these are raw).
+ * Numerics: two passes over the month (L2-resident), the first about `shift` ([ncols][nseg], NULL:
+ * 0) for the means, the second about the means for S; the first moments the second pass still
+ * finds are subtracted.  Every sum runs in one fixed order that depends on the month's USED rows
+ * alone: they are numbered in row order, cut into tiles of 64, tile c goes to wave c % 4 of the
+ * workgroup, which adds its tiles in order, four rows per v_mfma_f64_16x16x4_f64 (A = w z, B = z);
+ * the four waves' sums are then added in wave order.  No floating-point atomics.  So a repeat, a
+ * sub-range of the months, a subset of the problems, the panel with dropped rows taken out, and
+ * weights multiplied by a power of two (short of overflow and underflow) all give the same bits.
+ * Refused with FM_EINVAL before the launch: ncols outside 1..FM_WLS_MAX_COLS, pmax outside
+ * 1..FM_WLS_MAX_COLS, more than 65,535 problems, a negative size, col_stride < nrows, lo without hi,
+ * a mom_stride that does not hold 1 + (pmax+1) + (pmax+1)^2, a NULL required pointer.  Column
+ * indices outside the panel are clamped into it.  nseg == 0 or nprob == 0 is a valid empty call.
+ * Zero-initialize the struct (it grows at the end). */
+#define FM_WLS_MAX_COLS 15
+typedef struct fm_wls_args {
+    const double* cols;          /* [ncols][col_stride] */
+    int64_t col_stride;
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t ncols;               /* 1 .. FM_WLS_MAX_COLS */
+    int32_t nseg;
+    const int64_t* seg_off;      /* [nseg+1] */
+    const double* lo;            /* [ncols][nseg] clip bounds, or both NULL */
+    const double* hi;
+    const double* shift;         /* [ncols][nseg] pivot of the first pass, or NULL */
+    const uint8_t* level;        /* [rows] universe level, or NULL */
+    const double* weight;        /* [rows] */
+    int32_t nprob;
+    int32_t pmax;                /* >= max K + 1 over the problems, <= FM_WLS_MAX_COLS */
+    const int32_t* prob_level;   /* [nprob] */
+    const int32_t* prob_z;       /* [nprob][32] z indices: 0, 1 + x columns..., 1 + y column */
+    const int32_t* prob_nz;      /* [nprob] K + 2 */
+    double* rec;                 /* [nseg][nprob][pmax+2] */
+    uint32_t* status;            /* [nseg][nprob] FM_ST_* bits */
+    double* moments;             /* [nseg][nprob][mom_stride] or NULL */
+    int32_t mom_stride;
+    int32_t pad_wls;
+} fm_wls_args;
+
+int fm_wls(const fm_wls_args* args, void* stream);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
