@@ -28,15 +28,13 @@
 // the sort keeps anyway; phase 4 reads the return column through the same layout.  No clipped
 // panel and no forecast vector ever reach HBM.
 //
-// fm_forecast_dist (A14; paper Table 3) is fdist_kernel below: the same phases 1-2 from the same
-// three sources, then two fixed-order reductions of the forecasts instead of phases 3-4.
-//
-// fm_forecast_compare (A15; paper Table 4) is fcmp_kernel below, over a grid of (month, pair):
-// phase 1's load for the pair's two forecasts, then eleven of those reductions and no selection.
-//
-// fm_forecast_horizon (A17; paper Section 4, second approach) is fhor_kernel below: fdist_kernel's
-// phases 1-2, the forecasts scaled around their mean in place, then eight of those reductions, the
-// last five against the long-horizon return vector.
+// The forecast statistics -- fm_forecast_dist (A14; paper Table 3; fdist_kernel), fm_forecast_compare
+// (A15; paper Table 4; fcmp_kernel, over a grid of (month, pair)) and fm_forecast_horizon (A17; paper
+// Section 4, second approach; fhor_kernel) -- keep the month in registers as phase 1 leaves it and are
+// written in terms of the device helpers above fdist_kernel: load_eligible (phase 1 from the same three
+// sources), quantile_keys (phase 2), load_returns, and for every sum masked_sum / tile_sum, whose order
+// depends on the month's rows alone; fit_rows is the regression of one row set on another built from
+// them.  No list is staged and no row is partitioned.
 #include <math.h>
 
 #include "fm_common.h"
@@ -53,8 +51,8 @@ namespace {
 
 // What a month's workgroup sorts by.  PlainSrc: the caller's forecast and return vectors
 // (fm_portfolio_sort).  PanelSrc<PL>: sort j of the fm_forecast_src that fm_fport_args,
-// fm_fdist_args and fm_fhor_args embed as `src`, panel values from the FP64 columns or (PL) from the planes, two
-// 4-byte loads joined in registers.
+// fm_fdist_args, fm_fcmp_args and fm_fhor_args embed as `src`, panel values from the FP64 columns or
+// (PL) from the planes, two 4-byte loads joined in registers.
 struct PlainSrc {
     static constexpr bool FUSED = false;
     __device__ static PlainSrc make(const fm_port_args&) { return {}; }
@@ -497,7 +495,26 @@ int launch(const A& a, dim3 grid, size_t lds, const char* who, hipStream_t st) {
     return check_launch(who);
 }
 
-// What both entry points ask of the arguments they share
+// Every entry point here gives a month one workgroup: the refusal of longer months
+int check_max_rows(int max_seg_len, const char* who) {
+    if (max_seg_len <= PORT_MAX_ROWS) return FM_OK;
+    set_error("%s: %d-row months exceed %d", who, max_seg_len, PORT_MAX_ROWS);
+    return FM_ETOOBIG;
+}
+
+// What fm_forecast_dist and fm_forecast_horizon ask of the arguments they share
+int check_dist_args(int nq, const double* q, int min_count, int max_seg_len, const char* who) {
+    FM_REQUIRE(max_seg_len >= 0, "%s: bad sizes", who);
+    FM_REQUIRE(nq >= 0 && nq <= FM_MAX_DIST_Q, "%s: nq must be 0..%d", who, FM_MAX_DIST_Q);
+    for (int i = 0; i < nq; ++i) {
+        const double lo = i == 0 ? 0.0 : q[i - 1];
+        FM_REQUIRE(q[i] > lo && q[i] < 1.0, "%s: q must be strictly ascending in (0, 1)", who);
+    }
+    FM_REQUIRE(min_count >= 1, "%s: min_count must be >= 1", who);
+    return FM_OK;
+}
+
+// What both sorts' entry points ask of the arguments they share
 template <class A>
 int check_sort_args(const A& a, const char* who) {
     FM_REQUIRE(a.nport >= 2 && a.nport <= FM_MAX_PORTS, "%s: nport must be 2..%d", who, FM_MAX_PORTS);
@@ -507,11 +524,7 @@ int check_sort_args(const A& a, const char* who) {
     }
     FM_REQUIRE(a.nyse_breakpoints == 0 || a.nyse != nullptr, "%s: nyse_breakpoints needs nyse", who);
     FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
-    if (a.max_seg_len > PORT_MAX_ROWS) {
-        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
-        return FM_ETOOBIG;
-    }
-    return FM_OK;
+    return check_max_rows(a.max_seg_len, who);
 }
 
 // What both fused entry points ask of their fm_forecast_src over nseg months; vec: the caller's
@@ -545,13 +558,11 @@ int check_forecast_src(const fm_forecast_src& f, int nseg, const char* who, bool
     return FM_OK;
 }
 
-// ---- fm_forecast_dist (extension A14; paper Table 3) -----------------------------------------
-// Per (month, sort): the count, mean, ddof-1 standard deviation and nq quantiles of the eligible
-// forecasts.  Phases 1-2 are port_kernel's (the same loads, fused_forecast, the same sample select
-// and full sort, here as the device function order_stat_keys: port_kernel keeps its own text for
-// the register count noted above it, and tests/test_gpu_fdist.py holds the two to the same keys);
-// phase 3 reduces the fe registers twice instead of partitioning rows.  No list is staged and
-// neither return nor weight is read.
+// ---- what the forecast statistics share ------------------------------------------------------
+// Phases 1-2 are port_kernel's (the same loads, fused_forecast, the same sample select and full
+// sort, here as the device function order_stat_keys: port_kernel keeps its own text for the
+// register count noted above it, and tests/test_gpu_fdist.py holds the two to the same keys).
+// Every sum over a month's rows goes through tile_sum, by way of masked_sum.
 
 // The plain source of fm_forecast_dist and fm_forecast_horizon: sort j's forecasts are the caller's vector j
 struct VecSrc {
@@ -586,10 +597,120 @@ __device__ __forceinline__ double tile_sum(const double (&x)[VPT], double* s_til
     return s_tile[NTILE];
 }
 
+// tile_sum of term(v) over the thread's rows whose bit of mask is set (+0.0 for the others); term
+// is a lambda over the caller's registers
+template <int NW, int VPT, class Term>
+__device__ __forceinline__ double masked_sum(uint32_t mask, double* s_tile, int w, int lane, Term term) {
+    double x[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) x[v] = ((mask >> v) & 1u) ? term(v) : 0.0;
+    return tile_sum<NW, VPT>(x, s_tile, w, lane);
+}
+
+// The thread's row v of an L-row month: row_index is in the month when it is below L; every load
+// goes to row_clamped (the month's last row beyond it), unconditionally, and is masked after
+template <int VPT>
+__device__ __forceinline__ int row_index(int w, int v, int lane) {
+    return (w * VPT + v) * WAVE + lane;
+}
+__device__ __forceinline__ int row_clamped(int idx, int L) { return idx < L ? idx : L - 1; }
+__device__ __forceinline__ int row_level(const uint8_t* level, int64_t row) {
+    return level != nullptr ? (int)level[row] : 255;
+}
+
+// Phase 1 of month s of sort src.j (L rows from r0; A is fm_fdist_args or fm_fhor_args): fe[v] = the
+// forecast of the thread's row v, fused or from the caller's vector, where the row is eligible (in
+// the month, finite, at the sort's level), NaN elsewhere.  Returns the eligible rows' bit mask.
+template <int VPT, class A, class Src>
+__device__ __forceinline__ uint32_t load_eligible(const A& a, const Src& src, int s, int64_t so, int64_t ro,
+                                                  int64_t r0, int L, int w, int lane, double (&fe)[VPT]) {
+    uint32_t mask = 0;
+    if (L > 0) {   // block-uniform
+        const int min_level = a.src.sel_level[src.j];
+        if constexpr (Src::FUSED) fused_forecast<VPT>(src, a.nseg, s, so, ro, r0, L, w, lane, fe);
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = row_index<VPT>(w, v, lane), ci = row_clamped(idx, L);
+            double f;
+            if constexpr (Src::FUSED) f = fe[v];
+            else f = a.forecast[ro + ci];
+            const int lv = row_level(a.level, r0 + ci);   // loaded whatever f is, not behind the && below
+            const bool elig = idx < L && isfinite(f) && lv >= min_level;
+            fe[v] = elig ? f : NAN;
+            mask |= elig ? 1u << v : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) fe[v] = NAN;
+    }
+    return mask;
+}
+
+// Phase 2: the 2 nq order statistics of the n rows of mask (their forecasts in fe) that the levels
+// q need, as keys in sh.okey[2 i], sh.okey[2 i + 1] with the interpolation weight in s_g[i]; the
+// caller's thread i < nq makes quantile i of them with qlerp.  nq > 0, block-uniform.
+template <int NT, int VPT, class Sh>
+__device__ __forceinline__ void quantile_keys(const double (&fe)[VPT], uint32_t mask, int n, int nq, const double* q,
+                                              uint64_t* pbuf, Sh& sh, double* s_g) {
+    const int tid = threadIdx.x;
+    if (tid < nq) {
+        int i, j;
+        double g;
+        qranks(n, q[tid], 0, i, j, g);
+        sh.trank[2 * tid] = i;
+        sh.trank[2 * tid + 1] = j;
+        s_g[tid] = g;
+    }
+    if (tid == 0) {
+        sh.n = 0;
+        sh.over = 0;
+    }
+    order_stat_keys<NT, VPT>(fe, mask, n, 2 * nq, pbuf, sh);
+}
+
+// The thread's returns into x, get(row of the month) each, read once (when the registers are free).
+// Returns the bit mask of set R: the rows of em with a finite return.
+template <int VPT, class Get>
+__device__ __forceinline__ uint32_t load_returns(uint32_t em, int L, int w, int lane, Get get, double (&x)[VPT]) {
+    uint32_t rm = 0;
+    if (L <= 0) return rm;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        x[v] = get(row_clamped(row_index<VPT>(w, v, lane), L));
+        rm |= (((em >> v) & 1u) && isfinite(x[v])) ? 1u << v : 0u;
+    }
+    return rm;
+}
+
+// r regressed on g over the n rows of mask: both are centred in place on their means over the
+// mask, then Sgg, Sgr, Srr.  NaN when n < 2 (block-uniform).
+struct RowFit {
+    double slope, icept, r2;
+};
+template <int NW, int VPT>
+__device__ __forceinline__ RowFit fit_rows(uint32_t mask, int n, double (&g)[VPT], double (&r)[VPT], double* s_tile,
+                                           int w, int lane) {
+    if (n < 2) return {NAN, NAN, NAN};
+    const double mg = masked_sum<NW, VPT>(mask, s_tile, w, lane, [&](int v) { return g[v]; }) / (double)n;
+    const double mr = masked_sum<NW, VPT>(mask, s_tile, w, lane, [&](int v) { return r[v]; }) / (double)n;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        g[v] = g[v] - mg;
+        r[v] = r[v] - mr;
+    }
+    const double Sgg = masked_sum<NW, VPT>(mask, s_tile, w, lane, [&](int v) { return g[v] * g[v]; });
+    const double Sgr = masked_sum<NW, VPT>(mask, s_tile, w, lane, [&](int v) { return g[v] * r[v]; });
+    const double Srr = masked_sum<NW, VPT>(mask, s_tile, w, lane, [&](int v) { return r[v] * r[v]; });
+    const double slope = Sgr / Sgg;
+    return {slope, mr - slope * mg, (Sgr * Sgr) / (Sgg * Srr)};
+}
+
+// ---- fm_forecast_dist (extension A14; paper Table 3) -----------------------------------------
+// Per (month, sort): the count, mean, ddof-1 standard deviation and nq quantiles of the eligible
+// forecasts.  Neither return nor weight is read.
 template <int NT, int VPT, class Src>
 __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fdist_kernel(fm_fdist_args a) {
     constexpr int NW = NT / WAVE;
-    constexpr bool FUSED = Src::FUSED;
     const Src src = Src::make(a);
     extern __shared__ uint64_t pbuf[];   // the keys of the order statistics
     __shared__ OrderSh<NW> sh;
@@ -603,30 +724,9 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fdist_kernel(fm_fdist_a
     int L = (int)(a.seg_off[s + 1] - r0);
     L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
     const int64_t so = s + (int64_t)src.j * a.nseg, ro = r0 + (int64_t)src.j * a.src.nrows;
-    const int min_level = a.src.sel_level[src.j];
 
-    // ---- 1. load, eligibility ---------------------------------------------------------------
-    double fe[VPT];     // the eligible rows' forecasts, NaN otherwise
-    uint32_t bpm = 0;   // bit v: row v of this thread is eligible
-    if (L > 0) {        // block-uniform
-        const int last = L - 1;
-        if constexpr (FUSED) fused_forecast<VPT>(src, a.nseg, s, so, ro, r0, L, w, lane, fe);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
-            const int idx = (w * VPT + v) * WAVE + lane;
-            const int ci = idx < L ? idx : last;
-            double f;
-            if constexpr (FUSED) f = fe[v];
-            else f = a.forecast[ro + ci];
-            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
-            const bool elig = idx < L && isfinite(f) && lv >= min_level;
-            fe[v] = elig ? f : NAN;
-            bpm |= elig ? 1u << v : 0u;
-        }
-    } else {
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) fe[v] = NAN;
-    }
+    double fe[VPT];   // the eligible rows' forecasts, NaN otherwise
+    const uint32_t bpm = load_eligible<VPT>(a, src, s, so, ro, r0, L, w, lane, fe);
     const int n = block_sum<NW>((int)__popc(bpm), sh.iscr);
     double* rec = a.rec + so * nrec;
     if (tid == 0) a.cnt[so] = n;
@@ -635,36 +735,16 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fdist_kernel(fm_fdist_a
         if (tid < nrec) rec[tid] = NAN;
         return;
     }
-
-    // ---- 2. the 2 nq order statistics, quantiles ---------------------------------------------
     if (nq > 0) {   // block-uniform
-        if (tid < nq) {
-            int i, j;
-            double g;
-            qranks(n, a.q[tid], 0, i, j, g);
-            sh.trank[2 * tid] = i;
-            sh.trank[2 * tid + 1] = j;
-            s_g[tid] = g;
-        }
-        if (tid == 0) {
-            sh.n = 0;
-            sh.over = 0;
-        }
-        order_stat_keys<NT, VPT>(fe, bpm, n, 2 * nq, pbuf, sh);
+        quantile_keys<NT, VPT>(fe, bpm, n, nq, a.q, pbuf, sh, s_g);
         if (tid < nq) rec[2 + tid] = qlerp(kval(sh.okey[2 * tid]), kval(sh.okey[2 * tid + 1]), s_g[tid], 0);
     }
-
-    // ---- 3. mean, then the squared deviations from it, each in tile_sum's fixed order --------
-    double x[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((bpm >> v) & 1u) ? fe[v] : 0.0;
-    const double mean = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)n;
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
+    // the mean, then the squared deviations from it
+    const double mean = masked_sum<NW, VPT>(bpm, s_tile, w, lane, [&](int v) { return fe[v]; }) / (double)n;
+    const double ss = masked_sum<NW, VPT>(bpm, s_tile, w, lane, [&](int v) {
         const double d = fe[v] - mean;
-        x[v] = ((bpm >> v) & 1u) ? d * d : 0.0;
-    }
-    const double ss = tile_sum<NW, VPT>(x, s_tile, w, lane);
+        return d * d;
+    });
     if (tid == 0) {
         rec[0] = mean;
         rec[1] = n > 1 ? sqrt(ss / (double)(n - 1)) : NAN;
@@ -682,13 +762,13 @@ int launch_fdist(const fm_fdist_args& a, size_t lds, hipStream_t st) {
 
 // ---- fm_forecast_compare (extension A15; paper Table 4) --------------------------------------
 // Per (month, pair): forecast b regressed on forecast a over the rows where both are finite, then
-// the realised return regressed on that regression's residual.  Phase 1 is fdist_kernel's load,
-// twice (fused_forecast for the pair's two sorts, or the caller's two vectors); no order
-// statistics follow, so there are no keys: the month stays in registers and eleven tile_sums
-// (2 + 3 + 3 + 3) reduce it.  The register budget of the 1024 x 16 form (128 VGPRs) holds two row
-// sets of 16 doubles, not three: the deviations replace the forecasts, the residual replaces
-// F_b's deviation, and the return is loaded only then, into the registers F_a's deviation has
-// left.  Each forecast column is read from HBM once per pair, the return once.
+// the realised return regressed on that regression's residual (fit_rows).  Phase 1 loads two
+// forecasts (fused_forecast for the pair's two sorts, or the caller's two vectors), so it keeps its
+// own shape; no order statistics follow, so there are no keys: the month stays in registers and
+// eleven masked_sums (2 + 3 + 1 + 5) reduce it.  The register budget of the 1024 x 16 form (128
+// VGPRs) holds two row sets of 16 doubles, not three: the deviations replace the forecasts, the
+// residual replaces F_b's deviation, and the return is loaded only then, into the registers F_a's
+// deviation has left.  Each forecast column is read from HBM once per pair, the return once.
 
 // The plain source of fm_forecast_compare: the caller's forecast vectors and return vector
 struct CmpVecSrc {
@@ -717,9 +797,9 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fcmp_kernel(fm_fcmp_arg
     const int64_t r0 = a.seg_off[s];
     int L = (int)(a.seg_off[s + 1] - r0);
     L = L < a.max_seg_len ? L : a.max_seg_len;   // the workgroup's form was chosen from max_seg_len
-    const int last = L - 1;
     const int64_t so = s + (int64_t)p * a.nseg;
     double* rec = a.rec + so * FM_FCMP_NREC;
+    auto sum = [&](uint32_t mask, auto term) { return masked_sum<NW, VPT>(mask, s_tile, w, lane, term); };
 
     // ---- 1. the two forecasts, set E ----------------------------------------------------------
     double fa[VPT], fb[VPT];   // F_a, F_b; then their deviations; fb then the residual, fa the return
@@ -730,44 +810,33 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fcmp_kernel(fm_fcmp_arg
             fused_forecast<VPT>(sa, a.nseg, s, s + (int64_t)ja * a.nseg, r0 + (int64_t)ja * a.src.nrows, r0, L, w, lane, fa);
             if constexpr (PARK) {   // each thread parks and fetches its own rows: no barrier
 #pragma unroll
-                for (int v = 0; v < VPT; ++v) s_park[(w * VPT + v) * WAVE + lane] = fa[v];
+                for (int v = 0; v < VPT; ++v) s_park[row_index<VPT>(w, v, lane)] = fa[v];
             }
             fused_forecast<VPT>(sb, a.nseg, s, s + (int64_t)jb * a.nseg, r0 + (int64_t)jb * a.src.nrows, r0, L, w, lane, fb);
             if constexpr (PARK) {
 #pragma unroll
-                for (int v = 0; v < VPT; ++v) fa[v] = s_park[(w * VPT + v) * WAVE + lane];
+                for (int v = 0; v < VPT; ++v) fa[v] = s_park[row_index<VPT>(w, v, lane)];
             }
         }
 #pragma unroll
-        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
-            const int idx = (w * VPT + v) * WAVE + lane;
-            const int ci = idx < L ? idx : last;
+        for (int v = 0; v < VPT; ++v) {
+            const int idx = row_index<VPT>(w, v, lane), ci = row_clamped(idx, L);
             if constexpr (!FUSED) {
                 fa[v] = a.forecast[(int64_t)ja * a.src.nrows + r0 + ci];
                 fb[v] = a.forecast[(int64_t)jb * a.src.nrows + r0 + ci];
             }
-            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
+            const int lv = row_level(a.level, r0 + ci);
             em |= (idx < L && isfinite(fa[v]) && isfinite(fb[v]) && lv >= min_level) ? 1u << v : 0u;
         }
     }
     const int nE = block_sum<NW>((int)__popc(em), s_iscr);
     const int need = a.min_count > 2 ? a.min_count : 2;
-
-    // the thread's returns (into x) and its rows of set R, read once, when the registers are free
-    uint32_t rm = 0;   // bit v: row v of this thread is in R
-    auto load_returns = [&](double (&x)[VPT]) {
-        if (L <= 0) return;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            const int idx = (w * VPT + v) * WAVE + lane;
-            const int ci = idx < L ? idx : last;
-            if constexpr (FUSED) x[v] = Src{a.src, 0}.value(a.ret_col, r0 + ci);   // the same layout view
-            else x[v] = a.ret[r0 + ci];
-            rm |= (((em >> v) & 1u) && isfinite(x[v])) ? 1u << v : 0u;
-        }
+    auto ret_of = [&](int ci) {
+        if constexpr (FUSED) return Src{a.src, 0}.value(a.ret_col, r0 + ci);   // the same layout view
+        else return a.ret[r0 + ci];
     };
     if (nE < need) {   // block-uniform: the month has no regression
-        load_returns(fa);
+        const uint32_t rm = load_returns<VPT>(em, L, w, lane, ret_of, fa);
         const int nR = block_sum<NW>((int)__popc(rm), s_iscr);
         if (tid == 0) {
             a.cnt[so * 2] = nE;
@@ -779,71 +848,33 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fcmp_kernel(fm_fcmp_arg
     }
 
     // ---- 2. b on a over E: means, centered moments, the residual's own sum ---------------------
-    double x[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fa[v] : 0.0;
-    const double ma = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fb[v] : 0.0;
-    const double mb = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
+    const double ma = sum(em, [&](int v) { return fa[v]; }) / (double)nE;
+    const double mb = sum(em, [&](int v) { return fb[v]; }) / (double)nE;
 #pragma unroll
     for (int v = 0; v < VPT; ++v) {
         fa[v] = fa[v] - ma;   // da
         fb[v] = fb[v] - mb;   // db
     }
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fa[v] * fa[v] : 0.0;
-    const double Saa = tile_sum<NW, VPT>(x, s_tile, w, lane);
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fb[v] * fb[v] : 0.0;
-    const double Sbb = tile_sum<NW, VPT>(x, s_tile, w, lane);
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fa[v] * fb[v] : 0.0;
-    const double Sab = tile_sum<NW, VPT>(x, s_tile, w, lane);
+    const double Saa = sum(em, [&](int v) { return fa[v] * fa[v]; });
+    const double Sbb = sum(em, [&](int v) { return fb[v] * fb[v]; });
+    const double Sab = sum(em, [&](int v) { return fa[v] * fb[v]; });
     const double beta = Sab / Saa;
 #pragma unroll
     for (int v = 0; v < VPT; ++v) fb[v] = fb[v] - beta * fa[v];   // e
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fb[v] * fb[v] : 0.0;
-    const double See0 = tile_sum<NW, VPT>(x, s_tile, w, lane);
+    const double See0 = sum(em, [&](int v) { return fb[v] * fb[v]; });
 
-    // ---- 3. the return on the residual over R ---------------------------------------------------
-    load_returns(fa);   // r
+    // ---- 3. the return (into F_a's registers) on the residual over R ---------------------------
+    const uint32_t rm = load_returns<VPT>(em, L, w, lane, ret_of, fa);
     const int nR = block_sum<NW>((int)__popc(rm), s_iscr);
-    double pslope = NAN, picept = NAN, pr2 = NAN;
-    if (nR >= 2) {   // block-uniform
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fb[v] : 0.0;
-        const double me = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fa[v] : 0.0;
-        const double mr = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            fb[v] = fb[v] - me;
-            fa[v] = fa[v] - mr;
-        }
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fb[v] * fb[v] : 0.0;
-        const double See = tile_sum<NW, VPT>(x, s_tile, w, lane);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fb[v] * fa[v] : 0.0;
-        const double Ser = tile_sum<NW, VPT>(x, s_tile, w, lane);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fa[v] * fa[v] : 0.0;
-        const double Srr = tile_sum<NW, VPT>(x, s_tile, w, lane);
-        pslope = Ser / See;
-        picept = mr - pslope * me;
-        pr2 = (Ser * Ser) / (See * Srr);
-    }
+    const RowFit fit = fit_rows<NW, VPT>(rm, nR, fb, fa, s_tile, w, lane);
     if (tid == 0) {
         rec[0] = Sab / sqrt(Saa * Sbb);
         rec[1] = beta;
         rec[2] = mb - beta * ma;
         rec[3] = sqrt(See0 / (double)(nE - 1));
-        rec[4] = pslope;
-        rec[5] = picept;
-        rec[6] = pr2;
+        rec[4] = fit.slope;
+        rec[5] = fit.icept;
+        rec[6] = fit.r2;
         a.cnt[so * 2] = nE;
         a.cnt[so * 2 + 1] = nR;
         a.status[so] = 1u;
@@ -862,11 +893,11 @@ int launch_fcmp(const fm_fcmp_args& a, hipStream_t st) {
 // ---- fm_forecast_horizon (extension A17; the paper's Section 4, second approach) --------------
 // Per (month, sort): the monthly forecast F scaled to G = a m + g (F - m) around the month's mean
 // m, G's mean, standard deviation and quantiles, and the realised long-horizon return regressed on
-// G.  Phases 1-2 are fdist_kernel's (the same loads, fused_forecast, order_stat_keys on F: G is
-// non-decreasing in F, so F's order statistics mapped to G are G's); the mean comes first, since
-// the mapping needs it.  Then G replaces F in the fe registers, and eight tile_sums in all reduce
-// the month.  The return vector is read last, once, into registers of its own: with fe and the
-// term being summed that is fcmp_kernel's budget of two row sets and a transient third.
+// G (fit_rows).  The order statistics are F's (G is non-decreasing in F, so F's mapped to G are
+// G's); the mean comes first, since the mapping needs it.  Then G replaces F in the fe registers,
+// and eight sums in all reduce the month (three in the body, five in fit_rows).  The return vector
+// is read last, once, into registers of its own: with fe and the term being summed that is
+// fcmp_kernel's budget of two row sets and a transient third.
 
 // G of one forecast: three operations, each rounded on its own
 __device__ __forceinline__ double fhor_scale(double f, double m, double base, double g) {
@@ -877,7 +908,6 @@ __device__ __forceinline__ double fhor_scale(double f, double m, double base, do
 template <int NT, int VPT, class Src>
 __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_args a) {
     constexpr int NW = NT / WAVE;
-    constexpr bool FUSED = Src::FUSED;
     const Src src = Src::make(a);
     extern __shared__ uint64_t pbuf[];   // the keys of the order statistics
     __shared__ OrderSh<NW> sh;
@@ -890,49 +920,18 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_arg
     const int64_t r0 = a.seg_off[s];
     int L = (int)(a.seg_off[s + 1] - r0);
     L = L < a.max_seg_len ? L : a.max_seg_len;   // the LDS was sized from max_seg_len
-    const int last = L - 1;
     const int64_t so = s + (int64_t)src.j * a.nseg, ro = r0 + (int64_t)src.j * a.src.nrows;
-    const int min_level = a.src.sel_level[src.j];
 
     // ---- 1. load, set E -------------------------------------------------------------------------
-    double fe[VPT];    // the rows' forecasts F, NaN outside E; from phase 3 on G, then G - mg
-    uint32_t em = 0;   // bit v: row v of this thread is in E
-    if (L > 0) {       // block-uniform
-        if constexpr (FUSED) fused_forecast<VPT>(src, a.nseg, s, so, ro, r0, L, w, lane, fe);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {   // unconditional (clamped) loads, masked after
-            const int idx = (w * VPT + v) * WAVE + lane;
-            const int ci = idx < L ? idx : last;
-            double f;
-            if constexpr (FUSED) f = fe[v];
-            else f = a.forecast[ro + ci];
-            const int lv = a.level != nullptr ? (int)a.level[r0 + ci] : 255;
-            const bool elig = idx < L && isfinite(f) && lv >= min_level;
-            fe[v] = elig ? f : NAN;
-            em |= elig ? 1u << v : 0u;
-        }
-    } else {
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) fe[v] = NAN;
-    }
+    double fe[VPT];   // the rows' forecasts F, NaN outside E; from phase 3 on G, then G - mg
+    const uint32_t em = load_eligible<VPT>(a, src, s, so, ro, r0, L, w, lane, fe);
     const int nE = block_sum<NW>((int)__popc(em), sh.iscr);
     double* rec = a.rec + so * nrec;
     double* gout = a.scaled_out != nullptr ? a.scaled_out + ro : nullptr;
-
-    // the thread's returns (into x) and its rows of set R, read once, when the registers are free
-    uint32_t rm = 0;   // bit v: row v of this thread is in R
-    auto load_returns = [&](double (&x)[VPT]) {
-        if (L <= 0) return;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            const int idx = (w * VPT + v) * WAVE + lane;
-            x[v] = a.ret[r0 + (idx < L ? idx : last)];
-            rm |= (((em >> v) & 1u) && isfinite(x[v])) ? 1u << v : 0u;
-        }
-    };
-    double x[VPT];
+    auto ret_of = [&](int ci) { return a.ret[r0 + ci]; };
     if (nE < a.min_count) {   // block-uniform: the month has no scaled forecast
-        load_returns(x);
+        double x[VPT];
+        const uint32_t rm = load_returns<VPT>(em, L, w, lane, ret_of, x);
         const int nR = block_sum<NW>((int)__popc(rm), sh.iscr);
         if (tid == 0) {
             a.cnt[so * 2] = nE;
@@ -943,7 +942,7 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_arg
         if (gout != nullptr) {
 #pragma unroll
             for (int v = 0; v < VPT; ++v) {
-                const int idx = (w * VPT + v) * WAVE + lane;
+                const int idx = row_index<VPT>(w, v, lane);
                 if (idx < L) gout[idx] = NAN;
             }
         }
@@ -951,24 +950,15 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_arg
     }
 
     // ---- 2. the mean of F, then the quantiles of G from F's order statistics -------------------
+    // masked_sum's text in the body, here and twice in phase 3: through the helper these three sums
+    // cost the launch 0.2-0.5 %
+    double x[VPT];
 #pragma unroll
     for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fe[v] : 0.0;
     const double m = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
     const double g = a.gain, base = a.level_mult * m;
     if (nq > 0) {   // block-uniform
-        if (tid < nq) {
-            int i, j;
-            double gam;
-            qranks(nE, a.q[tid], 0, i, j, gam);
-            sh.trank[2 * tid] = i;
-            sh.trank[2 * tid + 1] = j;
-            s_g[tid] = gam;
-        }
-        if (tid == 0) {
-            sh.n = 0;
-            sh.over = 0;
-        }
-        order_stat_keys<NT, VPT>(fe, em, nE, 2 * nq, pbuf, sh);
+        quantile_keys<NT, VPT>(fe, em, nE, nq, a.q, pbuf, sh, s_g);
         if (tid < nq)
             rec[FM_FHOR_NREC + tid] = qlerp(fhor_scale(kval(sh.okey[2 * tid]), m, base, g),
                                             fhor_scale(kval(sh.okey[2 * tid + 1]), m, base, g), s_g[tid], 0);
@@ -978,9 +968,10 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_arg
 #pragma unroll
     for (int v = 0; v < VPT; ++v) {
         fe[v] = ((em >> v) & 1u) ? fhor_scale(fe[v], m, base, g) : NAN;
-        const int idx = (w * VPT + v) * WAVE + lane;
+        const int idx = row_index<VPT>(w, v, lane);
         if (gout != nullptr && idx < L) gout[idx] = fe[v];
     }
+    // (the two sums below keep their own text, not masked_sum: see phase 2)
 #pragma unroll
     for (int v = 0; v < VPT; ++v) x[v] = ((em >> v) & 1u) ? fe[v] : 0.0;
     const double mG = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nE;
@@ -993,40 +984,15 @@ __global__ __launch_bounds__(NT, NT >= 512 ? 4 : 2) void fhor_kernel(fm_fhor_arg
 
     // ---- 4. the return on G over R ----------------------------------------------------------------
     double r[VPT];
-    load_returns(r);
+    const uint32_t rm = load_returns<VPT>(em, L, w, lane, ret_of, r);
     const int nR = block_sum<NW>((int)__popc(rm), sh.iscr);
-    double pslope = NAN, picept = NAN, pr2 = NAN;
-    if (nR >= 2) {   // block-uniform
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fe[v] : 0.0;
-        const double mg = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? r[v] : 0.0;
-        const double mr = tile_sum<NW, VPT>(x, s_tile, w, lane) / (double)nR;
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            fe[v] = fe[v] - mg;
-            r[v] = r[v] - mr;
-        }
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fe[v] * fe[v] : 0.0;
-        const double Sgg = tile_sum<NW, VPT>(x, s_tile, w, lane);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? fe[v] * r[v] : 0.0;
-        const double Sgr = tile_sum<NW, VPT>(x, s_tile, w, lane);
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) x[v] = ((rm >> v) & 1u) ? r[v] * r[v] : 0.0;
-        const double Srr = tile_sum<NW, VPT>(x, s_tile, w, lane);
-        pslope = Sgr / Sgg;
-        picept = mr - pslope * mg;
-        pr2 = (Sgr * Sgr) / (Sgg * Srr);
-    }
+    const RowFit fit = fit_rows<NW, VPT>(rm, nR, fe, r, s_tile, w, lane);
     if (tid == 0) {
         rec[0] = mG;
         rec[1] = nE > 1 ? sqrt(ss / (double)(nE - 1)) : NAN;
-        rec[2] = pslope;
-        rec[3] = picept;
-        rec[4] = pr2;
+        rec[2] = fit.slope;
+        rec[3] = fit.icept;
+        rec[4] = fit.r2;
         rec[5] = m;
         a.cnt[so * 2] = nE;
         a.cnt[so * 2 + 1] = nR;
@@ -1086,17 +1052,8 @@ extern "C" int fm_forecast_dist(const fm_fdist_args* args, void* stream) {
     const char* who = "fm_forecast_dist";
     FM_REQUIRE(args != nullptr, "%s: null args", who);
     const fm_fdist_args& a = *args;
-    FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
-    FM_REQUIRE(a.nq >= 0 && a.nq <= FM_MAX_DIST_Q, "%s: nq must be 0..%d", who, FM_MAX_DIST_Q);
-    for (int i = 0; i < a.nq; ++i) {
-        const double lo = i == 0 ? 0.0 : a.q[i - 1];
-        FM_REQUIRE(a.q[i] > lo && a.q[i] < 1.0, "%s: q must be strictly ascending in (0, 1)", who);
-    }
-    FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
-    if (a.max_seg_len > PORT_MAX_ROWS) {
-        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
-        return FM_ETOOBIG;
-    }
+    if (const int rc = check_dist_args(a.nq, a.q, a.min_count, a.max_seg_len, who)) return rc;
+    if (const int rc = check_max_rows(a.max_seg_len, who)) return rc;
     const bool vec = a.forecast != nullptr;
     if (const int rc = check_forecast_src(a.src, a.nseg, who, vec)) return rc;
     if (a.nseg == 0 || a.src.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
@@ -1115,19 +1072,10 @@ extern "C" int fm_forecast_horizon(const fm_fhor_args* args, void* stream) {
     const char* who = "fm_forecast_horizon";
     FM_REQUIRE(args != nullptr, "%s: null args", who);
     const fm_fhor_args& a = *args;
-    FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
-    FM_REQUIRE(a.nq >= 0 && a.nq <= FM_MAX_DIST_Q, "%s: nq must be 0..%d", who, FM_MAX_DIST_Q);
-    for (int i = 0; i < a.nq; ++i) {
-        const double lo = i == 0 ? 0.0 : a.q[i - 1];
-        FM_REQUIRE(a.q[i] > lo && a.q[i] < 1.0, "%s: q must be strictly ascending in (0, 1)", who);
-    }
-    FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
+    if (const int rc = check_dist_args(a.nq, a.q, a.min_count, a.max_seg_len, who)) return rc;
     FM_REQUIRE(isfinite(a.gain) && a.gain > 0.0, "%s: gain must be finite and > 0", who);
     FM_REQUIRE(isfinite(a.level_mult), "%s: level_mult must be finite", who);
-    if (a.max_seg_len > PORT_MAX_ROWS) {
-        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
-        return FM_ETOOBIG;
-    }
+    if (const int rc = check_max_rows(a.max_seg_len, who)) return rc;
     const bool vec = a.forecast != nullptr;
     if (const int rc = check_forecast_src(a.src, a.nseg, who, vec)) return rc;
     if (a.nseg == 0 || a.src.nsel == 0) return FM_OK;   // nothing is read: an empty call has no pointers
@@ -1150,10 +1098,7 @@ extern "C" int fm_forecast_compare(const fm_fcmp_args* args, void* stream) {
     FM_REQUIRE(a.max_seg_len >= 0, "%s: bad sizes", who);
     FM_REQUIRE(a.npair >= 0 && a.npair <= FM_MAX_PAIRS, "%s: npair must be 0..%d", who, FM_MAX_PAIRS);
     FM_REQUIRE(a.min_count >= 1, "%s: min_count must be >= 1", who);
-    if (a.max_seg_len > PORT_MAX_ROWS) {
-        set_error("%s: %d-row months exceed %d", who, a.max_seg_len, PORT_MAX_ROWS);
-        return FM_ETOOBIG;
-    }
+    if (const int rc = check_max_rows(a.max_seg_len, who)) return rc;
     const bool vec = a.forecast != nullptr;
     if (const int rc = check_forecast_src(a.src, a.nseg, who, vec)) return rc;
     for (int p = 0; p < a.npair; ++p) {

@@ -1075,7 +1075,7 @@ def wls_weight(panel: DevicePanel, weight):
         if weight not in panel.names:
             raise ValueError(f"fm_pass_wls: the panel has no column {weight!r} to weight by")
         return column_vector(panel, weight)
-    return _row_vector(weight, torch.float64, panel.nrows, panel.device, "weight")
+    return _row_vector("fm_pass_wls", weight, torch.float64, panel.nrows, panel.device, "weight")
 
 
 def _wls_tables(panel, models, problems, dev):
@@ -1379,12 +1379,60 @@ class Portfolios:
     # forecast_portfolio_sort returns every tensor with a leading [nsel] dimension
 
 
-def _row_vector(t, dtype, n, dev, what):
-    if t is None:
+def _row_vector(who, t, dtype, n, dev, what, required=False):
+    """Argument ``what`` of ``who``, a ``dtype`` [n] tensor on ``dev`` (``n`` a tuple: of that shape),
+    made contiguous; None passes through unless ``required``."""
+    if t is None and not required:
         return None
-    if t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or t.device != dev:
-        raise ValueError(f"portfolio_sort: {what} must be a {dtype} [{n}] tensor on {dev}")
+    sh = tuple(n) if isinstance(n, tuple) else (n,)
+    if t is None or t.dtype != dtype or tuple(t.shape) != sh or t.device != dev:
+        raise ValueError(f"{who}: {what} must be a {dtype} {list(sh)} tensor on {dev}")
     return t.contiguous()
+
+
+def _months(who, seg_off, dev, what):
+    """The month offsets every row-vector entry point takes -> (seg_off contiguous, T); ``what``: whose
+    device ``dev`` is, for the message ("forecast's", "returns'", ...)."""
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
+        raise ValueError(f"{who}: seg_off must be an int64 [T+1] tensor on the {what} device")
+    return seg_off.contiguous(), int(seg_off.shape[0]) - 1
+
+
+def _longest_month(seg_off, T, max_seg_len):
+    """``max_seg_len`` if the caller knows it, else read from ``seg_off`` (one host sync)."""
+    if max_seg_len is not None:
+        return int(max_seg_len)
+    return int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+
+
+def _outputs(who, cls, shapes, out, dev):
+    """The result dataclass ``cls`` of ``who`` with the tensors ``shapes`` = {field: (shape, dtype)}:
+    allocated on ``dev``, or the caller's ``out`` checked tensor by tensor."""
+    if out is None:
+        return cls(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    for k, (sh, dt) in shapes.items():
+        t = getattr(out, k)
+        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+    return out
+
+
+def _new_or_filled(empty, shape, dtype, fill, dev):
+    """An output a launch will write; an ``empty`` call launches nothing, so its outputs are then
+    filled with what a launch would have written."""
+    if empty:
+        return torch.full(shape, fill, dtype=dtype, device=dev)
+    return torch.empty(shape, dtype=dtype, device=dev)
+
+
+def _rec_summary(rec, status, nw_lags):
+    """FM mean, Newey-West s.e., t and nobs of the monthly series of ``rec`` [S, T, ...] over the months
+    with ``status`` [S, T] 1, NaN entries dropped per series: every leading index is one problem of
+    two launches -> ``Summary`` with [S, k] tensors, k the series per problem."""
+    S, T = int(rec.shape[0]), int(rec.shape[1])
+    k = int(np.prod(rec.shape[2:], dtype=np.int64))
+    ix = ts_compact(status, 1, T, T, S)
+    return ts_summary(rec, k, T * k, ix, T, S, k, nw_lags)
 
 
 def _sort_plan(who, lead, T, n, nport, q, nyse_breakpoints, min_count):
@@ -1419,22 +1467,19 @@ def portfolio_sort(seg_off, forecast, ret, weight=None, level=None, nyse=None, n
     month if the caller knows it (otherwise read from ``seg_off``, one host sync)."""
     dev = forecast.device
     n = int(forecast.shape[0])
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("portfolio_sort: seg_off must be an int64 [T+1] tensor on the forecast's device")
-    seg_off = seg_off.contiguous()
-    T = int(seg_off.shape[0]) - 1
-    forecast = _row_vector(forecast, torch.float64, n, dev, "forecast")
-    ret = _row_vector(ret, torch.float64, n, dev, "ret")
-    weight = _row_vector(weight, torch.float64, n, dev, "weight")
-    level = _row_vector(level, torch.uint8, n, dev, "level")
-    nyse = _row_vector(nyse, torch.uint8, n, dev, "nyse")
-    fill, shapes = _sort_plan("portfolio_sort", (), T, n, int(nport), q, nyse_breakpoints, min_count)
-    if max_seg_len is None:
-        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    who = "portfolio_sort"
+    seg_off, T = _months(who, seg_off, dev, "forecast's")
+    forecast = _row_vector(who, forecast, torch.float64, n, dev, "forecast")
+    ret = _row_vector(who, ret, torch.float64, n, dev, "ret")
+    weight = _row_vector(who, weight, torch.float64, n, dev, "weight")
+    level = _row_vector(who, level, torch.uint8, n, dev, "level")
+    nyse = _row_vector(who, nyse, torch.uint8, n, dev, "nyse")
+    fill, shapes = _sort_plan(who, (), T, n, int(nport), q, nyse_breakpoints, min_count)
+    max_seg_len = _longest_month(seg_off, T, max_seg_len)
     a = fill(L.PortArgs())
     a.forecast, a.ret, a.weight, a.level, a.nyse = _ptr(forecast), _ptr(ret), _ptr(weight), _ptr(level), _ptr(nyse)
-    a.seg_off, a.nseg, a.max_seg_len, a.min_level = seg_off.data_ptr(), T, int(max_seg_len), int(min_level)
-    out = Portfolios(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
+    a.seg_off, a.nseg, a.max_seg_len, a.min_level = seg_off.data_ptr(), T, max_seg_len, int(min_level)
+    out = _outputs(who, Portfolios, shapes, None, dev)
     for k in shapes:
         setattr(a, k, getattr(out, k).data_ptr())
     _kcall("fm_portfolio_sort", "fm_portfolio_sort", L.C.byref(a), _stream())
@@ -1519,21 +1564,17 @@ def forecast_portfolio_sort(panel: DevicePanel, coef, sel, cuts: Cuts = None, re
     definition is in fm_hip.h).  One launch per FM_MAX_SORTS sorts.  Returns ``Portfolios`` whose
     tensors carry a leading [nsel] dimension; ``forecast_out``: also the forecasts [nsel, rows];
     ``out``: a ``Portfolios`` of that shape to write into (else allocated)."""
-    src, sel, coef, lo, hi = _forecast_plan("forecast_portfolio_sort", panel, coef, sel, cuts)
+    who = "forecast_portfolio_sort"
+    src, sel, coef, lo, hi = _forecast_plan(who, panel, coef, sel, cuts)
     dev = src.device
     n, T, nsel = panel.nrows, panel.nseg, len(sel)
-    weight = _row_vector(weight, torch.float64, n, dev, "weight")
-    level = _row_vector(level, torch.uint8, n, dev, "level")
-    nyse = _row_vector(nyse, torch.uint8, n, dev, "nyse")
-    fill, shapes = _sort_plan("forecast_portfolio_sort", (nsel,), T, n, int(nport), q, nyse_breakpoints, min_count)
+    weight = _row_vector(who, weight, torch.float64, n, dev, "weight")
+    level = _row_vector(who, level, torch.uint8, n, dev, "level")
+    nyse = _row_vector(who, nyse, torch.uint8, n, dev, "nyse")
+    fill, shapes = _sort_plan(who, (nsel,), T, n, int(nport), q, nyse_breakpoints, min_count)
     if forecast_out:
         shapes["forecast"] = ((nsel, n), torch.float64)
-    if out is None:
-        out = Portfolios(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
-    for k, (sh, dt) in shapes.items():
-        t = getattr(out, k)
-        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"forecast_portfolio_sort: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+    out = _outputs(who, Portfolios, shapes, out, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
         a = fill(L.FPortArgs())
         _fill_forecast_src(a.src, n, sel[j0:j0 + L.FM_MAX_SORTS], j0, src, coef, lo, hi,
@@ -1557,8 +1598,7 @@ def portfolio_summary(p: Portfolios, nw_lags=4):
     is one problem of the same two launches, and the tensors are [nsel, nport+1, 4]."""
     if p.rec.dim() == 4:
         S, T, n1, k = p.rec.shape
-        ix = ts_compact(p.status, 1, T, T, S)
-        s = ts_summary(p.rec, n1 * k, T * n1 * k, ix, T, S, n1 * k, nw_lags)
+        s = _rec_summary(p.rec, p.status, nw_lags)
         return Summary(s.mean.view(S, n1, k), s.se.view(S, n1, k), s.tstat.view(S, n1, k), s.nobs.view(S, n1, k))
     T, n1, k = p.rec.shape
     ix = ts_compact(p.status.view(T, 1), 1, 1, T, 1)
@@ -1670,12 +1710,7 @@ def _dist_plan(who, nsel, T, n, q, min_count, forecast_out, out, dev):
                   status=((nsel, T), torch.int32))
     if forecast_out:
         shapes["forecast"] = ((nsel, n), torch.float64)
-    if out is None:
-        out = ForecastDist(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
-    for k, (sh, dt) in shapes.items():
-        t = getattr(out, k)
-        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+    out = _outputs(who, ForecastDist, shapes, out, dev)
 
     def fill(a, j0):
         a.nq, a.min_count, a.nseg = len(qs), int(min_count), T
@@ -1700,7 +1735,7 @@ def forecast_dist(panel: DevicePanel, coef, sel, cuts: Cuts = None, level=None, 
     src, sel, coef, lo, hi = _forecast_plan("forecast_dist", panel, coef, sel, cuts)
     dev = src.device
     n, T, nsel = panel.nrows, panel.nseg, len(sel)
-    level = _row_vector(level, torch.uint8, n, dev, "level")
+    level = _row_vector("forecast_dist", level, torch.uint8, n, dev, "level")
     out, fill = _dist_plan("forecast_dist", nsel, T, n, q, min_count, forecast_out, out, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
         a = fill(L.FDistArgs(), j0)
@@ -1712,34 +1747,40 @@ def forecast_dist(panel: DevicePanel, coef, sel, cuts: Cuts = None, level=None, 
     return out
 
 
+def _forecast_vectors(who, forecast, seg_off, level, min_level, max_seg_len):
+    """What the entry points on the caller's own forecast vectors share: ``forecast`` as a contiguous
+    [nsel, rows] block (a 1-D forecast is one vector), the months, ``level`` checked, ``min_level`` as
+    one level per vector and the longest month -> (forecast, seg_off, T, level, levels, max_seg_len)."""
+    dev = forecast.device
+    if forecast.dtype != torch.float64 or forecast.dim() not in (1, 2):
+        raise ValueError(f"{who}: forecast must be a float64 [rows] or [nsel, rows] tensor")
+    forecast = forecast.view(1, -1) if forecast.dim() == 1 else forecast
+    forecast = forecast.contiguous()
+    nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
+    seg_off, T = _months(who, seg_off, dev, "forecast's")
+    level = _row_vector(who, level, torch.uint8, n, dev, "level")
+    levels = [int(min_level)] * nsel if np.ndim(min_level) == 0 else [int(v) for v in min_level]
+    if len(levels) != nsel:
+        raise ValueError(f"{who}: min_level must be one value or {nsel}")
+    return forecast, seg_off, T, level, levels, _longest_month(seg_off, T, max_seg_len)
+
+
 def forecast_dist_vector(seg_off, forecast, level=None, min_level=0, q=(0.1, 0.9), min_count=1, max_seg_len=None):
     """A14 on forecast vectors the caller holds: ``forecast`` float64 [rows] or [nsel, rows] on the
     device, months ``seg_off`` int64 [T+1]; eligible rows are the finite forecasts with ``level`` >=
     ``min_level`` (one value, or one per vector).  Returns ``ForecastDist`` with a leading [nsel]
     dimension (1 for a 1-D forecast).  ``max_seg_len``: the longest month if the caller knows it
     (otherwise read from ``seg_off``, one host sync)."""
-    dev = forecast.device
-    if forecast.dtype != torch.float64 or forecast.dim() not in (1, 2):
-        raise ValueError("forecast_dist_vector: forecast must be a float64 [rows] or [nsel, rows] tensor")
-    forecast = forecast.view(1, -1) if forecast.dim() == 1 else forecast
-    forecast = forecast.contiguous()
-    nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("forecast_dist_vector: seg_off must be an int64 [T+1] tensor on the forecast's device")
-    seg_off = seg_off.contiguous()
-    T = int(seg_off.shape[0]) - 1
-    level = _row_vector(level, torch.uint8, n, dev, "level")
-    levels = [int(min_level)] * nsel if np.ndim(min_level) == 0 else [int(v) for v in min_level]
-    if len(levels) != nsel:
-        raise ValueError(f"forecast_dist_vector: min_level must be one value or {nsel}")
-    if max_seg_len is None:
-        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
-    out, fill = _dist_plan("forecast_dist_vector", nsel, T, n, q, min_count, False, None, dev)
+    who = "forecast_dist_vector"
+    forecast, seg_off, T, level, levels, max_seg_len = _forecast_vectors(who, forecast, seg_off, level, min_level,
+                                                                         max_seg_len)
+    dev, (nsel, n) = forecast.device, forecast.shape
+    out, fill = _dist_plan(who, nsel, T, n, q, min_count, False, None, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
         a = fill(L.FDistArgs(), j0)
         _fill_forecast_src(a.src, n, [((), lv) for lv in levels[j0:j0 + L.FM_MAX_SORTS]])
         a.forecast = forecast[j0:].data_ptr() if nsel else None
-        a.level, a.seg_off, a.max_seg_len = _ptr(level), seg_off.data_ptr(), int(max_seg_len)
+        a.level, a.seg_off, a.max_seg_len = _ptr(level), seg_off.data_ptr(), max_seg_len
         _kcall("fm_forecast_dist", "fm_forecast_dist", L.C.byref(a), _stream())
         _remember("fm_forecast_dist", "fm_forecast_dist", a, seg_off, forecast, level, out)
     return out
@@ -1750,9 +1791,7 @@ def forecast_dist_summary(d: ForecastDist, nw_lags=4):
     months with status 1, NaN entries dropped per series (the sd of a one-row month) ->
     ``Summary`` with [nsel, 2+nq] tensors: every sort is one problem of the two launches
     ``portfolio_summary`` issues."""
-    S, T, k = d.rec.shape
-    ix = ts_compact(d.status, 1, T, T, S)
-    return ts_summary(d.rec, k, T * k, ix, T, S, k, nw_lags)
+    return _rec_summary(d.rec, d.status, nw_lags)
 
 
 @dataclass
@@ -1790,12 +1829,7 @@ def _compare_plan(who, npair, T, nsel, n, forecast_out, out, dev):
                   status=((npair, T), torch.int32))
     if forecast_out:
         shapes["forecast"] = ((nsel, n), torch.float64)
-    if out is None:
-        out = ForecastCompare(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
-    for k, (sh, dt) in shapes.items():
-        t = getattr(out, k)
-        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+    out = _outputs(who, ForecastCompare, shapes, out, dev)
 
     def fill(a, p0, part):
         a.npair, a.nseg = len(part), T
@@ -1832,7 +1866,7 @@ def forecast_compare(panel: DevicePanel, coef, sel, pairs, cuts: Cuts = None, re
     dev = src.device
     n, T, nsel = panel.nrows, panel.nseg, len(sel)
     pairs, batches = _pair_batches("forecast_compare", pairs, nsel)
-    level = _row_vector(level, torch.uint8, n, dev, "level")
+    level = _row_vector("forecast_compare", level, torch.uint8, n, dev, "level")
     out, fill = _compare_plan("forecast_compare", len(pairs), T, nsel, n, forecast_out, out, dev)
     if forecast_out:
         unused = sorted(set(range(nsel)) - {j for a, b, _ in pairs for j in (a, b)})
@@ -1864,22 +1898,18 @@ def forecast_compare_vector(seg_off, forecast, ret, pairs, level=None, min_count
         raise ValueError("forecast_compare_vector: forecast must be a float64 [nsel, rows] tensor")
     forecast = forecast.contiguous()
     nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("forecast_compare_vector: seg_off must be an int64 [T+1] tensor on the forecast's device")
-    seg_off = seg_off.contiguous()
-    T = int(seg_off.shape[0]) - 1
-    ret = _row_vector(ret, torch.float64, n, dev, "ret")
-    level = _row_vector(level, torch.uint8, n, dev, "level")
+    seg_off, T = _months("forecast_compare_vector", seg_off, dev, "forecast's")
+    ret = _row_vector("forecast_compare_vector", ret, torch.float64, n, dev, "ret")
+    level = _row_vector("forecast_compare_vector", level, torch.uint8, n, dev, "level")
     pairs, batches = _pair_batches("forecast_compare_vector", pairs, nsel)
-    if max_seg_len is None:
-        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    max_seg_len = _longest_month(seg_off, T, max_seg_len)
     out, fill = _compare_plan("forecast_compare_vector", len(pairs), T, nsel, n, False, None, dev)
     for p0, part, js in batches:
         a = fill(L.FCmpArgs(), p0, part)
         fj = _rows_of(forecast, js)
         _fill_forecast_src(a.src, n, [((), 0)] * len(js))
         a.forecast, a.ret = fj.data_ptr() if js else None, _ptr(ret)
-        a.level, a.seg_off, a.max_seg_len, a.min_count = _ptr(level), seg_off.data_ptr(), int(max_seg_len), int(min_count)
+        a.level, a.seg_off, a.max_seg_len, a.min_count = _ptr(level), seg_off.data_ptr(), max_seg_len, int(min_count)
         _kcall("fm_forecast_compare", "fm_forecast_compare", L.C.byref(a), _stream())
         _remember("fm_forecast_compare", "fm_forecast_compare", a, seg_off, fj, ret, level, out)
     return out
@@ -1890,9 +1920,7 @@ def forecast_compare_summary(c: ForecastCompare, nw_lags=4):
     status 1, NaN entries dropped per series (a constant forecast, a zero residual, a month without
     returns) -> ``Summary`` with [npair, 7] tensors: every pair is one problem of the two launches
     ``forecast_dist_summary`` issues."""
-    S, T, k = c.rec.shape
-    ix = ts_compact(c.status, 1, T, T, S)
-    return ts_summary(c.rec, k, T * k, ix, T, S, k, nw_lags)
+    return _rec_summary(c.rec, c.status, nw_lags)
 
 
 @dataclass
@@ -1928,12 +1956,7 @@ def _horizon_plan(who, nsel, T, n, q, min_count, level_mult, gain, scaled_out, f
         shapes["scaled"] = ((nsel, n), torch.float64)
     if forecast_out:
         shapes["forecast"] = ((nsel, n), torch.float64)
-    if out is None:
-        out = ForecastHorizon(**{k: torch.empty(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()})
-    for k, (sh, dt) in shapes.items():
-        t = getattr(out, k)
-        if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"{who}: out.{k} must be a contiguous {dt} {list(sh)} tensor on {dev}")
+    out = _outputs(who, ForecastHorizon, shapes, out, dev)
 
     def fill(a, j0):
         a.nq, a.min_count, a.nseg = len(qs), int(min_count), T
@@ -1964,8 +1987,8 @@ def forecast_horizon(panel: DevicePanel, coef, sel, ret, level_mult, gain, cuts:
     src, sel, coef, lo, hi = _forecast_plan("forecast_horizon", panel, coef, sel, cuts)
     dev = src.device
     n, T, nsel = panel.nrows, panel.nseg, len(sel)
-    ret = _row_vector(ret, torch.float64, n, dev, "ret")
-    level = _row_vector(level, torch.uint8, n, dev, "level")
+    ret = _row_vector("forecast_horizon", ret, torch.float64, n, dev, "ret")
+    level = _row_vector("forecast_horizon", level, torch.uint8, n, dev, "level")
     out, fill = _horizon_plan("forecast_horizon", nsel, T, n, q, min_count, level_mult, gain, scaled_out,
                               forecast_out, out, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
@@ -1986,30 +2009,17 @@ def forecast_horizon_vector(seg_off, forecast, ret, level_mult, gain, level=None
     are the finite forecasts with ``level`` >= ``min_level`` (one value, or one per vector).  Returns
     ``ForecastHorizon`` with a leading [nsel] dimension (1 for a 1-D forecast).  ``max_seg_len``: the
     longest month if the caller knows it (otherwise read from ``seg_off``, one host sync)."""
-    dev = forecast.device
-    if forecast.dtype != torch.float64 or forecast.dim() not in (1, 2):
-        raise ValueError("forecast_horizon_vector: forecast must be a float64 [rows] or [nsel, rows] tensor")
-    forecast = forecast.view(1, -1) if forecast.dim() == 1 else forecast
-    forecast = forecast.contiguous()
-    nsel, n = int(forecast.shape[0]), int(forecast.shape[1])
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("forecast_horizon_vector: seg_off must be an int64 [T+1] tensor on the forecast's device")
-    seg_off = seg_off.contiguous()
-    T = int(seg_off.shape[0]) - 1
-    ret = _row_vector(ret, torch.float64, n, dev, "ret")
-    level = _row_vector(level, torch.uint8, n, dev, "level")
-    levels = [int(min_level)] * nsel if np.ndim(min_level) == 0 else [int(v) for v in min_level]
-    if len(levels) != nsel:
-        raise ValueError(f"forecast_horizon_vector: min_level must be one value or {nsel}")
-    if max_seg_len is None:
-        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
-    out, fill = _horizon_plan("forecast_horizon_vector", nsel, T, n, q, min_count, level_mult, gain, scaled_out,
-                              False, None, dev)
+    who = "forecast_horizon_vector"
+    forecast, seg_off, T, level, levels, max_seg_len = _forecast_vectors(who, forecast, seg_off, level, min_level,
+                                                                         max_seg_len)
+    dev, (nsel, n) = forecast.device, forecast.shape
+    ret = _row_vector(who, ret, torch.float64, n, dev, "ret")
+    out, fill = _horizon_plan(who, nsel, T, n, q, min_count, level_mult, gain, scaled_out, False, None, dev)
     for j0 in range(0, max(nsel, 1), L.FM_MAX_SORTS):
         a = fill(L.FHorArgs(), j0)
         _fill_forecast_src(a.src, n, [((), lv) for lv in levels[j0:j0 + L.FM_MAX_SORTS]])
         a.forecast = forecast[j0:].data_ptr() if nsel else None
-        a.ret, a.level, a.seg_off, a.max_seg_len = _ptr(ret), _ptr(level), seg_off.data_ptr(), int(max_seg_len)
+        a.ret, a.level, a.seg_off, a.max_seg_len = _ptr(ret), _ptr(level), seg_off.data_ptr(), max_seg_len
         _kcall("fm_forecast_horizon", "fm_forecast_horizon", L.C.byref(a), _stream())
         _remember("fm_forecast_horizon", "fm_forecast_horizon", a, seg_off, forecast, ret, level, out)
     return out
@@ -2020,9 +2030,7 @@ def forecast_horizon_summary(h: ForecastHorizon, nw_lags=4):
     with status 1, NaN entries dropped per series (a constant forecast, a month without k-month
     returns, the sd of a one-row month) -> ``Summary`` with [nsel, 6+nq] tensors: every sort is one
     problem of the two launches ``forecast_compare_summary`` issues."""
-    S, T, k = h.rec.shape
-    ix = ts_compact(h.status, 1, T, T, S)
-    return ts_summary(h.rec, k, T * k, ix, T, S, k, nw_lags)
+    return _rec_summary(h.rec, h.status, nw_lags)
 
 
 # fm_rank_transform's month limit (FM_RANK_MAX_ROWS): up to 16,384 rows one workgroup per (month,
@@ -2149,19 +2157,15 @@ def horizon_return(seg_off, ret, link, horizon, out=None):
     int32 [rows]; returns (or fills ``out``) float64 [rows]."""
     n = int(ret.shape[0])
     dev = ret.device
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("horizon_return: seg_off must be an int64 [T+1] tensor on the returns' device")
-    seg_off = seg_off.contiguous()
-    for t, dt, what in ((ret, torch.float64, "ret"), (link, torch.int32, "link")):
-        if t.dtype != dt or t.dim() != 1 or t.shape[0] != n or t.device != dev:
-            raise ValueError(f"horizon_return: {what} must be a {dt} [{n}] tensor on {dev}")
-    ret, link = ret.contiguous(), link.contiguous()
+    seg_off, T = _months("horizon_return", seg_off, dev, "returns'")
+    ret = _row_vector("horizon_return", ret, torch.float64, n, dev, "ret", required=True)
+    link = _row_vector("horizon_return", link, torch.int32, n, dev, "link", required=True)
     if out is None:
         out = torch.empty(n, dtype=torch.float64, device=dev)
     elif out.dtype != torch.float64 or out.shape != (n,) or out.device != dev or not out.is_contiguous():
         raise ValueError(f"horizon_return: out must be a contiguous float64 [{n}] tensor on {dev}")
     a = L.HorizonArgs(ret=ret.data_ptr(), link=link.data_ptr(), seg_off=seg_off.data_ptr(), nrows=n,
-                      nseg=int(seg_off.shape[0]) - 1, horizon=int(horizon), out=out.data_ptr())
+                      nseg=T, horizon=int(horizon), out=out.data_ptr())
     _kcall("fm_horizon_return", "fm_horizon_return", L.C.byref(a), _stream())
     _remember("fm_horizon_return", "fm_horizon_return", a, ret, link, seg_off, out)
     return out
@@ -2243,10 +2247,8 @@ def portfolio_hold(seg_off, month_index, link_prev, port, status, ret, weight=No
     (for the predicted columns; None: they are NaN).  One launch, no host sync."""
     dev = ret.device
     n = int(ret.shape[0])
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("portfolio_hold: seg_off must be an int64 [T+1] tensor on the returns' device")
-    seg_off = seg_off.contiguous()
-    T = int(seg_off.shape[0]) - 1
+    who = "portfolio_hold"
+    seg_off, T = _months(who, seg_off, dev, "returns'")
     nport, hold = int(nport), int(hold)
     if not 2 <= nport <= L.FM_MAX_PORTS:
         raise ValueError(f"portfolio_hold: nport must be 2..{L.FM_MAX_PORTS}, got {nport}")
@@ -2257,29 +2259,22 @@ def portfolio_hold(seg_off, month_index, link_prev, port, status, ret, weight=No
     lead = (S,) if batched else ()
     if S > L.FM_MAX_SORTS:
         raise ValueError(f"portfolio_hold: at most {L.FM_MAX_SORTS} sorts per call, got {S}")
-    for t, dt, sh, what in ((month_index, torch.int32, (T,), "month_index"), (link_prev, torch.int32, (n,), "link_prev"),
-                            (port, torch.uint8, lead + (n,), "port"), (status, torch.int32, lead + (T,), "status"),
-                            (ret, torch.float64, (n,), "ret"), (weight, torch.float64, (n,), "weight"),
-                            (sort_rec, torch.float64, lead + (T, nport + 1, 4), "sort_rec")):
-        if t is None and what in ("weight", "sort_rec"):
-            continue
-        if t is None or t.dtype != dt or tuple(t.shape) != sh or t.device != dev:
-            raise ValueError(f"portfolio_hold: {what} must be a {dt} {list(sh)} tensor on {dev}")
-    month_index, link_prev, port, status, ret = (t.contiguous() for t in (month_index, link_prev, port, status, ret))
-    weight = None if weight is None else weight.contiguous()
-    sort_rec = None if sort_rec is None else sort_rec.contiguous()
+    month_index = _row_vector(who, month_index, torch.int32, T, dev, "month_index", required=True)
+    link_prev = _row_vector(who, link_prev, torch.int32, n, dev, "link_prev", required=True)
+    port = _row_vector(who, port, torch.uint8, lead + (n,), dev, "port", required=True)
+    status = _row_vector(who, status, torch.int32, lead + (T,), dev, "status", required=True)
+    ret = _row_vector(who, ret, torch.float64, n, dev, "ret", required=True)
+    weight = _row_vector(who, weight, torch.float64, n, dev, "weight")
+    sort_rec = _row_vector(who, sort_rec, torch.float64, lead + (T, nport + 1, 4), dev, "sort_rec")
 
-    def new(shape, dtype, fill):
-        # an empty call launches nothing: its outputs are then what a launch would have written
-        if n and T and S:
-            return torch.empty(lead + shape, dtype=dtype, device=dev)
-        return torch.full(lead + shape, fill, dtype=dtype, device=dev)
-
-    out = HeldPortfolios(rec=new((T, nport + 1, 4), torch.float64, float("nan")), status=new((T,), torch.int32, 0),
-                         cohort=new((T, hold, nport, 2), torch.float64, float("nan")),
-                         cohort_n=new((T, hold, nport, 2), torch.int32, 0),
-                         members=new((T, hold + 1, nport), torch.int32, 0), stay=new((T, hold + 1, nport), torch.int32, 0),
-                         turnover=new((T, nport), torch.float64, float("nan")), hold=hold)
+    empty, nan, f64, i32 = not (n and T and S), float("nan"), torch.float64, torch.int32
+    out = HeldPortfolios(rec=_new_or_filled(empty, lead + (T, nport + 1, 4), f64, nan, dev),
+                         status=_new_or_filled(empty, lead + (T,), i32, 0, dev),
+                         cohort=_new_or_filled(empty, lead + (T, hold, nport, 2), f64, nan, dev),
+                         cohort_n=_new_or_filled(empty, lead + (T, hold, nport, 2), i32, 0, dev),
+                         members=_new_or_filled(empty, lead + (T, hold + 1, nport), i32, 0, dev),
+                         stay=_new_or_filled(empty, lead + (T, hold + 1, nport), i32, 0, dev),
+                         turnover=_new_or_filled(empty, lead + (T, nport), f64, nan, dev), hold=hold)
     a = L.HoldArgs(seg_off=seg_off.data_ptr(), month_index=month_index.data_ptr(), link_prev=link_prev.data_ptr(),
                    port=port.data_ptr(), status=status.data_ptr(), ret=ret.data_ptr(), weight=_ptr(weight),
                    sort_rec=_ptr(sort_rec), nrows=n, nseg=T, nsel=S, nport=nport, hold=hold,
@@ -2379,15 +2374,11 @@ def double_sort(seg_off, a, b, ret, weight=None, level=None, nyse=None, na=5, nb
     for t, what in ((a, "a"), (b, "b")):
         if t.dim() == 2 and int(t.shape[0]) != S:
             raise ValueError(f"{who}: {what} holds {int(t.shape[0])} sorts, the other signal {S}")
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError(f"{who}: seg_off must be an int64 [T+1] tensor on the signals' device")
-    T = int(seg_off.shape[0]) - 1
-    for t, dt, what in ((ret, torch.float64, "ret"), (weight, torch.float64, "weight"), (level, torch.uint8, "level"),
-                        (nyse, torch.uint8, "nyse")):
-        if t is None and what != "ret":
-            continue
-        if t is None or t.dtype != dt or t.dim() != 1 or t.shape[0] != n or t.device != dev:
-            raise ValueError(f"{who}: {what} must be a {dt} [{n}] tensor on {dev}")
+    seg_off, T = _months(who, seg_off, dev, "signals'")
+    ret = _row_vector(who, ret, torch.float64, n, dev, "ret", required=True)
+    weight = _row_vector(who, weight, torch.float64, n, dev, "weight")
+    level = _row_vector(who, level, torch.uint8, n, dev, "level")
+    nyse = _row_vector(who, nyse, torch.uint8, n, dev, "nyse")
     na, nb = int(na), int(nb)
     qa = _dsort_levels(who, "a", na, qa)
     qb = _dsort_levels(who, "b", nb, qb)
@@ -2401,27 +2392,21 @@ def double_sort(seg_off, a, b, ret, weight=None, level=None, nyse=None, na=5, nb
         raise ValueError(f"{who}: nyse_breakpoints needs nyse")
     if S > 65535:
         raise ValueError(f"{who}: at most 65535 sorts per call, got {S}")
-    seg_off, a, b, ret = seg_off.contiguous(), a.contiguous(), b.contiguous(), ret.contiguous()
-    weight, level, nyse = (None if t is None else t.contiguous() for t in (weight, level, nyse))
-    if max_seg_len is None:
-        max_seg_len = int((seg_off[1:] - seg_off[:-1]).max().item()) if T > 0 else 0
+    a, b = a.contiguous(), b.contiguous()
+    max_seg_len = _longest_month(seg_off, T, max_seg_len)
 
-    def new(shape, dtype, fill):
-        # an empty call launches nothing: its outputs are then what a launch would have written
-        if T and S:
-            return torch.empty(shape, dtype=dtype, device=dev)
-        return torch.full(shape, fill, dtype=dtype, device=dev)
-
-    nan = float("nan")
-    out = DoubleSort(rec_b=new((S, na + 1, T, nb + 1, 4), torch.float64, nan),
-                     rec_a=new((S, nb + 1, T, na + 1, 4), torch.float64, nan),
-                     cnt=new((S, T, na, nb), torch.int32, 0), cell=new((S, n), torch.uint8, 255),
-                     bpa=new((S, T, na - 1), torch.float64, nan), bpb=new((S, T, na, nb - 1), torch.float64, nan),
-                     status=new((S, T), torch.int32, 0), na=na, nb=nb, conditional=bool(conditional))
+    empty, nan, f64, i32 = not (T and S), float("nan"), torch.float64, torch.int32
+    out = DoubleSort(rec_b=_new_or_filled(empty, (S, na + 1, T, nb + 1, 4), f64, nan, dev),
+                     rec_a=_new_or_filled(empty, (S, nb + 1, T, na + 1, 4), f64, nan, dev),
+                     cnt=_new_or_filled(empty, (S, T, na, nb), i32, 0, dev),
+                     cell=_new_or_filled(empty, (S, n), torch.uint8, 255, dev),
+                     bpa=_new_or_filled(empty, (S, T, na - 1), f64, nan, dev),
+                     bpb=_new_or_filled(empty, (S, T, na, nb - 1), f64, nan, dev),
+                     status=_new_or_filled(empty, (S, T), i32, 0, dev), na=na, nb=nb, conditional=bool(conditional))
     args = L.DsortArgs(a=a.data_ptr(), b=b.data_ptr(), a_sort_stride=n if a.dim() == 2 else 0,
                        b_sort_stride=n if b.dim() == 2 else 0, ret=ret.data_ptr(), weight=_ptr(weight),
                        level=_ptr(level), nyse=_ptr(nyse), seg_off=seg_off.data_ptr(), nrows=n, nseg=T, nsel=S,
-                       max_seg_len=int(max_seg_len), na=na, nb=nb, conditional=int(bool(conditional)),
+                       max_seg_len=max_seg_len, na=na, nb=nb, conditional=int(bool(conditional)),
                        min_level=int(min_level), nyse_breakpoints=int(bool(nyse_breakpoints)), min_count=min_count,
                        min_count_bin=min_count_bin, rec_b=out.rec_b.data_ptr(), rec_a=out.rec_a.data_ptr(),
                        cnt=out.cnt.data_ptr(), cell=out.cell.data_ptr(), bpa=out.bpa.data_ptr(),
@@ -2517,17 +2502,9 @@ def group_adjust_columns(seg_off, x, group, ngroups, mode="demean", min_count=1,
         raise ValueError("group_adjust: x must be a float64 [C, rows] tensor with contiguous rows")
     dev = x.device
     C, n = int(x.shape[0]), int(x.shape[1])
-    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or seg_off.shape[0] < 1 or seg_off.device != dev:
-        raise ValueError("group_adjust: seg_off must be an int64 [T+1] tensor on the values' device")
-    seg_off = seg_off.contiguous()
-    T = int(seg_off.shape[0]) - 1
-    for t, dt, what in ((group, torch.int32, "group"), (level, torch.uint8, "level")):
-        if t is None and what == "level":
-            continue
-        if t is None or t.dtype != dt or t.dim() != 1 or t.shape[0] != n or t.device != dev:
-            raise ValueError(f"group_adjust: {what} must be a {dt} [{n}] tensor on {dev}")
-    group = group.contiguous()
-    level = None if level is None else level.contiguous()
+    seg_off, T = _months("group_adjust", seg_off, dev, "values'")
+    group = _row_vector("group_adjust", group, torch.int32, n, dev, "group", required=True)
+    level = _row_vector("group_adjust", level, torch.uint8, n, dev, "level")
     if out is None:
         out = torch.empty((C, n), dtype=torch.float64, device=dev)
     elif out.dtype != torch.float64 or tuple(out.shape) != (C, n) or out.device != dev or \
@@ -2538,14 +2515,10 @@ def group_adjust_columns(seg_off, x, group, ngroups, mode="demean", min_count=1,
     empty = not (C and n and T)
     st = None
     if stats:
-        def table(dtype, fill):
-            # an empty call launches nothing: its tables are then what a launch would have written
-            if empty:
-                return torch.full((C, T, ngroups), fill, dtype=dtype, device=dev)
-            return torch.empty((C, T, ngroups), dtype=dtype, device=dev)
-        st = GroupStats(mean=table(torch.float64, float("nan")),
-                        sd=table(torch.float64, float("nan")) if mode == "zscore" else None,
-                        count=table(torch.int32, 0))
+        sh, nan = (C, T, ngroups), float("nan")
+        st = GroupStats(mean=_new_or_filled(empty, sh, torch.float64, nan, dev),
+                        sd=_new_or_filled(empty, sh, torch.float64, nan, dev) if mode == "zscore" else None,
+                        count=_new_or_filled(empty, sh, torch.int32, 0, dev))
     a = L.GroupAdjArgs(src=x.data_ptr(), src_stride=x.stride(0) if C > 1 else max(n, 1), dst=out.data_ptr(),
                        dst_stride=out.stride(0) if C > 1 else max(n, 1), seg_off=seg_off.data_ptr(),
                        group=group.data_ptr(), level=_ptr(level), nrows=n, ncols=C, nseg=T, ngroups=ngroups,
