@@ -21,6 +21,7 @@ FM_ST_CONST_SUSPECT = 0x10
 FM_ST_CONST_COL = 0x20
 FM_ST_RANK_DEF = 0x40
 FM_ST_REFIT = 0x80
+FM_ST_NEG_VAR = 0x100
 
 FM_MAX_COLS = 31
 FM_MAX_MODELS = 6
@@ -255,6 +256,22 @@ class WlsArgs(C.Structure):
     ]
 
 
+FM_POOL_MAX_K = 14
+FM_POOL_FIRM_BLOCK = 256
+FM_POOL_SE_CLASSICAL, FM_POOL_SE_WHITE, FM_POOL_SE_MONTH, FM_POOL_SE_FIRM, FM_POOL_SE_TWOWAY = range(5)
+FM_POOL_SE_NAMES = ("classical", "white", "month", "firm", "twoway")
+
+
+class PoolArgs(C.Structure):
+    _fields_ = [
+        ("cols", _p), ("col_stride", _i64), ("nrows", _i64), ("ncols", _i32), ("nseg", _i32), ("seg_off", _p),
+        ("lo", _p), ("hi", _p), ("shift", _p), ("level", _p), ("firm", _p), ("nfirms", _i32), ("seg_lo", _i32),
+        ("seg_hi", _i32), ("month_fe", _i32), ("small_sample", _i32), ("nprob", _i32), ("pmax", _i32),
+        ("stage", _i32), ("prob_level", _p), ("prob_z", _p), ("prob_nz", _p), ("coef", _p), ("se", _p),
+        ("cov", _p), ("stat", _p), ("status", _p), ("resid", _p), ("bad", _p), ("ws", _p), ("ws_bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "fm_version": (C.c_char_p, []),
@@ -303,6 +320,8 @@ _SIGS = {
     "fm_group_adjust_batch": (_i32, [_i32]),
     "fm_portfolio_double_sort": (_i32, [C.POINTER(DsortArgs), _p]),
     "fm_wls": (_i32, [C.POINTER(WlsArgs), _p]),
+    "fm_pool": (_i32, [C.POINTER(PoolArgs), _p]),
+    "fm_pool_ws_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "fm_segment_moments": (_i32, [_p, _i64, _i32, _p, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "fm_distinct_count": (_i32, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i64, _i64, _p, _p, _p]),
     "fm_firm_chars": (_i32, [C.POINTER(CharsArgs), _p]),
@@ -323,7 +342,8 @@ _STRUCTS = {"fm_gram_args": GramArgs, "fm_solve_args": SolveArgs, "fm_select_arg
             "fm_fcmp_args": FCmpArgs, "fm_links_args": LinksArgs, "fm_horizon_args": HorizonArgs,
             "fm_fhor_args": FHorArgs, "fm_alpha_args": AlphaArgs,
             "fm_hold_args": HoldArgs, "fm_gadj_args": GroupAdjArgs,
-            "fm_dsort_args": DsortArgs, "fm_wls_args": WlsArgs}
+            "fm_dsort_args": DsortArgs, "fm_wls_args": WlsArgs,
+            "fm_pool_args": PoolArgs}
 
 _lib = None
 

@@ -1132,6 +1132,100 @@ def fm_pass_wls(panel: DevicePanel, models: Sequence[Model], weight=None, level=
     return FMResult(problems=problems, rec=rec, status=status, pmax=pmax, moments=mom, mom_stride=mom_stride)
 
 
+def firm_codes(panel: DevicePanel):
+    """Dense firm codes of the panel's rows: (int32 [rows] tensor, nfirms), code = the rank of the
+    row's ``panel.ids`` among the panel's distinct ids, so the codes ascend inside a month where the
+    ids do.  Made once and kept with the panel."""
+    if panel.ids is None:
+        raise ValueError("firm_codes: the panel has no firm ids (DevicePanel.ids)")
+    cache = panel.__dict__.get("_firm_codes")
+    if cache is None:
+        uniq, inv = torch.unique(panel.ids, return_inverse=True)
+        cache = (inv.to(torch.int32).contiguous(), int(uniq.numel()))
+        panel.__dict__["_firm_codes"] = cache
+    return cache
+
+
+@dataclass
+class PooledResult:
+    problems: List[Problem]
+    coef: torch.Tensor            # [nprob, pmax]: a, b_1 .. b_K, NaN pad (a is NaN under month FE)
+    se: torch.Tensor              # [nprob, 5, pmax]: classical, White, month, firm, two-way
+    cov: Optional[torch.Tensor]   # [nprob, 5, pmax, pmax]
+    stat: torch.Tensor            # [nprob, 8]: N, G_t, G_f, R2, SSR, s2, classical dof, 0
+    status: torch.Tensor          # [nprob] int32 (FM_ST_* bits)
+    resid: Optional[torch.Tensor]   # [nprob, rows], NaN on unused rows
+    pmax: int
+
+    @property
+    def nprob(self):
+        return len(self.problems)
+
+    def tstat(self, kind="twoway"):
+        """coef / se of one covariance kind ("classical", "white", "month", "firm", "twoway" or 0..4)."""
+        k = L.FM_POOL_SE_NAMES.index(kind) if isinstance(kind, str) else int(kind)
+        return self.coef / self.se[:, k, :]
+
+
+_POOL_WS = {}   # device -> the fm_pool workspace (grown on demand; every call rewrites what it reads)
+
+
+def pooled_regressions(panel: DevicePanel, models: Sequence[Model], level=None, nlevels=1, cuts: Cuts = None,
+                       month_fe=False, small_sample=True, seg_lo=0, seg_hi=None, cov=False, resid=False, shift=None,
+                       firm=None):
+    """Pooled panel OLS of every (model, universe level) problem over the months [seg_lo, seg_hi)
+    with classical, White, month-clustered, firm-clustered and two-way clustered standard errors
+    (A23, fm_pool), with or without month fixed effects.  Models of at most 15 regressors; the panel
+    may have any number of FP64 columns.  ``firm``: (int32 [rows] codes, nfirms) in place of
+    firm_codes(panel).  Raises ValueError when the firm codes do not ascend inside every month."""
+    if panel.cols is None:
+        raise ValueError("pooled_regressions: a planes-only panel is not supported (fm_pool reads FP64 columns)")
+    src = panel.cols
+    dev = src.device
+    T = panel.nseg
+    seg_hi = T if seg_hi is None else int(seg_hi)
+    codes, nfirms = firm_codes(panel) if firm is None else firm
+    codes = _row_vector("pooled_regressions", codes, torch.int32, panel.nrows, dev, "firm")
+    problems = _problems(models, nlevels)
+    if any(p.K > L.FM_POOL_MAX_K for p in problems):
+        raise ValueError(f"pooled_regressions: at most {L.FM_POOL_MAX_K} regressors per model")
+    pmax = max(2, max(p.K + 1 for p in problems))
+    nprob = len(problems)
+    nan = float("nan")
+    coef = torch.full((nprob, pmax), nan, dtype=torch.float64, device=dev)
+    se = torch.full((nprob, 5, pmax), nan, dtype=torch.float64, device=dev)
+    cv = torch.full((nprob, 5, pmax, pmax), nan, dtype=torch.float64, device=dev) if cov else None
+    stat = torch.zeros((nprob, 8), dtype=torch.float64, device=dev)
+    status = torch.full((nprob,), L.FM_ST_SKIPPED, dtype=torch.int32, device=dev)   # an empty call fits nothing
+    rs = torch.full((nprob, panel.nrows), nan, dtype=torch.float64, device=dev) if resid else None
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = int(L.load().fm_pool_ws_bytes(T, nprob, pmax, int(nfirms)))
+    if need < 0:
+        raise ValueError("fm_pool_ws_bytes: bad sizes")
+    ws = _POOL_WS.get(str(dev))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        _POOL_WS[str(dev)] = ws
+    lo = cuts.lo if cuts is not None else None
+    hi = cuts.hi if cuts is not None else None
+    pl, pz, pnz = _wls_tables(panel, models, problems, dev)
+    pa = L.PoolArgs(
+        cols=src.data_ptr(), col_stride=src.stride(0), nrows=panel.nrows, ncols=src.shape[0], nseg=T,
+        seg_off=panel.seg_off.data_ptr(), lo=_ptr(lo), hi=_ptr(hi), shift=_ptr(shift), level=_ptr(level),
+        firm=codes.data_ptr(), nfirms=int(nfirms), seg_lo=int(seg_lo), seg_hi=seg_hi, month_fe=int(bool(month_fe)),
+        small_sample=int(bool(small_sample)), nprob=nprob, pmax=pmax, prob_level=pl.data_ptr(), prob_z=pz.data_ptr(),
+        prob_nz=pnz.data_ptr(), coef=coef.data_ptr(), se=se.data_ptr(), cov=_ptr(cv), stat=stat.data_ptr(),
+        status=status.data_ptr(), resid=_ptr(rs), bad=bad.data_ptr(), ws=ws.data_ptr(), ws_bytes=ws.numel())
+    _kcall("fm_pool", "fm_pool", L.C.byref(pa), _stream())
+    _remember("fm_pool", "fm_pool", pa, src, lo, hi, shift, level, codes, pl, pz, pnz, coef, se, cv, stat, status, rs,
+              bad, ws)
+    nbad = int(bad.item())
+    if nbad:
+        raise ValueError(f"pooled_regressions: {nbad} rows have a firm code outside 0..{int(nfirms) - 1} or not above "
+                         "the previous row's in their month (rows must be sorted by (month, firm))")
+    return PooledResult(problems=problems, coef=coef, se=se, cov=cv, stat=stat, status=status, resid=rs, pmax=pmax)
+
+
 def drop_degenerate_months(res: FMResult, models: Sequence[Model], sd):
     """Standardized passes (A9): a month in which a regressor has fewer than two values or
     zero dispersion has an all-NaN z-score column, so every row drops out and the month is

@@ -126,6 +126,20 @@ class PipelineConfig:
     # standardize and a planes-only panel: ValueError.  None = exactly the launches of before.  Here,
     # in front of every field whose place tests pin.
     wls_weights: Optional[object] = field(default=None, kw_only=True)
+    # A23 (the robustness table beside the FM numbers): ``pooled`` runs every problem of the Table-2
+    # pass -- the same panel (after group adjustment and ranks), cuts, universe levels, models and
+    # dependent column -- once more as ONE pooled panel OLS over all months (engine.pooled_regressions)
+    # and reports classical, White, month-clustered, firm-clustered and two-way clustered standard
+    # errors, ``pooled_month_fe`` with month fixed effects, ``pooled_small_sample`` with the usual
+    # finite-sample factors.  With ``horizon`` > 1 the dependent variable is the overlapping k-month
+    # return: clustering by firm is the textbook treatment of the serial correlation that the overlap
+    # builds into a firm's residuals (Petersen 2009), beside the Newey-West lags of the FM path.
+    # Needs a panel with firm ids and FP64 columns; excludes ``wls_weights`` (weighted pooled fits are
+    # not built) and ``standardize`` (the z-scores exist only inside the Gram): ValueError otherwise.
+    # False = no launch more.  Here, in front of every field whose place tests pin.
+    pooled: bool = field(default=False, kw_only=True)
+    pooled_month_fe: bool = field(default=False, kw_only=True)
+    pooled_small_sample: bool = field(default=True, kw_only=True)
     # A14 inside the pipeline (paper Table 3's univariate properties): each month's cross-sectional
     # mean, standard deviation and ``forecast_dist_q`` quantiles of the same forecasts, over the same
     # problems and universes, under the same two rules as ``portfolios``; off = no launch more.
@@ -216,6 +230,7 @@ class PipelineResult:
     portfolio_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
     double_sort: Optional[E.DoubleSort] = None        # cfg.double_sort: tensors with a leading [nsort] dimension
     double_sort_summary: Optional[tuple] = None       # (Summary of by_b [nsort, na+1, nb+1, 4], of by_a [nsort, nb+1, na+1, 4])
+    pooled: Optional[E.PooledResult] = None               # cfg.pooled: the problems of ``res``, in its order
     forecast_dist: Optional[E.ForecastDist] = None       # cfg.forecast_dist: [nsort, T, 2+nq] and [nsort, T]
     forecast_dist_summary: Optional[E.Summary] = None    # [nsort, 2+nq]
     forecast_dist_problems: Optional[List[int]] = None   # the problem index (res.problems) of each sort
@@ -371,6 +386,21 @@ def check_wls(cfg: PipelineConfig, panel=None, y="retx"):
             raise ValueError(f"PipelineConfig: wls_weights takes a panel of at most {E.L.FM_WLS_MAX_COLS} columns, this "
                              f"one has {panel.ncols}" + (f" and horizon={cfg.horizon} adds the k-month return" if extra
                                                          else ""))
+
+
+def check_pooled(cfg: PipelineConfig, panel=None):
+    """The rules of ``PipelineConfig.pooled`` (no device work); ``panel``: the run's panel, when there
+    is one."""
+    if not cfg.pooled:
+        return
+    if cfg.wls_weights is not None:
+        raise ValueError("PipelineConfig: pooled excludes wls_weights (weighted pooled fits are not built)")
+    if cfg.standardize:
+        raise ValueError("PipelineConfig: pooled excludes standardize (the z-scores exist only inside the Gram)")
+    if panel is not None and panel.ids is None:
+        raise ValueError("PipelineConfig: pooled needs a panel with firm ids (build it with ids=...)")
+    if panel is not None and panel.cols is None:
+        raise ValueError("PipelineConfig: pooled needs a panel with FP64 columns, not a planes-only one")
 
 
 def check_horizon(cfg: PipelineConfig):
@@ -534,7 +564,10 @@ def horizon_column(panel: E.DevicePanel, cfg: PipelineConfig, y="retx"):
 def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=None, y="retx"):
     """The whole pass on one device.  ``cfg.horizon`` = h > 1 (A16): every stage -- the Gram, the
     fix-ups, the predictive records and the returns of the portfolio and comparison stages -- takes
-    the compounded h-month return f"{y}_{h}m" as the dependent variable (``PipelineResult.y_col``)."""
+    the compounded h-month return f"{y}_{h}m" as the dependent variable (``PipelineResult.y_col``).
+    ``cfg.pooled`` (A23) adds the pooled panel OLS of the same problems on the same panel, cuts,
+    levels and dependent column (``PipelineResult.pooled``); with h > 1 its firm-clustered errors are
+    the textbook treatment of the overlapping returns' serial correlation within a firm."""
     cfg = cfg or PipelineConfig()
     model_cols = model_cols or table2_models()
     check_horizon(cfg)
@@ -544,6 +577,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     check_double_sort(cfg, panel)
     check_group_adjust(cfg, panel, model_cols, y)
     check_wls(cfg, panel, y)
+    check_pooled(cfg, panel)
     for on, what in ((cfg.portfolios is not None, "portfolios"), (cfg.forecast_dist, "forecast_dist"),
                      (cfg.forecast_compare, "forecast_compare"), (cfg.extrapolate is not None, "extrapolate")):
         if on and cfg.standardize:
@@ -559,6 +593,11 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
     psumm = None
     if cfg.forecasts:
         psumm, _ = E.summarize_predictive(pred, pst, cfg.nw_lags)
+    pooled = None
+    if cfg.pooled:
+        # A23: the Table-2 pass's problems as one pooled panel OLS each, on the panel the Gram read
+        pooled = E.pooled_regressions(gpanel, models, level=level, nlevels=3 if level is not None else 1, cuts=cuts,
+                                      month_fe=cfg.pooled_month_fe, small_sample=cfg.pooled_small_sample)
     ports = port_summ = port_probs = None
     dist = dist_summ = dist_probs = None
     comp = comp_summ = comp_pairs = None
@@ -631,7 +670,7 @@ def run_pipeline(panel: E.DevicePanel, cfg: PipelineConfig = None, model_cols=No
                           forecast_compare=comp, forecast_compare_summary=comp_summ, forecast_compare_pairs=comp_pairs,
                           y_col=y, group_stats=None if gadj is None else gadj[0],
                           group_adjusted=None if gadj is None else gadj[1], held=held, held_summary=held_summ, held_alphas=held_alphas, portfolio_alphas=alphas,
-                          extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
+                          pooled=pooled, extrapolated=extr, extrapolated_summary=extr_summ, extrapolated_problems=extr_probs)
 
 
 def problem_index(res: E.FMResult, names, model_name, level):

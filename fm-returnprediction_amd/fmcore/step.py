@@ -51,6 +51,9 @@ class ShardedStep:
         if cfg.wls_weights is not None:
             raise ValueError("ShardedStep: cfg.wls_weights must be None (the step's Gram exchange carries fm_gram's "
                              "partials, which hold no weights)")
+        if cfg.pooled:
+            raise ValueError("ShardedStep: cfg.pooled must be False (a firm's scores are summed over every month, "
+                             "which a month shard does not hold)")
         self.panel, self.cfg, self.model_cols = panel, cfg, model_cols
         self.world, self.rank, self.group = world, rank, group
         self.seg_lo = seg_lo

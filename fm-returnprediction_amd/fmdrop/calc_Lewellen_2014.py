@@ -588,6 +588,62 @@ def build_table_2(subsets_comp_crsp: dict, variables_dict: dict, weight_col: str
     return _format_table_2(stats, list(subsets_comp_crsp.keys()))
 
 
+def build_table_2_pooled(subsets_comp_crsp: dict, variables_dict: dict, month_fe: bool = False) -> pd.DataFrame:
+    """The robustness table beside Table 2 (build-defined, A23; no reference line): for every Table-2
+    (model, universe, predictor) the Fama-MacBeth slope and Newey-West(4) t-statistic -- build_table_2's
+    pass, unchanged -- and beside them the slope of ONE pooled panel OLS over all months
+    (run_pooled_regression; ``month_fe``: with month fixed effects) with its t-statistics from White,
+    month-clustered, firm-clustered (permno) and two-way clustered standard errors.  A firm effect that
+    Fama-MacBeth ignores shows as a firm-clustered t well below the FM one (Petersen 2009).  Numeric
+    frame: rows (Model, Predictor), columns (universe, "FM slope" / "FM t" / "Pooled slope" / "t white" /
+    "t month" / "t firm" / "t twoway").  The frames need ``permno`` and datetime64 or integer
+    ``mthcaldt``."""
+    model_cols = _LW.table2_models(variables_dict)
+    metrics = ["FM slope", "FM t", "Pooled slope", "t white", "t month", "t firm", "t twoway"]
+    batched = _batched_subsets(subsets_comp_crsp)
+    jobs = []
+    if batched is not None:
+        frame, level = batched
+        jobs.append((frame, level, 3, {i: s for i, s in enumerate(_LW.SUBSET_NAMES)}))
+    else:
+        for s, frame in subsets_comp_crsp.items():
+            jobs.append((frame, None, 1, {0: s}))
+    cells = {}
+    for frame, level, nlevels, level_names in jobs:
+        ids = _firm_ids(frame["permno"], frame["mthcaldt"])
+        if ids is None:
+            raise ValueError("build_table_2_pooled: 'permno' must hold whole-number firm ids and 'mthcaldt' "
+                             "datetime64 or integer months")
+        # rows by (month, permno): the order the firm codes of a month must ascend in
+        order = np.lexsort((ids, frame["mthcaldt"].to_numpy()))
+        frame = frame.iloc[order]
+        level = None if level is None else level[order]
+        panel, models, res = _fm_summaries(frame, model_cols, level, nlevels)
+        status_h = res.status.cpu().numpy()
+        for k in sorted(range(len(res.problems)), key=lambda k: (res.problems[k].model, res.problems[k].level)):
+            _api.raise_like_reference(status_h[:, k], res.problems[k].K)
+        summ, _ = _E.summarize_result(res)
+        mean, tstat = summ.mean.cpu().numpy(), summ.tstat.cpu().numpy()
+        import torch
+        panel.ids = torch.from_numpy(ids[order][panel.order].astype(np.int64)).to(panel.device)
+        lvl_t = None if level is None else torch.from_numpy(np.ascontiguousarray(level[panel.order])).to(panel.device)
+        pool = _E.pooled_regressions(panel, models, level=lvl_t, nlevels=nlevels, month_fe=month_fe)
+        coef, pt = pool.coef.cpu().numpy(), [pool.tstat(kind).cpu().numpy() for kind in ("white", "month", "firm", "twoway")]
+        for k, p in enumerate(res.problems):
+            name = models[p.model].name
+            for r in range(p.K):
+                cells[(name, r, level_names[p.level])] = [mean[k, 1 + r], tstat[k, 1 + r], coef[k, 1 + r]] + \
+                    [t[k, 1 + r] for t in pt]
+    present = [s for s in _LW.SUBSET_NAMES if s in subsets_comp_crsp]
+    index, rows = [], []
+    for model, labels in _LW.MODELS_PREDICTORS.items():
+        for r, lbl in enumerate(labels):
+            index.append((model, lbl))
+            rows.append([v for s in present for v in cells.get((model, r, s), [np.nan] * len(metrics))])
+    return pd.DataFrame(rows, index=pd.MultiIndex.from_tuples(index, names=["Model", "Predictor"]),
+                        columns=pd.MultiIndex.from_tuples([(s, m) for s in present for m in metrics]), dtype=np.float64)
+
+
 # ------------------------------------------------------------------------------------------
 # Figure 1
 # ------------------------------------------------------------------------------------------

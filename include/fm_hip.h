@@ -79,6 +79,10 @@
  *   fm_wls          <- build-defined extension A22; no reference line: the weighted (value-weighted)
  *                      monthly cross-sections, statsmodels' WLS per month, written as fm_solve
  *                      writes the OLS ones
+ *   fm_pool         <- build-defined extension A23; no reference line: the pooled panel OLS of the
+ *                      same regressions with classical, White, month-clustered, firm-clustered and
+ *                      two-way clustered standard errors, with or without month fixed effects
+ *                      (Petersen 2009; Thompson 2011; Cameron, Gelbach and Miller 2011)
  *   fm_segment_moments, fm_distinct_count <- build_table_1's monthly mean / std(ddof=1)
  *                      and permno nunique (src/calc_Lewellen_2014.py:623-646)
  *   fm_firm_chars   <- get_factors' twelve monthly characteristics: groupby("permno")
@@ -127,6 +131,7 @@ extern "C" {
 #define FM_ST_RANK_DEF 0x40u      /* pinv min-norm solution (a null direction was cut)  */
 #define FM_ST_REFIT 0x80u         /* ill-conditioned Sxx (pivot < 1e-6 of its diagonal):
                                      fm_solve_fixup re-solves from the rows (QR + SVD)   */
+#define FM_ST_NEG_VAR 0x100u      /* fm_pool: a two-way clustered variance is not above 0 */
 
 #define FM_MAX_COLS 31            /* z = [1, cols] fits two 16-wide MFMA tiles          */
 #define FM_MAX_MODELS 6
@@ -235,7 +240,8 @@ const char* fm_last_error(void);
     X(fm_gram_args) X(fm_solve_args) X(fm_select_args) X(fm_universe_args) X(fm_ts_args)      \
     X(fm_chars_args) X(fm_port_args) X(fm_rank_args) X(fm_forecast_src) X(fm_fport_args)      \
     X(fm_fdist_args) X(fm_fcmp_args) X(fm_links_args) X(fm_horizon_args) X(fm_fhor_args)      \
-    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args) X(fm_dsort_args) X(fm_wls_args)
+    X(fm_alpha_args) X(fm_hold_args) X(fm_gadj_args) X(fm_dsort_args) X(fm_wls_args) \
+    X(fm_pool_args)
 /* sizeof the named struct of FM_ARG_STRUCTS ("fm_gram_args", ...); -1 for an unknown name.
  * Bindings check their struct layouts against it before the first call. */
 int64_t fm_struct_size(const char* name);
@@ -1222,6 +1228,109 @@ typedef struct fm_wls_args {
 } fm_wls_args;
 
 int fm_wls(const fm_wls_args* args, void* stream);
+
+/* fm_pool: the pooled panel OLS of y on [1, x] over all months of a range at once, for every problem
+ * (model x universe level), with five covariance estimates of its coefficients (build-defined
+ * extension A23; the reference has no pooled fit, so no reference line: the definition is the
+ * textbook sandwich of Petersen 2009 / Cameron, Gelbach and Miller 2011).  FP64 columns (cols ==
+ * NULL, a planes-only panel, is refused); rows sorted by (month, firm), months seg_off[nseg+1] of
+ * any length; only the months [seg_lo, seg_hi) take part.  The problem tables are fm_wls's (prob_z[p]
+ * = 0, 1 + the panel columns of x_1 .. x_K, 1 + the panel column of y; K = prob_nz[p] - 2 <=
+ * FM_POOL_MAX_K, so z = [1, x, y] is one 16-wide tile): the limit is on the model's width, the panel
+ * may have any number of columns.  firm[rows] is a dense firm code in 0 .. nfirms-1, strictly
+ * ascending inside each month; bad[0] (zeroed by the caller) receives the number of rows of the range
+ * whose code is outside 0 .. nfirms-1 or not above their predecessor's in the month.  The results of
+ * a call with bad != 0 are unspecified, but every access stays in bounds.  Per problem:
+ *   a row is used when every column of the list (y included) is non-NaN and level >= prob_level[p]
+ *     (level NULL: every row); values are clipped first, as fm_gram / fm_wls clip (max with lo, then
+ *     min with hi, both [ncols][nseg]; a NaN bound is ignored; both NULL: no clipping);
+ *   N = rows used, G_t = months with a used row, G_f = firms with a used row, p0 = K + 1;
+ *   month_fe == 0: the pooled means m and the moments S centred about them give b = Sxx^-1 Sxy,
+ *     a = m_y - b'm_x, R2 = 1 - SSR / Syy, classical dof = N - K - 1; the covariances are formed for
+ *     the regressors x~ = [1, x - m_x] and mapped back to the raw intercept (exactly: x~ is a
+ *     reparametrisation);
+ *   month_fe != 0: x and y are demeaned within each month over that month's used rows; no intercept
+ *     (coef[0] and every se[.][0] are NaN, the covariances' row and column 0 too),
+ *     b = (sum_t S_t,xx)^-1 sum_t S_t,xy, R2 is the within R2, classical dof = N - K - G_t;
+ *   residuals e come from the centred data, scores u_i = x~_i e_i; with A the inverse of x~'x~:
+ *     FM_POOL_SE_CLASSICAL s2 A with s2 = SSR / dof;  FM_POOL_SE_WHITE A (sum u u') A;
+ *     FM_POOL_SE_MONTH A sum_t (sum_{i in t} u)(..)' A;  FM_POOL_SE_FIRM A sum_f (sum_t u_ft)(..)' A;
+ *     FM_POOL_SE_TWOWAY V_firm + V_month - V_white;
+ *   small_sample != 0: White is multiplied by N / (N - p0), a clustered kind with G clusters by
+ *     G / (G - 1) (N - 1) / (N - p0), two-way combines the corrected terms.  A clustered kind with
+ *     G < 2 is NaN, and so is two-way.  A diagonal entry of V_twoway that is not above 0 gives a NaN
+ *     se and sets FM_ST_NEG_VAR beside FM_ST_FITTED;
+ *   status: N < p0 + 1 or dof < 1: FM_ST_SKIPPED alone; else a used row with +-inf after clipping:
+ *     FM_ST_INF_IN_X / FM_ST_INF_IN_Y alone; else a predictor whose centred second moment is not
+ *     above 1e-20 of its raw one, or a Cholesky pivot not above 1e-6 (fm_solve's REFIT_REL) of its
+ *     diagonal entry: FM_ST_RANK_DEF alone (no pinv re-solve, as in fm_wls).  In these cases coef, se
+ *     and cov are NaN and stat[0] = N.
+ * Outputs: coef[nprob][pmax] (a, b_1 .. b_K, NaN pad), se[nprob][5][pmax], cov[nprob][5][pmax][pmax]
+ * (optional), stat[nprob][8] = N, G_t, G_f, R2, SSR, s2, classical dof, 0; status[nprob];
+ * resid[nprob][nrows] (optional): e on the used rows of the range's months and NaN on their other
+ * rows (rows of months outside the range are not written).
+ * Eight launches, all on `stream`: (1) the code check; (2) per (month, problem) the sums about
+ * `shift` ([ncols][nseg], NULL: 0); (3) per problem the means, N, G_t and the skipped / inf verdict;
+ * (4) the pass of (2) about the means for the centred moments; (5) per problem the fit; (6) per
+ * (month, problem) the residuals, sum u and sum u u'; (7) per (block of FM_POOL_FIRM_BLOCK firm
+ * codes, problem) the firms' score sums, kept in LDS while the workgroup walks the months in order
+ * (its rows of a month are one run, found by binary search in `firm`), then sum_f s_f s_f' over
+ * its firms in code order; (8) per problem the sandwiches.  The month passes put 64 rows into an
+ * LDS tile and add them with sixteen v_mfma_f64_16x16x4_f64 (A = B = the tile's rows, unused rows
+ * as zeros); tile c of a month is wave c % 4's, the waves are added in
+ * wave order, months and firm blocks in index order.  No floating-point atomics.  So a repeat, a
+ * problem alone or in a batch, firm codes that are the same, and [seg_lo, seg_hi) of a panel against
+ * a panel of those months alone give the same bits.
+ * Refused with FM_EINVAL before any launch (the message names the field): a negative size, ncols
+ * < 1, more than 65,535 problems, pmax outside 2 .. FM_POOL_MAX_K + 1, col_stride < nrows, lo
+ * without hi, a stage outside 0 .. 8, seg_lo > seg_hi or outside [0, nseg], nfirms < 0, a NULL
+ * required pointer, ws_bytes below fm_pool_ws_bytes(nseg, nprob, pmax, nfirms) (-1 for sizes below
+ * zero).  Column indices outside the panel are clamped into it, a prob_nz outside 2 .. pmax + 1
+ * into that range.  nseg == 0, nprob == 0 or seg_lo == seg_hi is a valid empty call.
+ * Zero-initialize the struct (it grows at the end). */
+#define FM_POOL_MAX_K 14
+#define FM_POOL_FIRM_BLOCK 256
+#define FM_POOL_SE_CLASSICAL 0
+#define FM_POOL_SE_WHITE 1
+#define FM_POOL_SE_MONTH 2
+#define FM_POOL_SE_FIRM 3
+#define FM_POOL_SE_TWOWAY 4
+typedef struct fm_pool_args {
+    const double* cols;          /* [ncols][col_stride] */
+    int64_t col_stride;
+    int64_t nrows;               /* seg_off[nseg] */
+    int32_t ncols;               /* >= 1, any width */
+    int32_t nseg;
+    const int64_t* seg_off;      /* [nseg+1] */
+    const double* lo;            /* [ncols][nseg] clip bounds, or both NULL */
+    const double* hi;
+    const double* shift;         /* [ncols][nseg] pivot of the first pass, or NULL */
+    const uint8_t* level;        /* [rows] universe level, or NULL */
+    const int32_t* firm;         /* [rows] dense firm code, strictly ascending inside a month */
+    int32_t nfirms;
+    int32_t seg_lo, seg_hi;      /* the months that take part */
+    int32_t month_fe;
+    int32_t small_sample;
+    int32_t nprob;
+    int32_t pmax;                /* >= max K + 1 over the problems, 2 .. FM_POOL_MAX_K + 1 */
+    int32_t stage;               /* 0: every launch; 1..8 (timing tools): that launch alone, on the
+                                    workspace and outputs a full call with the same arguments left */
+    const int32_t* prob_level;   /* [nprob] */
+    const int32_t* prob_z;       /* [nprob][32] z indices: 0, 1 + x columns..., 1 + y column */
+    const int32_t* prob_nz;      /* [nprob] K + 2 */
+    double* coef;                /* [nprob][pmax] */
+    double* se;                  /* [nprob][5][pmax] */
+    double* cov;                 /* [nprob][5][pmax][pmax] or NULL */
+    double* stat;                /* [nprob][8] */
+    uint32_t* status;            /* [nprob] FM_ST_* bits */
+    double* resid;               /* [nprob][nrows] or NULL */
+    int32_t* bad;                /* [1], zeroed by the caller */
+    void* ws;                    /* fm_pool_ws_bytes(nseg, nprob, pmax, nfirms) bytes */
+    int64_t ws_bytes;
+} fm_pool_args;
+
+int64_t fm_pool_ws_bytes(int32_t nseg, int32_t nprob, int32_t pmax, int32_t nfirms);
+int fm_pool(const fm_pool_args* args, void* stream);
 
 /* Table 1.  A row counts for column c when level == NULL or level[r] >= min_level, its value
  * is not NaN and, with finite_only != 0, not +-inf.  fm_segment_moments: per (column, segment)
