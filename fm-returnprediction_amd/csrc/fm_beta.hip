@@ -82,15 +82,6 @@ __global__ __launch_bounds__(BT) void beta_prefix_kernel(const double* __restric
     }
 }
 
-__device__ __forceinline__ int64_t lower_bound_days(const int32_t* day, int64_t lo, int64_t hi, int v) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (day[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // numpy's pairwise-sum leaf (a block of <= 128 values: eight running accumulators combined
 // as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8 tail; < 8 values in order), so a
 // short window's sums are the oracle's bit for bit.  Longer windows (non-finite ones only)
@@ -159,8 +150,8 @@ __global__ __launch_bounds__(BT) void beta_query_kernel(const int32_t* __restric
         const int t0 = week_start_dev(day[a]), last = day[b - 1];
         for (int S = week_start_dev(q_day1[q]); S >= q_day0[q]; S -= 7) {
             if (S < t0 || S > last) continue;
-            const int64_t i0 = lower_bound_days(day, a, b, S);
-            const int64_t i1 = lower_bound_days(day, i0, b, S + period_days);
+            const int64_t i0 = lower_bound(day, a, b, S);
+            const int64_t i1 = lower_bound(day, i0, b, S + period_days);
             if (i1 <= i0) continue;   // an empty window is not emitted
             double s[5];
 #pragma unroll

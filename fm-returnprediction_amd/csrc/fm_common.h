@@ -43,8 +43,61 @@ int raise_dynamic_lds(size_t max_bytes, const char* who) {
     return FM_OK;
 }
 
+// whether [a, a + na) and [b, b + nb) share a byte
+inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na > 0 && nb > 0 && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// A named argument array of an entry point; an optional one may be NULL.
+struct Span {
+    const char* name;
+    const void* p;
+    int64_t bytes;
+    bool optional = false;
+};
+// The entry points' pointer checks: every span that is not optional is there, and no output shares
+// a byte with an input.
+template <int NI, int NO>
+int check_spans(const char* who, const Span (&in)[NI], const Span (&out)[NO]) {
+    for (const Span& s : in) FM_REQUIRE(s.p != nullptr || s.optional, "%s: %s is NULL", who, s.name);
+    for (const Span& s : out) FM_REQUIRE(s.p != nullptr || s.optional, "%s: %s is NULL", who, s.name);
+    for (const Span& o : out)
+        for (const Span& s : in)
+            FM_REQUIRE(o.p == nullptr || s.p == nullptr || !overlaps(o.p, o.bytes, s.p, s.bytes),
+                       "%s: %s must not overlap %s", who, o.name, s.name);
+    return FM_OK;
+}
+
 constexpr uint64_t SENT = ~0ull;   // key of NaN / absent values: sorts after +inf
 constexpr int WAVE = 64;
+// A pivot below REFIT_REL of its original diagonal (1 - R^2 of a regressor on the previous
+// ones) means cond(Sxx) >~ 1e6: the normal-equation error (~eps * cond(Sxx)) could exceed
+// the 1e-9 contract, so the problem is flagged FM_ST_REFIT and re-solved from its rows by
+// fm_solve_fixup (Householder QR + SVD of R: error ~eps * cond(X), as statsmodels' SVD).
+// fm_wls and fm_pool refuse such a pivot (FM_ST_RANK_DEF).
+constexpr double REFIT_REL = 1e-6;
+
+// first index in [lo, hi) whose value is >= key (hi if none); v ascends there
+template <typename T, typename I, typename K>
+__device__ __forceinline__ I lower_bound(const T* v, I lo, I hi, K key) {
+    while (lo < hi) {
+        const I mid = lo + ((hi - lo) >> 1);
+        if (v[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Month s's rows [*b0, *b1): a foreign seg_off reads nothing outside [0, nrows), and never runs
+// backwards.
+__device__ __forceinline__ void month_rows(const int64_t* seg_off, int s, int64_t nrows, int64_t* b0, int64_t* b1) {
+    int64_t x0 = seg_off[s], x1 = seg_off[s + 1];
+    x0 = x0 < 0 ? 0 : (x0 > nrows ? nrows : x0);
+    x1 = x1 > nrows ? nrows : (x1 < x0 ? x0 : x1);
+    *b0 = x0;
+    *b1 = x1;
+}
 
 // Panel values as FP64 columns or as the split panel's two 32-bit planes (high words, low
 // words; fm_gen_panel_planes / fm_split_planes): element i (= c * stride + r) either way.
@@ -133,6 +186,9 @@ __device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
     return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(v), l));
 }
 // 64-bit readfirstlane: a value the caller knows to be wave-uniform, into SGPRs
 __device__ __forceinline__ uint64_t readfirstlane_u64(uint64_t v) {

@@ -190,19 +190,6 @@ __global__ __launch_bounds__(GDT) void group_adjust_kernel(fm_gadj_args a, int B
     }
 }
 
-// whether [a, a + na) and [b, b + nb) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return na > 0 && nb > 0 && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
-struct Span {
-    const char* name;
-    const void* p;
-    int64_t bytes;
-    bool optional = false;
-};
-
 }  // namespace
 }  // namespace fm
 
@@ -234,12 +221,7 @@ extern "C" int fm_group_adjust(const fm_gadj_args* args, void* stream) {
                        {"group", a.group, 4 * n},                       {"level", a.level, n, true}};
     const Span out[] = {{"dst", a.dst, 8 * ((C - 1) * a.dst_stride + n)}, {"gcount", a.gcount, 4 * C * T * G, true},
                         {"gmean", a.gmean, 8 * C * T * G, true},          {"gsd", a.gsd, 8 * C * T * G, true}};
-    for (const Span& s : in) FM_REQUIRE(s.p != nullptr || s.optional, "fm_group_adjust: %s is NULL", s.name);
-    for (const Span& s : out) FM_REQUIRE(s.p != nullptr || s.optional, "fm_group_adjust: %s is NULL", s.name);
-    for (const Span& o : out)
-        for (const Span& s : in)
-            FM_REQUIRE(o.p == nullptr || s.p == nullptr || !overlaps(o.p, o.bytes, s.p, s.bytes),
-                       "fm_group_adjust: %s must not overlap %s", o.name, s.name);
+    if (const int rc = check_spans("fm_group_adjust", in, out)) return rc;   // the group tables are optional
     // as few batches of columns as the bins allow, of equal size (every batch finds the tiles' codes again)
     int B = fm_group_adjust_batch(a.ngroups);
     B = B > a.ncols ? a.ncols : B;

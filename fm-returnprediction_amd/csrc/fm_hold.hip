@@ -61,9 +61,10 @@ __global__ __launch_bounds__(HDT) void portfolio_hold_kernel(fm_hold_args a, int
     for (int i = tid; i < ncnt; i += HDT) cnt[i] = 0;
     __syncthreads();
 
+    // (month_rows' clamp in the looser form the loop below needs: the strict one cost 1 % at hold 1 and 6)
     int64_t b0 = a.seg_off[t], b1 = a.seg_off[t + 1];
     b0 = b0 < 0 ? 0 : b0;
-    b1 = b1 > nrows ? nrows : b1;   // a foreign seg_off reads nothing outside [0, nrows)
+    b1 = b1 > nrows ? nrows : b1;
     double* ws = sums + (size_t)w * nsum;
     double* wt = term + w * 3 * WAVE;
     uint8_t* wo = own_port + (size_t)w * B * WAVE;
@@ -211,19 +212,6 @@ __global__ __launch_bounds__(HDT) void portfolio_hold_kernel(fm_hold_args a, int
     if (tid < nb) a.status_out[(int64_t)(j0 + tid) * a.nseg + t] = run_ok(j0 + tid, k - 1) ? 1u : 0u;
 }
 
-// whether [a, a + na) and [b, b + nb) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return na > 0 && nb > 0 && x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
-struct Span {
-    const char* name;
-    const void* p;
-    int64_t bytes;
-    bool optional = false;
-};
-
 }  // namespace
 }  // namespace fm
 
@@ -249,13 +237,7 @@ extern "C" int fm_portfolio_hold(const fm_hold_args* args, void* stream) {
                         {"cohort_n", a.cohort_n, 4 * S * T * k * P * 2}, {"cohort", a.cohort, 8 * S * T * k * P * 2},
                         {"status_out", a.status_out, 4 * S * T},         {"rec", a.rec, 8 * S * T * (P + 1) * 4},
                         {"turnover", a.turnover, 8 * S * T * P}};
-    for (const Span& s : in)
-        FM_REQUIRE(s.p != nullptr || s.optional, "fm_portfolio_hold: %s is NULL", s.name);
-    for (const Span& s : out) FM_REQUIRE(s.p != nullptr, "fm_portfolio_hold: %s is NULL", s.name);
-    for (const Span& o : out)
-        for (const Span& s : in)
-            FM_REQUIRE(s.p == nullptr || !overlaps(o.p, o.bytes, s.p, s.bytes), "fm_portfolio_hold: %s must not overlap %s",
-                       o.name, s.name);
+    if (const int rc = check_spans("fm_portfolio_hold", in, out)) return rc;   // every output is required
     // as few batches of sorts as the LDS budget allows, of equal size (every batch repeats the walk)
     const size_t per_sort = hold_lds_bytes(1, a.hold, a.nport) - 8 * HDW * 3 * WAVE;
     int B = (int)((HOLD_LDS_BUDGET - 8 * HDW * 3 * WAVE) / per_sort);

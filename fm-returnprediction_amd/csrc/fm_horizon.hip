@@ -27,17 +27,6 @@ namespace {
 constexpr int HT = 256;          // threads per workgroup: four 64-row tiles
 constexpr int H_MAX_GRID = 4096; // 256 CUs x 8 workgroups x 2 rounds; longer panels stride
 
-// first index j in [lo, hi) with a[j] >= key (hi if none)
-__device__ __forceinline__ int64_t lower_bound_i64(const int64_t* __restrict__ a, int64_t lo, int64_t hi,
-                                                   int64_t key) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // the segment of row r: the s with seg_off[s] <= r < seg_off[s+1], searched in [s_lo, s_hi]
 // (r lies in one of them); empty segments are skipped by the strict upper bound
 __device__ __forceinline__ int seg_of_row(const int64_t* __restrict__ seg_off, int s_lo, int s_hi, int64_t r) {
@@ -81,7 +70,7 @@ __device__ __forceinline__ int wave_seg_of_row(const int64_t* __restrict__ seg_o
 // segment (which starts at row t0) that holds the match if there is one.
 __device__ __forceinline__ int32_t link_of(const int64_t* __restrict__ ids, int64_t id, int64_t t0, int64_t w_lo,
                                            int64_t w_hi) {
-    const int64_t pos = lower_bound_i64(ids, w_lo, w_hi, id);
+    const int64_t pos = lower_bound(ids, w_lo, w_hi, id);
     if (pos < w_hi && ids[pos] == id) return (int32_t)(pos - t0);
     return -1;
 }
@@ -112,9 +101,8 @@ __global__ __launch_bounds__(HT) void month_links_kernel(const int64_t* __restri
             const int64_t id = live ? ids[i] : 0;
             if (live && i > 0 && i > seg_off[s0]) nbad = ids[i - 1] >= id;
             if (t_ok) {
-                int64_t t0 = seg_off[t], t1 = seg_off[t + 1];
-                t0 = t0 < 0 ? 0 : t0;
-                t1 = t1 > nrows ? nrows : t1;   // a foreign seg_off reads nothing outside ids
+                int64_t t0, t1;
+                month_rows(seg_off, t, nrows, &t0, &t1);
                 // the window of the tile's ids in month t, from its first and last id
                 const int64_t id_first = (int64_t)readlane_u64((uint64_t)id, 0);
                 const int64_t id_last = (int64_t)readlane_u64((uint64_t)id, (int)(r1 - r0));
@@ -135,9 +123,8 @@ __global__ __launch_bounds__(HT) void month_links_kernel(const int64_t* __restri
             const int64_t id = ids[i];
             if (i > 0 && i > seg_off[s]) nbad = ids[i - 1] >= id;
             if (t_ok) {
-                int64_t t0 = seg_off[t], t1 = seg_off[t + 1];
-                t0 = t0 < 0 ? 0 : t0;
-                t1 = t1 > nrows ? nrows : t1;
+                int64_t t0, t1;
+                month_rows(seg_off, t, nrows, &t0, &t1);
                 out = link_of(ids, id, t0, t0, t1);
             }
         }
@@ -193,12 +180,6 @@ __global__ __launch_bounds__(HT) void horizon_return_kernel(const double* __rest
 int tile_grid(int64_t nrows) {
     const int64_t blocks = (nrows + HT - 1) / HT;
     return (int)(blocks < H_MAX_GRID ? blocks : H_MAX_GRID);
-}
-
-// whether [a, a + na) and [b, b + nb) share a byte
-bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
 }
 
 }  // namespace

@@ -18,23 +18,20 @@
 // The three passes are one piece of code: a wave's lanes hold one row each, compute the row's z (or
 // u) and put it into the wave's LDS tile, unused rows marked; the tile is then added to the wave's
 // 16 x 16 accumulator with sixteen v_mfma_f64_16x16x4_f64 (lane (k, q) holds column q of row k of a
-// 4-row group, as in fm_wls; A = B = z).  Tile c of a month is wave c % 4's, the four waves are added
-// in wave order.  pass<2> and firm compute a row's scores with the same function, so a firm that
+// 4-row group; A = B = z).  Tile c of a month is wave c % 4's, the four waves are added in wave
+// order.  What fm_wls.hip does the same way is in fm_reg16_dev.h: a problem's width and columns, a
+// month's column parameters (ColPar), the accumulator epilogue.  pass<2> and firm compute a row's scores with the same function, so a firm that
 // occurs once has the bits of its White term.
 #include <math.h>
 
-#include "fm_common.h"
+#include "fm_reg16_dev.h"
 
 namespace fm {
 namespace {
 
 constexpr int PT = 256;                    // threads of a workgroup
 constexpr int PNW = PT / WAVE;             // waves
-constexpr int ZW = 16;                     // z = [1, x_1 .. x_K, y], K + 2 <= 16
-constexpr int RS = ZW + 1;                 // tile row stride (doubles): odd; slot ZW marks a used row
 constexpr int FB = FM_POOL_FIRM_BLOCK;
-constexpr double REFIT_REL = 1e-6;         // fm_solve's: a pivot below this part of its diagonal is ill-conditioned
-constexpr double CONST_REL = 1e-20;        // centred / raw second moment at or below this: a constant column
 
 // workspace, in doubles
 constexpr int REC = 288;                   // per (month, problem): [0, 256) the 16 x 16 sums, [256, 272) sum u, 272 the inf bits
@@ -46,8 +43,6 @@ constexpr int FIT_M = 272;                 // [16] the pooled means by z index: 
 constexpr int FIT_MR = 296;                // [16] the same with what the pivots left of the first moments
 constexpr int FIT_OK = 288, FIT_N = 289, FIT_GT = 290, FIT_SYY = 291, FIT_DOF = 292;
 constexpr int FPART = 257;                 // per (problem, firm block): 16 x 16 partial meat, then the block's G_f
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 struct Ws {
     double* rec;    // [nseg][nprob][REC]
@@ -70,30 +65,7 @@ __host__ __device__ inline Ws ws_of(const fm_pool_args& a) {
     return w;
 }
 
-__device__ __forceinline__ int prob_width(const fm_pool_args& a, int p) {   // nz = K + 2, inside the tile and coef
-    int nz = a.prob_nz[p];
-    nz = nz > a.pmax + 1 ? a.pmax + 1 : nz;
-    return nz < 2 ? 2 : (nz > ZW ? ZW : nz);
-}
-__device__ __forceinline__ int64_t col_offset(const fm_pool_args& a, const int32_t* zi, int j, int nz) {
-    int c = zi[j < nz ? j : nz - 1] - 1;
-    c = c < 0 ? 0 : (c >= a.ncols ? a.ncols - 1 : c);
-    return (int64_t)c;
-}
-__device__ __forceinline__ void month_rows(const fm_pool_args& a, int s, int64_t* b0, int64_t* b1) {
-    int64_t x0 = a.seg_off[s], x1 = a.seg_off[s + 1];
-    x0 = x0 < 0 ? 0 : (x0 > a.nrows ? a.nrows : x0);
-    x1 = x1 > a.nrows ? a.nrows : (x1 < x0 ? x0 : x1);   // a foreign seg_off reads nothing outside [0, nrows)
-    *b0 = x0;
-    *b1 = x1;
-}
-
-// The month's parameters of the problem's local columns: clip bounds and pivot.
-struct ColPar {
-    double lo[ZW], hi[ZW], piv[ZW];
-};
-
-// Row r of a month: z[0] = 1, z[j] = clip(column j) - piv[j] for j < nz, 0 past the list.  Returns
+// Row r of a month (a tile row holds z and, in slot ZW, whether the row is used): z[0] = 1, z[j] = clip(column j) - piv[j] for j < nz, 0 past the list.  Returns
 // whether the row is used; *inf gets the FM_ST_INF_* bits of its clipped values.
 __device__ __forceinline__ bool pool_row(const fm_pool_args& a, const int64_t* coff, const ColPar& cp, int nz, int u,
                                          int64_t r, double (&z)[ZW], uint32_t* inf) {
@@ -133,7 +105,7 @@ __device__ __forceinline__ double pool_scores(const double* b, int nz, double (&
 __global__ __launch_bounds__(PT) void pool_check_kernel(fm_pool_args a) {
     const int s = a.seg_lo + blockIdx.x;
     int64_t b0, b1;
-    month_rows(a, s, &b0, &b1);
+    month_rows(a.seg_off, s, a.nrows, &b0, &b1);
     int n = 0;
     for (int64_t r = b0 + threadIdx.x; r < b1; r += PT) {
         const int f = a.firm[r];
@@ -167,7 +139,7 @@ __global__ __launch_bounds__(PT) void pool_pass_kernel(fm_pool_args a) {
     const int u = a.prob_level[p];
     const int32_t* zi = a.prob_z + (int64_t)p * 32;
     int64_t b0, b1;
-    month_rows(a, s, &b0, &b1);
+    month_rows(a.seg_off, s, a.nrows, &b0, &b1);
     const int64_t so = (int64_t)s * a.nprob + p;
     double* rec = W.rec + so * REC;
     const double* fit = W.fit + (int64_t)p * FIT;
@@ -178,14 +150,8 @@ __global__ __launch_bounds__(PT) void pool_pass_kernel(fm_pool_args a) {
     }
     if (tid < ZW) {
         const int j = tid;
-        const int64_t c = col_offset(a, zi, j, nz);
-        L.coff[j] = c * a.col_stride;
-        const bool col = j >= 1 && j < nz;
-        L.cp.lo[j] = col && a.lo ? a.lo[c * a.nseg + s] : NAN;
-        L.cp.hi[j] = col && a.hi ? a.hi[c * a.nseg + s] : NAN;
-        double pv = 0.0;
-        if (col) pv = MODE == 0 ? (a.shift ? a.shift[c * a.nseg + s] : 0.0) : W.piv[so * 16 + j];
-        L.cp.piv[j] = pv;
+        L.coff[j] = col_offset(a, zi, j, nz) * a.col_stride;
+        stage_col_par(a, zi, j, nz, s, MODE == 0 ? nullptr : W.piv + so * 16, L.cp);
         L.b[j] = MODE == 2 && j >= 1 && j < nz - 1 ? fit[FIT_B + j] : 0.0;
     }
     if (tid == 0) L.flags = 0;
@@ -224,16 +190,10 @@ __global__ __launch_bounds__(PT) void pool_pass_kernel(fm_pool_args a) {
         if (lane == 0 && inf != 0) atomicOr(&L.flags, inf);
     }
     __syncthreads();   // every wave is done with its tile
-    // v_mfma_f64_16x16x4_f64: register r of lane (kr, q) is D[kr + 4 r][q]
-    double* img = L.tile + w * (ZW * ZW);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) img[(kr + 4 * r) * ZW + q] = acc[r];
+    gram16_store_image(acc, L.tile, w, kr, q);
     if (MODE == 2 && kr == 0) L.tile[PNW * ZW * ZW + w * ZW + q] = acc1[0];   // D[0][q] = sum u_q
     __syncthreads();
-    double g = L.tile[tid];
-#pragma unroll
-    for (int x = 1; x < PNW; ++x) g += L.tile[x * (ZW * ZW) + tid];
-    rec[tid] = g;
+    rec[tid] = gram16_sum_images<PNW>(L.tile, tid);
     if (MODE == 2 && tid < ZW) {
         double v = L.tile[PNW * ZW * ZW + tid];
 #pragma unroll
@@ -264,6 +224,8 @@ __global__ __launch_bounds__(PT) void pool_means_kernel(fm_pool_args a) {
     double* fit = W.fit + (int64_t)p * FIT;
     if (tid < ZW) {   // thread j: column j's sum over the months, in month order
         const int j = tid;
+        // (the shift by hand, not through col_par: inside this serial loop over the months the helper's
+        // column lookup is not hoisted and the launch takes 156 us instead of 91)
         const int64_t c = col_offset(a, zi, j, nz);
         const bool col = j >= 1 && j < nz;
         double sum = 0.0, N = 0.0, Gt = 0.0;
@@ -426,15 +388,6 @@ struct FirmLds {
     int run_lo[PT], run_n[PT];   // of a chunk of 256 months: the block's first row (from the month's first) and row count
 };
 
-__device__ __forceinline__ int64_t lower_bound_i32(const int32_t* v, int64_t lo, int64_t hi, int key) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(PT) void pool_firm_kernel(fm_pool_args a) {
     __shared__ FirmLds L;
     const Ws W = ws_of(a);
@@ -451,16 +404,10 @@ __global__ __launch_bounds__(PT) void pool_firm_kernel(fm_pool_args a) {
         L.coff[tid] = col_offset(a, zi, tid, nz) * a.col_stride;
         L.b[tid] = tid >= 1 && tid < nz - 1 ? fit[FIT_B + tid] : 0.0;
     }
-    auto stage = [&](int s, int slot) {   // threads 0 .. 15: month s's parameters
-        const int j = tid;
-        const int64_t c = col_offset(a, zi, j, nz);
-        const bool col = j >= 1 && j < nz;
-        ColPar& cp = L.cp[slot];
-        cp.lo[j] = col && a.lo ? a.lo[c * a.nseg + s] : NAN;
-        cp.hi[j] = col && a.hi ? a.hi[c * a.nseg + s] : NAN;
-        cp.piv[j] = col ? W.piv[((int64_t)s * a.nprob + p) * 16 + j] : 0.0;
+    auto stage = [&](int j, int s) {   // sixteen threads: month s's parameters into its slot
+        stage_col_par(a, zi, j, nz, s, W.piv + ((int64_t)s * a.nprob + p) * 16, L.cp[(s - a.seg_lo) & 1]);
     };
-    if (tid < ZW) stage(a.seg_lo, 0);
+    if (tid < ZW) stage(tid, a.seg_lo);
     for (int c0 = a.seg_lo; c0 < a.seg_hi; c0 += PT) {
         __syncthreads();   // the previous chunk's runs are consumed
         {
@@ -468,9 +415,9 @@ __global__ __launch_bounds__(PT) void pool_firm_kernel(fm_pool_args a) {
             int lo = 0, n = 0;
             if (s < a.seg_hi) {
                 int64_t b0, b1;
-                month_rows(a, s, &b0, &b1);
-                const int64_t x0 = lower_bound_i32(a.firm, b0, b1, f0);
-                const int64_t x1 = lower_bound_i32(a.firm, x0, b1, f0 + FB);
+                month_rows(a.seg_off, s, a.nrows, &b0, &b1);
+                const int64_t x0 = lower_bound(a.firm, b0, b1, f0);
+                const int64_t x1 = lower_bound(a.firm, x0, b1, f0 + FB);
                 const int64_t len = x1 - x0;
                 lo = (int)(x0 - b0);
                 n = (int)(len > FB ? FB : len);   // more than FB only where the codes do not ascend
@@ -482,18 +429,10 @@ __global__ __launch_bounds__(PT) void pool_firm_kernel(fm_pool_args a) {
         const int cend = a.seg_hi - c0 < PT ? a.seg_hi - c0 : PT;
         for (int m = 0; m < cend; ++m) {
             const int s = c0 + m, slot = (s - a.seg_lo) & 1;
-            if (tid >= PT - ZW && s + 1 < a.seg_hi) {   // the last sixteen threads stage the next month
-                const int j = tid - (PT - ZW);
-                const int64_t c = col_offset(a, zi, j, nz);
-                const bool col = j >= 1 && j < nz;
-                ColPar& cp = L.cp[slot ^ 1];
-                cp.lo[j] = col && a.lo ? a.lo[c * a.nseg + s + 1] : NAN;
-                cp.hi[j] = col && a.hi ? a.hi[c * a.nseg + s + 1] : NAN;
-                cp.piv[j] = col ? W.piv[((int64_t)(s + 1) * a.nprob + p) * 16 + j] : 0.0;
-            }
+            if (tid >= PT - ZW && s + 1 < a.seg_hi) stage(tid - (PT - ZW), s + 1);   // the last sixteen threads: the next month
             if (tid < L.run_n[m]) {
                 int64_t b0, b1;
-                month_rows(a, s, &b0, &b1);
+                month_rows(a.seg_off, s, a.nrows, &b0, &b1);
                 const int64_t r = b0 + L.run_lo[m] + tid;   // inside [b0, b1): the searches stay there
                 const int f = a.firm[r] - f0;
                 double z[ZW];

@@ -18,7 +18,7 @@
 
 #include <type_traits>
 
-#include "fm_common.h"
+#include "fm_reg16_dev.h"
 
 FM_PROBE_BUFFER(solve)
 
@@ -31,11 +31,6 @@ constexpr int MAXB_LDS = 8192;   // doubles of bucket sums held in LDS (64 KB ma
 constexpr int64_t SCAN_GRID = 1024;   // workgroups of the status-scanning fix-up launches
 constexpr double CHOL_REL = 1e-9;
 constexpr double EIG_REL = 1e-12;
-// A pivot below REFIT_REL of its original diagonal (1 - R^2 of a regressor on the previous
-// ones) means cond(Sxx) >~ 1e6: the normal-equation error (~eps * cond(Sxx)) could exceed
-// the 1e-9 contract, so the problem is flagged FM_ST_REFIT and re-solved from its rows by
-// fm_solve_fixup (Householder QR + SVD of R: error ~eps * cond(X), as statsmodels' SVD).
-constexpr double REFIT_REL = 1e-6;
 
 template <int MD>
 struct WaveScratch {
@@ -119,10 +114,6 @@ __device__ void jacobi_pinv(double* A, double* V, int K, const double* sxy, cons
         const double t = b0 * wi / den;
         for (int j = 0; j < K; ++j) b[j] += t * V[j * MD + i];
     }
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(v), l));
 }
 
 // Sum the month's chunk partials into LDS: BCH loads per thread in flight per chunk (a
@@ -238,7 +229,7 @@ __global__ __launch_bounds__(VT) void solve_kernel(fm_solve_args a) {
         if (__ballot(lane == K && isinf(gdiag)) != 0) st |= FM_ST_INF_IN_Y;
         if (a.gram_flags) st |= a.gram_flags[(int64_t)s * a.nmodels + m] & (FM_ST_INF_IN_X | FM_ST_INF_IN_Y);
         if (!(n >= (double)(K + 1))) {
-            for (int k = lane; k < rs; k += WAVE) a.rec[ro + k] = k == a.pmax + 1 ? n : NAN;
+            write_failed_rec(a.rec, ro, rs, a.pmax, n, lane, WAVE);
             if (lane == 0) a.status[(int64_t)s * a.nprob + p] = FM_ST_SKIPPED;
             continue;
         }
@@ -345,14 +336,7 @@ __global__ __launch_bounds__(VT) void solve_kernel(fm_solve_args a) {
         // b_{k-1} to lane k (all lanes active: a bpermute reads nothing from inactive lanes);
         // rs <= 34 < 64, so lane k writes record entry k
         const double bsh = __shfl(bi, lane > 0 ? lane - 1 : 0, WAVE);
-        for (int k = lane; k < rs; k += WAVE) {
-            double v = NAN;   // pad between the slopes and R^2
-            if (k == 0) v = icpt;
-            else if (k <= K) v = bsh;
-            else if (k == a.pmax) v = r2;
-            else if (k == a.pmax + 1) v = n;
-            a.rec[ro + k] = v;
-        }
+        write_fitted_rec(a.rec, ro, rs, a.pmax, K, icpt, bsh, r2, n, lane, WAVE);
         if (lane == 0) a.status[(int64_t)s * a.nprob + p] = st | FM_ST_FITTED;
     }
 }
@@ -1013,7 +997,7 @@ __device__ __forceinline__ Fact16 factor16(const fm_solve_args& a, const Slot16&
     const int64_t ro = ((int64_t)q.s * a.nprob + q.pp) * rs;
     const bool skip = !(n >= (double)(K + 1));
     if (q.live && skip) {
-        for (int k = i; k < rs; k += G16) a.rec[ro + k] = k == a.pmax + 1 ? n : NAN;
+        write_failed_rec(a.rec, ro, rs, a.pmax, n, i, G16);
         if (i == 0) a.status[(int64_t)q.s * a.nprob + q.pp] = t_st[q.pp] = FM_ST_SKIPPED;
     }
     const bool act0 = q.live && !skip;
@@ -1244,6 +1228,8 @@ __global__ __launch_bounds__(S16T, 3) void solve16_kernel(fm_solve_args a) {
             icpt += t_ab[zy - 1] - t_abx;
         }
         if (act0) {
+            // write_fitted_rec's layout, in this kernel's own text: through the helper (one select
+            // fewer per entry) the kernel spills four more registers
             for (int k = i; k < rs; k += G16) {
                 double v = NAN;   // pad between the slopes and R^2
                 if (k == 0) v = icpt;

@@ -314,17 +314,6 @@ constexpr int RCH = TT / RKMAX * RPT;     // 256 output rows per workgroup
 constexpr int RMAXW = 1024;
 constexpr int RSPAN = RCH + 128;          // staged rows (windows up to 129 here): 52 KB of LDS
 
-// First position of the ascending list ix[0..n) holding a value >= v (block-uniform).
-__device__ __forceinline__ int lower_bound_i32(const int32_t* ix, int n, int v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ix[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // The per-stage kernels read the fused launch's fm_ts_args (the host entry points below fill
 // the members their kernel uses; the rolling kernels write a.roll with a.kmax values per row).
 //
@@ -340,9 +329,9 @@ __global__ __launch_bounds__(TT) void rolling_kernel(fm_ts_args a) {
     const int32_t* ix = a.idx + (int64_t)p * a.nseg;
     int ra = 0, rb = cnt;
     if (a.roll_own) {
-        ra = lower_bound_i32(ix, cnt, a.seg_lo) - a.lag;
+        ra = lower_bound(ix, 0, cnt, a.seg_lo) - a.lag;
         ra = ra < 0 ? 0 : ra;
-        rb = lower_bound_i32(ix, cnt, a.seg_hi);
+        rb = lower_bound(ix, 0, cnt, a.seg_hi);
         if (c0 + RCH <= ra || c0 >= rb) return;   // block-uniform
     } else {
         // rows past the fitted-month count have no month: NaN (never left uninitialised)
@@ -917,9 +906,9 @@ __device__ void ts_rolling_wg(const fm_ts_args& a, int p, int chunk, const int* 
     if (a.roll_own && r0 < cnt) {
         // a sharded rank rolls only the rows its predictive records read: [first fitted row of
         // its months - lag, first fitted row past them)
-        int ra = lower_bound_i32(ixs, cnt, a.seg_lo) - (predictive ? a.lag : 0);
+        int ra = lower_bound(ixs, 0, cnt, a.seg_lo) - (predictive ? a.lag : 0);
         ra = ra < 0 ? 0 : ra;
-        const int rb = lower_bound_i32(ixs, cnt, a.seg_hi);
+        const int rb = lower_bound(ixs, 0, cnt, a.seg_hi);
         if (r0 + RROWS <= ra || r0 >= rb) {   // block-uniform: none of this chunk's rows needed
             if (predictive) {
                 // the chunk's predictive records are still this rank's to write: -0.0 records of

@@ -10,7 +10,8 @@
 // (A = w z of four rows, B = z of the same rows, z = [1, clip(x) - pivot]; lane (k, q) holds
 // column q of row k, as in fm_gram_dev.h, and clips its own column at the operand).  The next
 // block's loads are issued before the tiles are consumed.  At the end the four accumulators are
-// added in wave order.  So every sum depends on the sequence of used rows alone: dropped rows leave
+// added in wave order (fm_reg16_dev.h, which also holds how a problem's width, columns and column
+// parameters are read and how a record is laid out: fm_pool.hip reads them the same way).  So every sum depends on the sequence of used rows alone: dropped rows leave
 // no trace, and weights times a power of two scale every term exactly.
 //
 // Two such passes: the first, about `shift` (or 0), gives the weighted means; the second, about
@@ -20,21 +21,15 @@
 // pivot rows are broadcast by readlane), on the zero-padded 16 x 16 matrix with no test of the size.
 #include <math.h>
 
-#include "fm_common.h"
+#include "fm_reg16_dev.h"
 
 namespace fm {
 namespace {
 
 constexpr int WLT = 256;                   // threads of a workgroup
 constexpr int WNW = WLT / WAVE;            // waves
-constexpr int ZW = 16;                     // z = [1, x_1 .. x_K, y], K + 2 <= 16
-constexpr int RS = ZW + 1;                 // ring row stride (doubles): odd, so a column read spreads over the banks
 constexpr int RING_TILES = 5;              // < 64 compact rows left over + <= 256 new ones
 constexpr int RING = RING_TILES * WAVE;
-constexpr double REFIT_REL = 1e-6;         // fm_solve's: a pivot below this part of its diagonal is ill-conditioned
-constexpr double CONST_REL = 1e-20;        // centred / raw second moment at or below this: a constant column
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 struct WlsLds {
     double ring[RING * RS];   // the used rows; after a pass the four waves' accumulator images
@@ -47,41 +42,24 @@ struct WlsLds {
 };
 static_assert(WNW * ZW * ZW <= RING * RS, "the accumulator images must fit the ring");
 
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    return __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(v), l));
-}
-
 __global__ __launch_bounds__(WLT, 3) void wls_kernel(fm_wls_args a) {
     __shared__ WlsLds L;
     const int s = blockIdx.x, p = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
     const int q = lane & 15, kr = lane >> 4;   // MFMA operand: column q of row kr of a 4-row group
-    int nz = a.prob_nz[p];
-    nz = nz > a.pmax + 1 ? a.pmax + 1 : nz;   // K + 1 <= pmax: what rec and moments hold
-    nz = nz < 2 ? 2 : (nz > ZW ? ZW : nz);
+    const int nz = prob_width(a, p);
     const int K = nz - 2, K1 = K + 1;
     const int u = a.prob_level[p];
     const int32_t* zi = a.prob_z + (int64_t)p * 32;
-    int64_t b0 = a.seg_off[s], b1 = a.seg_off[s + 1];
-    b0 = b0 < 0 ? 0 : (b0 > a.nrows ? a.nrows : b0);
-    b1 = b1 > a.nrows ? a.nrows : (b1 < b0 ? b0 : b1);   // a foreign seg_off reads nothing outside [0, nrows)
-    auto panel_col = [&](int j) {   // local column j (1 .. nz-1) -> panel column, inside the panel
-        const int c = zi[j] - 1;
-        return c < 0 ? 0 : (c >= a.ncols ? a.ncols - 1 : c);
-    };
-    // this lane's operand column: its cuts and the first pass's pivot
+    int64_t b0, b1;
+    month_rows(a.seg_off, s, a.nrows, &b0, &b1);
+    // this lane's operand column: its cuts and the first pass's pivot, in registers
     const bool colq = q >= 1 && q < nz;
-    double plo = NAN, phi = NAN, psh = 0.0;
-    if (colq) {
-        const int64_t o = (int64_t)panel_col(q) * a.nseg + s;
-        if (a.lo) plo = a.lo[o];
-        if (a.hi) phi = a.hi[o];
-        if (a.shift) psh = a.shift[o];
-    }
+    const ColVal pq = col_par(a, zi, q, nz, s);
+    const double plo = pq.lo, phi = pq.hi, psh = pq.shift;
     if (tid == 0) L.flags = 0;
-    // (the slots past the list repeat y's column: the row loop then needs no per-column condition)
-    if (tid >= 1 && tid < ZW) L.coff[tid] = (int64_t)panel_col(tid < nz ? tid : nz - 1) * a.col_stride;
+    if (tid >= 1 && tid < ZW) L.coff[tid] = col_offset(a, zi, tid, nz) * a.col_stride;
     __syncthreads();
     const int rs = a.pmax + 2;
     const int64_t ro = ((int64_t)s * a.nprob + p) * rs;
@@ -158,17 +136,9 @@ __global__ __launch_bounds__(WLT, 3) void wls_kernel(fm_wls_args a) {
             if (lane == 0 && bits != 0) atomicOr(&L.flags, bits);
         }
         __syncthreads();   // every wave is done with the ring
-        // v_mfma_f64_16x16x4_f64: register r of lane (kr, q) is D[kr + 4 r][q]
-        double* img = L.ring + w * (ZW * ZW);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) img[(kr + 4 * r) * ZW + q] = acc[r];
+        gram16_store_image(acc, L.ring, w, kr, q);
         __syncthreads();
-        {
-            double g = L.ring[tid];
-#pragma unroll
-            for (int x = 1; x < WNW; ++x) g += L.ring[x * (ZW * ZW) + tid];
-            L.G[tid] = g;
-        }
+        L.G[tid] = gram16_sum_images<WNW>(L.ring, tid);
         __syncthreads();
         return total;
     };
@@ -181,7 +151,7 @@ __global__ __launch_bounds__(WLT, 3) void wls_kernel(fm_wls_args a) {
         if (pass == 0) {
             if (N < (uint32_t)K1 || L.flags != 0) {   // block-uniform
                 const uint32_t st = N < (uint32_t)K1 ? FM_ST_SKIPPED : L.flags;
-                for (int k = tid; k < rs; k += WLT) a.rec[ro + k] = k == a.pmax + 1 ? (double)N : NAN;
+                write_failed_rec(a.rec, ro, rs, a.pmax, (double)N, tid, WLT);
                 if (tid == 0) a.status[so] = st;
                 return;
             }
@@ -246,7 +216,7 @@ __global__ __launch_bounds__(WLT, 3) void wls_kernel(fm_wls_args a) {
         row[k] = good ? (lane == k ? lkk : lik) : row[k];
     }
     if (ngood != K) {   // a refused pivot (what later steps did with it is dropped here)
-        for (int k = lane; k < rs; k += WAVE) a.rec[ro + k] = k == a.pmax + 1 ? (double)N : NAN;
+        write_failed_rec(a.rec, ro, rs, a.pmax, (double)N, lane, WAVE);
         if (lane == 0) a.status[so] = FM_ST_RANK_DEF;
         return;
     }
@@ -276,14 +246,7 @@ __global__ __launch_bounds__(WLT, 3) void wls_kernel(fm_wls_args a) {
     const double r2 = 1.0 - (syy - t_sxy) / syy;
     const double icpt = readlane_f64(mu, K) - t_mu;
     const double bsh = __shfl(bi, lane > 0 ? lane - 1 : 0, WAVE);   // b_{k-1} to lane k
-    for (int k = lane; k < rs; k += WAVE) {
-        double v = NAN;   // pad between the slopes and R^2
-        if (k == 0) v = icpt;
-        else if (k <= K) v = bsh;
-        else if (k == a.pmax) v = r2;
-        else if (k == a.pmax + 1) v = (double)N;
-        a.rec[ro + k] = v;
-    }
+    write_fitted_rec(a.rec, ro, rs, a.pmax, K, icpt, bsh, r2, (double)N, lane, WAVE);
     if (lane == 0) a.status[so] = FM_ST_FITTED;
 }
 

@@ -158,7 +158,58 @@ def test_one_month_panel(E, parity_data):
             assert_series_close(h["se"][k, [0, 1, 3]].ravel(), refs[k]["se"][[0, 1, 3]].ravel(), "one month: se", RTOL)
 
 
+EDGE_LENS = (0, 1, 63, 64, 65, 255, 256, 257, 300)               # round the wave tile (64) and the block (256)
+EDGE_MODELS = [(14, (0,), (0, 1, 2)), (14, tuple(range(7)), (0, 1, 2)), (14, tuple(range(14)), (0, 1, 2))]
+
+
+def edge_panel(seed=29):
+    """Nine months of EDGE_LENS rows, 15 columns with 5 % NaN, levels 0 .. 2, ascending firm ids."""
+    rng = np.random.default_rng(seed)
+    n = sum(EDGE_LENS)
+    cols = [np.where(rng.random(n) < 0.05, np.nan, rng.normal(size=n)) for _ in range(15)]
+    return dict(cols=cols, seg_off=np.concatenate([[0], np.cumsum(EDGE_LENS)]).astype(np.int64),
+                ids=np.concatenate([np.arange(m, dtype=np.int64) * 3 + 7 for m in EDGE_LENS]),
+                level=rng.integers(0, 3, size=n).astype(np.uint8))
+
+
+def test_wls_and_pool_count_the_same_rows(E):
+    """fm_wls and fm_pool read a problem's width, columns and month rows through the same helpers: with
+    unit weights and no cuts both count exactly the rows a numpy mask counts (level >= u and no NaN
+    among the problem's columns), per month and in all, at every edge of the 64-row tile and the
+    256-row block and for K = 1, 7 and 14."""
+    d = edge_panel()
+    panel, models = _panel(E, d), _models(E, EDGE_MODELS)
+    level = _dev(E, d["level"])
+    T, n = len(EDGE_LENS), int(d["seg_off"][-1])
+    month = np.repeat(np.arange(T), EDGE_LENS)
+    want = []                                                      # [problem][month] used rows
+    for mi, u, _ in PO.problems(EDGE_MODELS):
+        y, xs, _ = EDGE_MODELS[mi]
+        use = d["level"] >= u
+        for c in list(xs) + [y]:
+            use &= ~np.isnan(d["cols"][c])
+        want.append(np.bincount(month[use], minlength=T))
+    want = np.array(want, dtype=np.int64)
+    assert want.shape == (9, T) and (want[:, 0] == 0).all() and (want[:, 2:].sum(axis=1) > 0).all()
+    assert len({tuple(w) for w in want}) == 9                      # every problem counts its own rows
+    wls = E.fm_pass_wls(panel, models, weight=torch.ones(n, dtype=torch.float64, device=level.device), level=level,
+                        nlevels=3)
+    torch.cuda.synchronize()
+    assert [(p.model, p.level, p.K) for p in wls.problems] == PO.problems(EDGE_MODELS) and wls.pmax == 15
+    nt = wls.rec.cpu().numpy()[:, :, wls.pmax + 1]                 # [T, nprob]
+    assert np.array_equal(nt, want.T.astype(np.float64))
+    for fe in (False, True):
+        res, h = _run(E, d, EDGE_MODELS, panel=panel, month_fe=fe, cov=False, resid=False)
+        assert res.pmax == wls.pmax
+        for p in range(9):
+            w = (fe, p)
+            assert int(nt[:, p].sum()) == int(h["stat"][p, 0]) == int(want[p].sum()), w
+            assert int((nt[:, p] > 0).sum()) == int(h["stat"][p, 1]) == int((want[p] > 0).sum()), w
+            assert h["stat"][p, 0] == np.floor(h["stat"][p, 0]) and h["stat"][p, 1] == np.floor(h["stat"][p, 1]), w
+
+
 # ---------------------------------------------------------------- 3. the checker panel
+
 def test_checker_panel_exact(E):
     d = PO.checker_panel()
     res, h = _run(E, d, PO.CHECKER_MODELS)

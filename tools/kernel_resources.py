@@ -18,7 +18,7 @@ HOT = ("select_pair_hk_kernelILi", "select_pair_kernelILi40", "select_fixup_univ
        "select_fixup_kernelILi20", "select_long_hk_kernelILi40", "universe_kernelILi20",
        "gram_kernelILi1ELi15ELi3ELb1", "gram_kernelILi1ELi15ELi3ELb0", "solve16_kernel", "ts_fused_kernel",
        "rolling_std_kernel", "firm_chars_kernel", "split_planes_kernel", "port_kernelILi", "fdist_kernelILi", "fcmp_kernelILi", "fhor_kernelILi", "rank_kernelILi",
-       "rank_long_kernel")
+       "rank_long_kernel", "wls_kernel", "pool_pass_kernelILi", "pool_firm_kernel")
 
 
 def bodies(s):
